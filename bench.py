@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the count path (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--kmer-size 31]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--kmer-size 31] [--dump-outputs DIR]
 
 One "step" = one pass of the whole hot path (2-bit encode -> canonical k-mers ->
 radix partition -> LDS hash aggregate -> histogram + solidity filter -> sorted
@@ -30,12 +30,14 @@ sys.path.insert(0, ROOT)
 COLLECTIVE_TIMEOUT_S = 180.0   # longest any rank waits inside one collective of the N > 1 bench before it fails loudly
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: 8.0 TB/s spec
 HBM_COPY_GBS = 6290.0   # MI355X_MICROARCH.md: measured float4 copy (79 % of spec)
+DUMP_BYTES = 64 << 20   # --dump-outputs: all files of all ranks together stay below this
+DUMP_SEED = 0xD5C0FFEE  # --dump-outputs: which rows the sample keeps (fixed, so that two builds dump the same rows)
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps of every timed loop (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default=None,
                     help="default: c2_10Mx150 (BASELINE.json configs[1]) at --gpus 1; c3_shard_25Mx150 per GPU at --gpus N > 1 "
@@ -58,7 +60,13 @@ def parse():
                          "ascending inside every output partition (DSKGPU_F_PARTITION_ORDER, one pass over the rows); global = ascending over all rows "
                          "(three passes).  The other one is timed beside it (ms_per_step_global_order / _partition_order)")
     ap.add_argument("--no-place", action="store_true", help="plain hipMalloc for the big device buffers instead of the best-placed of 8 candidates (DSKGPU_F_PLACE)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (solid rows, histogram, partition offsets, totals) as float64 "
+                         "DIR/<name>.npy files, %d MB at most: a fixed, seeded sample of the rows plus a digest of all of them" % (DUMP_BYTES >> 20))
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
 
 
 def algorithmic_bytes(stage, n_bytes, n_kmers, W=8, n_solid=None, sent_words=None, recv_words=None):
@@ -355,6 +363,46 @@ def rows_strictly_ascending(kc, dev, words):
     return ok, int(n), ab_sum
 
 
+def dump_outputs(kc, st, out_dir, world, rank, sorted_rows):
+    """--dump-outputs: what the last count of `kc` left for its caller, as float64 .npy files in out_dir (one set per rank,
+    suffixed _rank<r> when world > 1), so that two builds can be compared file for file on the same seeded inputs:
+      totals             n_kmers, n_distinct, n_solid, n_partitions
+      histogram          the abundance histogram (dskgpu_histogram)
+      partition_offsets  first row of every output partition, then the number of rows
+      rows_digest        [rows, sum of abundances, digest low 32 bits, digest high 32 bits] over ALL solid rows, in order
+      row_index          the rows the sample keeps: all of them, or a sorted draw of DUMP_SEED when they do not fit
+      kmers              those rows' k-mers as 32-bit halves, least significant first (2 per 64-bit word: exact in float64)
+      abundances         those rows' abundances
+    Without sorting (--no-sort) the engine's row order is not part of its contract: the rows are put in ascending order first."""
+    import numpy as np
+    kmers, ab = kc.rows()
+    if not sorted_rows and len(ab):
+        order = np.lexsort(kmers.T[::-1])           # (most significant word last in lexsort's key order)
+        kmers, ab = kmers[order], ab[order]
+    n, words = len(ab), kmers.shape[1]
+    arrays = {"totals": np.array([st["n_kmers"], st["n_distinct"], st["n_solid"], st["n_partitions"]]),
+              "histogram": kc.histogram(), "partition_offsets": kc.partition_offsets()}
+    m1 = np.uint64(0x9E3779B97F4A7C15)
+    h = np.arange(n, dtype=np.uint64) * m1 ^ ab.astype(np.uint64)
+    for w in range(words):
+        h = (h ^ kmers[:, w]) * np.uint64(0xBF58476D1CE4E5B9)
+        h ^= h >> np.uint64(31)
+    dig = int(h.sum(dtype=np.uint64)) if n else 0
+    arrays["rows_digest"] = np.array([n, int(ab.sum(dtype=np.uint64)), dig & 0xFFFFFFFF, dig >> 32])
+    per_row = (2 * words + 2) * 8                   # kmers halves + abundance + row_index
+    fixed = sum(a.size for a in arrays.values()) * 8 + 7 * 128      # (+ the .npy headers)
+    m = min(n, max(0, (DUMP_BYTES // world - fixed) // per_row))
+    idx = np.arange(n) if m == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, m, replace=False))
+    sel = kmers[idx]
+    arrays["row_index"] = idx
+    arrays["kmers"] = np.stack([sel & np.uint64(0xFFFFFFFF), sel >> np.uint64(32)], axis=2).reshape(len(idx), 2 * words)
+    arrays["abundances"] = ab[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.asarray(a).astype(np.float64))
+
+
 def self_launch(args):
     """`python bench.py --gpus N` started bare (no WORLD_SIZE): become the launcher of the N ranks.  This process never
     touches the GPU (torch is not even imported here): the ranks are children of torch.distributed.run, rank 0's JSON line
@@ -432,7 +480,7 @@ def main():
     n_bytes = reads.numel()
 
     stream = torch.cuda.current_stream().cuda_stream
-    # the same steps on plain hipMalloc buffers first (3 warm-up + 10 timed, same process, before any context asks for placement --
+    # the same steps on plain hipMalloc buffers first (3 warm-up + --steps timed, same process, before any context asks for placement --
     # the flag is process-wide): reported next to the headline as ms_per_step_no_place
     no_place_ms = None
     if world == 1 and not args.no_place and not args.no_place_compare:
@@ -443,10 +491,10 @@ def main():
                 kp.count()
             torch.cuda.synchronize()
             tp = time.perf_counter()
-            for _ in range(10):
+            for _ in range(args.steps):
                 kp.count()
             torch.cuda.synchronize()
-            no_place_ms = (time.perf_counter() - tp) / 10 * 1e3
+            no_place_ms = (time.perf_counter() - tp) / args.steps * 1e3
     kc = KmerCounter(kmer_size=args.kmer_size, abundance_min=args.abundance_min, device=local_rank, timing=True,
                      sort=not args.no_sort, world_size=world, rank=rank, stream=stream, place=not args.no_place and not share_gpu,      # (ranks sharing one GPU: no room for placement candidates)
                      partition_order=args.row_order == "partition")      # (every rank of a multi-GPU job orders its own share the same way)
@@ -534,6 +582,8 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     st = kc.stats()
+    if args.dump_outputs:
+        dump_outputs(kc, st, args.dump_outputs, world, rank, sorted_rows=not args.no_sort)
     # N = 1: the same steps with the OTHER row order (same context, same buffers), outside the timed region
     other_order_ms = None
     if world == 1 and not args.no_sort and not args.no_place_compare:
@@ -542,10 +592,10 @@ def main():
             kc.count()
         torch.cuda.synchronize()
         tp = time.perf_counter()
-        for _ in range(10):
+        for _ in range(args.steps):
             kc.count()
         torch.cuda.synchronize()
-        other_order_ms = (time.perf_counter() - tp) / 10 * 1e3
+        other_order_ms = (time.perf_counter() - tp) / args.steps * 1e3
         other_stage = dict(kc.stage_times())
         kc.set_row_order(args.row_order == "partition")
         kc.count()                      # (the result the checks below look at is the timed configuration's)

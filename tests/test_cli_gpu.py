@@ -295,3 +295,32 @@ def test_bench_line_contract():
     for key in ("value", "unit", "cores", "kind", "sample"):
         assert key in c, key
     assert c["kind"] == "port" and c["value"] > 0 and c["cores"] >= 1 and c["unit"] == d["unit"]
+
+
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR`: float64 .npy files of at most 64 MB that agree with the JSON line, the same in two runs with
+    the same arguments (seeded inputs), so that two builds can be compared output for output."""
+    import json
+    import sys
+    import numpy as np
+    dumps, lines = [], []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "small", "--steps", "1", "--warmup", "1", "--no-e2e", "--no-k63",
+                            "--no-human-standin", "--no-repeat-rich", "--no-place-compare", "--no-cpu-baseline", "--dump-outputs", str(d)],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr.decode(errors="replace")[-2000:]
+        lines.append(json.loads(p.stdout.decode().strip().splitlines()[-1]))
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+        dumps.append({f.stem: np.load(f) for f in d.iterdir()})
+    a, b = dumps
+    assert sorted(a) == ["abundances", "histogram", "kmers", "partition_offsets", "row_index", "rows_digest", "totals"]
+    for name in a:
+        assert a[name].dtype == np.float64 and np.array_equal(a[name], b[name]), name
+    d = lines[0]
+    assert d["steps"] == 1
+    n_solid = int(d["n_solid"])
+    assert a["totals"][:3].tolist() == [d["n_kmers"], d["n_distinct"], d["n_solid"]]
+    assert int(a["histogram"].sum()) == d["n_distinct"] and int(a["rows_digest"][0]) == n_solid == int(a["partition_offsets"][-1])
+    assert a["kmers"].shape == (len(a["row_index"]), 2) and len(a["abundances"]) == len(a["row_index"]) <= n_solid
+    assert (a["abundances"] >= 2).all() and int(a["rows_digest"][1]) >= a["abundances"].sum()

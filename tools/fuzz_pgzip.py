@@ -4,12 +4,14 @@ FASTQ / FASTA / random printable / extremely repetitive text, levels 1-9, the Z_
 flushes (empty stored blocks, short fixed-Huffman blocks), two members; chunk sizes from 8 KB (chunks shorter than the 32 KB window)
 to 256 KB, 2-8 threads.  Every file must come out byte for byte as zlib inflates it ("OK") or be declined before anything was
 handed on ("NA").   python tools/fuzz_pgzip.py [seed=1] [n=300]"""
-import gzip, zlib, subprocess, sys, os
+import gzip, zlib, subprocess, sys, os, shutil, tempfile
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 exe = os.path.join(ROOT, 'tests', 'host', 'test_pgzip')
 rng=np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 1)
 bad=0; ok=0; na=0
+tmp=tempfile.mkdtemp(prefix='fuzz_pgzip_')      # (a directory of this run's own: no fixed path shared with other users or runs)
+vgz=os.path.join(tmp,'v.gz')
 for it in range(int(sys.argv[2]) if len(sys.argv) > 2 else 300):
     kind=int(rng.integers(0,5))
     n=int(rng.integers(200,6000))
@@ -32,13 +34,15 @@ for it in range(int(sys.argv[2]) if len(sys.argv) > 2 else 300):
         z+=c.flush()
     else:
         k=len(data)//2; z=gzip.compress(data[:k],level,mtime=0)+gzip.compress(data[k:],level,mtime=0)
-    open('/tmp/v.gz','wb').write(z)
+    open(vgz,'wb').write(z)
     ch=str(int(rng.choice([8192,16384,32768,65536,262144])))
     th=str(int(rng.choice([2,3,4,8])))
-    o=subprocess.run([exe,'/tmp/v.gz',th,ch],stdout=subprocess.PIPE,stderr=subprocess.PIPE).stdout.decode().strip()
+    o=subprocess.run([exe,vgz,th,ch],stdout=subprocess.PIPE,stderr=subprocess.PIPE).stdout.decode().strip()
     if o.startswith("OK"): ok+=1
     elif o.startswith("NA"): na+=1
     else:
-        bad+=1; print("BAD", it, kind, level, mode, ch, th, len(data), len(z), o[:80]); os.system("cp /tmp/v.gz /tmp/bad_%d.gz"%it)
+        bad+=1; print("BAD", it, kind, level, mode, ch, th, len(data), len(z), o[:80]); shutil.copy(vgz,os.path.join(tmp,"bad_%d.gz"%it))
 print("ok",ok,"na",na,"bad",bad)
+if bad: print("failing inputs kept in", tmp)
+else: shutil.rmtree(tmp,ignore_errors=True)
 sys.exit(1 if bad else 0)
