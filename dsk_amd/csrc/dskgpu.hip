@@ -1,4 +1,4 @@
-// dskgpu.hip -- C-ABI (include/dskgpu.h) over the HIP kernels in kernels.h.
+// dskgpu.hip -- C-ABI (include/dskgpu.h) over the HIP kernels in kernels.h.  The row order of a result is rowsort.hip's.
 // Host-side orchestration of the count path that stands where
 // SortingCountAlgorithm<span>::execute() is called (src/DSK.cpp:60).
 // gfx950 only; there is no CPU fallback: every entry point needs a HIP device.
@@ -12,12 +12,9 @@
 
 #include <thread>
 #include <system_error>
-#include "../../include/dskgpu.h"
+#include "engine.h"
 #include "kernels.h"
 #include "superkmer.h"
-#include "rowsort.h"
-#include "rowsort2.h"
-#include "partsort.h"
 #include "rawparse.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -33,16 +30,6 @@ thread_local std::string g_create_err;
 // fill: 1.70 / 1.79), the same virtual address changes class after a free + malloc, and the kernels' "two speeds" (level 1: 3.8 /
 // 4.5 ms) follow (tools/micro/write_place.hip).  With DSKGPU_PLACE = K > 1 every allocation of >= 256 MB is the best of up to K
 // candidates, each timed with that store pattern (one-off: ~0.1 s per candidate of 10 GB); the others are freed.
-// the row sort's device scalars (matrix length, two work counters [, the ties flag]) set from KERNEL ARGUMENTS: the sorts are called many
-// times back to back from host loops, and an asynchronous copy from one host-side array would only be correct as long as the runtime
-// stages pageable copies synchronously
-// (z0, z1: two more words to clear -- the sort's "not finished in place" flag and the count of listed sub-buckets -- or null)
-__global__ void k_set_rs_scalars(u32* __restrict__ sc4, u32 len, u32 nwords, u32* __restrict__ z0 = nullptr, u32* __restrict__ z1 = nullptr) {
-    if (threadIdx.x == 0) sc4[0] = len;
-    else if (threadIdx.x < nwords) sc4[threadIdx.x] = 0u;
-    if (threadIdx.x == 32 && z0) *z0 = 0u;
-    if (threadIdx.x == 33 && z1) *z1 = 0u;
-}
 __global__ __launch_bounds__(1024) void k_place_probe(unsigned long long* __restrict__ out, unsigned long long n) {
     const unsigned long long per_block = n / gridDim.x, per_stream = per_block / 512;
     unsigned long long* base = out + (unsigned long long)blockIdx.x * per_block;
@@ -66,6 +53,8 @@ float place_probe_ms(void* p, size_t bytes) {
     (void)hipEventDestroy(a); (void)hipEventDestroy(b);
     return best;
 }
+}  // namespace
+
 hipError_t placed_malloc(void** out, size_t bytes) {
     if (g_place_k < 0) { const char* e = getenv("DSKGPU_PLACE"); g_place_k = e ? atoi(e) : 0; }      // (dskgpu_create with DSKGPU_F_PLACE sets 8)
     size_t free_b = 0, total_b = 0;
@@ -92,37 +81,8 @@ hipError_t placed_malloc(void** out, size_t bytes) {
     return hipSuccess;
 }
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        // growing a buffer that exists: 6 % on top, so that a size that wobbles by a few per cent from pass to pass (slices from
-        // sampled loads) does not free and allocate tens of GB again -- near a full HBM that took a second
-        size_t want = ((p ? bytes + bytes / 16 : bytes) + 255) & ~size_t(255);
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        hipError_t e = placed_malloc(&p, want);
-        if (e == hipSuccess) cap = want; else p = nullptr;
-        return e;
-    }
-    // grow, keeping the first `keep` bytes (device-to-device copy on `stream`); returns 0 on success
-    int ensure_keep(size_t bytes, size_t keep, hipStream_t stream) {
-        if (bytes <= cap) return 0;
-        void* np = nullptr;
-        size_t want = ((std::max(bytes, cap + cap / 2) + 255) & ~size_t(255));
-        if (hipMalloc(&np, want) != hipSuccess) return -1;
-        if (keep && p) {
-            if (hipMemcpyAsync(np, p, keep, hipMemcpyDeviceToDevice, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { (void)hipFree(np); return -1; }
-        }
-        if (p) (void)hipFree(p);
-        p = np; cap = want;
-        return 0;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
+namespace {
 
-enum Scalar { SC_NCH1 = 0, SC_MLEN1, SC_NCH2, SC_MLEN2, SC_OVERFLOW, SC_F, SC_SORTFLAG, SC_OVF2, SC_OVF1, SC_RSLEN, SC_RSWORK, SC_RSWORK2, SC_RSTIES, SC_EXT, SC_NCHAINED, SC_NCH_S, SC_MLEN_S, SC_WORK2, SC_COUNT = 24 };
 // everything the host wants to know after the count stage of a pass, gathered into ONE 80-byte record: seven 4- and 32-byte copies from
 // four buffers into pageable host memory cost ~20 us of idle GPU each (the runtime stages every one of them), 0.12 ms of a 14 ms step
 __global__ void k_gather_back(const u32* __restrict__ sc, const u32* __restrict__ nsolid_total, const u32* __restrict__ nk, const u64* __restrict__ gstats,
@@ -144,220 +104,9 @@ __global__ __launch_bounds__(256) void k_setup_pass(u32* __restrict__ sc, Scalar
     for (u32 i = t; i < nh; i += gridDim.x * 256) ghist[i] = 0ull;
     for (u64 i = t; i < nzero; i += (u64)gridDim.x * 256) zero[i] = 0u;
 }
-// the row sort's two words for the host (its "could not finish in place" flag, the number of listed sub-buckets), put behind the abundance
-// histogram so that the end of a step is ONE copy
-__global__ void k_sort_back(const u32* __restrict__ sc, const u32* __restrict__ ovs, u64* __restrict__ out) {
-    if (threadIdx.x == 0) { out[0] = sc[SC_SORTFLAG]; out[1] = ovs ? ovs[0] : 0u; }
-}
-#ifndef SORT_TOP_BITS
-#define SORT_TOP_BITS 32u      // 4 radix passes; 40 bits (5 passes) cost 0.3 ms more on 43 M rows, the in-place run fix-up absorbs the extra ties
-#endif
-
-struct Stage { const char* name; hipEvent_t ev; };
-
 }  // namespace
 
-// Test / experiment switches (NOTEBOOK.md "Environment switches"): read ONCE from the environment when a context is
-// created; none of them changes results.  The launch paths only look at this struct.
-struct Tuning {
-    bool no_opt1 = false, no_opt2 = false;      // DSKGPU_NO_OPT1 / _NO_OPT2: exact histogram + scan path at level 1 / at both levels
-    bool no_aligned = false;                    // DSKGPU_NO_ALIGNED: plain write-out for key-array scatters
-    u32 rs_heavy = 0;                           // DSKGPU_RS_HEAVY: rows of a first-digit bucket above which the row sort gives up (tests)
-    u32 rs_bbits = 0;                           // DSKGPU_RS_BBITS: forced width of the row sort's second digit (8..10; tests)
-    u32 rs_block_rows = 0;                      // DSKGPU_RS_BLOCK_ROWS: largest sub-bucket the hand-written row sort orders itself (tests: provoke its fallback)
-    bool sk_exact = false, no_recsrc = false;   // DSKGPU_SK_EXACT, DSKGPU_NO_RECSRC (multi-GPU sender layout / receiver source)
-    u32 opt_cap = 0;                            // DSKGPU_OPT_CAP: forced level-2 region size (keys)
-    u64 opt_slice = 0;                          // DSKGPU_OPT_SLICE: forced level-1 slice size (keys)
-    u64 sk_slice = 0, sk_minslice = 2000;       // DSKGPU_SK_SLICE, DSKGPU_SK_MINSLICE
-    u32 table_maxload = 0;                      // DSKGPU_TABLE_MAXLOAD: distinct keys a count table may hold (forces the finer-partition retry)
-    long long max_ext = -1;                     // DSKGPU_MAX_EXT: size of the extension-region pool of the level-2 scatter (tests: 0 = no chains)
-    bool no_sample = false;                     // DSKGPU_NO_SAMPLE: level-1 slices from the mean load instead of the sampled per-bin loads
-    bool no_heavy = false;                      // DSKGPU_NO_HEAVY: no k-mer is counted apart by the level-1 scatter
-    bool verbose = false;                       // DSKGPU_VERBOSE: trace of the plan decisions on stderr
-    bool no_level0 = false; u32 l0_passes = 0;  // DSKGPU_NO_LEVEL0: every pass of a multi-pass count re-generates its keys; DSKGPU_L0_PASSES=n: passes per level-0 sweep (tests)
-    u64 rs_max_rows = 0;                        // DSKGPU_RS_MAX_ROWS: most rows the MSD row sort takes in one piece (tests: the group-wise path of huge row sets on a small input)
-    u32 ps_maxc = 0;                            // DSKGPU_PS_MAXC: rows sharing a value bin that the partition-order sort still orders (tests: 1 provokes its fallback to the global order)
-    bool sk_generic = false;                    // DSKGPU_SK_GENERIC: the sender kernels with k and m at run time even for k = 31 / 63 (tests: both forms write the same records)
-    bool l0_keys = false;                       // DSKGPU_L0_KEYS: level 0 as key arrays (k_level0) even where the record-based one applies (experiments, tests)
-    u32 mp_pass_mkeys = 0;                      // DSKGPU_MP_PASS_MKEYS: keys (millions) per pass of an input that needs several passes (default 1000)
-    u64 rs_slab_rows = 0;                       // DSKGPU_RS_SLAB_ROWS: rows per slab of the row sort for >= 2^32 rows (tests: forces that path, with small slabs, on a small input)
-    void read() {
-        auto on = [](const char* n) { return getenv(n) != nullptr; };
-        auto num = [](const char* n, u64 dflt) { const char* e = getenv(n); return e ? (u64)atoll(e) : dflt; };
-        no_opt1 = on("DSKGPU_NO_OPT1"); no_opt2 = on("DSKGPU_NO_OPT2"); no_aligned = on("DSKGPU_NO_ALIGNED");
-        sk_exact = on("DSKGPU_SK_EXACT");
-        no_recsrc = on("DSKGPU_NO_RECSRC");
-        opt_cap = (u32)num("DSKGPU_OPT_CAP", 0) & ~7u; opt_slice = num("DSKGPU_OPT_SLICE", 0) & ~7ull;
-        sk_slice = num("DSKGPU_SK_SLICE", 0); sk_minslice = num("DSKGPU_SK_MINSLICE", 2000);
-        table_maxload = (u32)num("DSKGPU_TABLE_MAXLOAD", 0);
-        max_ext = getenv("DSKGPU_MAX_EXT") ? atoll(getenv("DSKGPU_MAX_EXT")) : -1;
-        no_sample = on("DSKGPU_NO_SAMPLE"); no_heavy = on("DSKGPU_NO_HEAVY"); verbose = on("DSKGPU_VERBOSE"); no_level0 = on("DSKGPU_NO_LEVEL0"); l0_passes = (u32)num("DSKGPU_L0_PASSES", 0); mp_pass_mkeys = (u32)num("DSKGPU_MP_PASS_MKEYS", 0); rs_max_rows = num("DSKGPU_RS_MAX_ROWS", 0); l0_keys = on("DSKGPU_L0_KEYS"); sk_generic = on("DSKGPU_SK_GENERIC"); ps_maxc = (u32)num("DSKGPU_PS_MAXC", 0);
-        rs_slab_rows = num("DSKGPU_RS_SLAB_ROWS", 0);
-        rs_block_rows = (u32)num("DSKGPU_RS_BLOCK_ROWS", 0); rs_bbits = (u32)num("DSKGPU_RS_BBITS", 0); rs_heavy = (u32)num("DSKGPU_RS_HEAVY", 0);
-    }
-};
-
-// state of a per-bank count in steps (banks_begin .. banks_finish below)
-struct BankJob { dskgpu_config cfg; const uint8_t* base; u64 total; std::vector<u64> ends; u64 nu, tot_kmers; u32 passes, retries; bool active = false; };
-
-struct dskgpu_ctx {
-    dskgpu_config cfg{};
-    BankJob bank_job{};
-    Tuning tune;
-    int W = 1;
-    int words_out = 1;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    int num_cu = 256;
-    std::string err;
-
-    // input
-    DevBuf reads_own; u64 reads_len = 0;
-    void* pin[2] = {nullptr, nullptr}; hipEvent_t pin_ev[2] = {nullptr, nullptr}; bool pin_used[2] = {false, false}; int pin_next = 0;   // pinned H2D staging
-    const uint8_t* d_reads = nullptr; u64 n_bytes = 0;
-    // dskgpu_push_raw: file text parsed on the device; the stream's length is on the device (RawState) until raw_finish reads it back
-    DevBuf raw_in, raw_blk, raw_boff, raw_bstate, raw_state;
-    bool raw_pending = false; u64 raw_base = 0, raw_ub = 0;      // the stream's length before the raw pushes / an upper bound of it now
-
-    DevBuf packed, inval;          // K1 output
-    DevBuf bufA, bufB;             // partition ping-pong
-    DevBuf mat1, mat2, sums, descs1, descs2, seg, fstart, nsolid, scalars, ghist, gstats, chain_next;
-    DevBuf fix_list;               // multi-word row sort: [count | (first row, rows) x FIX_LIST_CAP] of the prefix runs above FIX_CAP rows
-    DevBuf rs_g[4];                // row sort: the gathered rows of the listed sub-buckets, one buffer per round (sort_oversize)
-    DevBuf rs_del, rs_lens;        // row sort of >= 2^32 rows: per (slab, bin) 64-bit output offsets; the slabs' matrix lengths
-    std::vector<u64> h_rs_del; std::vector<u32> h_rs_lens, h_rs_lin;
-    DevBuf rs_ovs;                 // row sort: [count | (offset, rows, bits left) x RS_OVS_CAP] of the sub-buckets listed for another round
-    std::vector<u32> h_ovs;
-    u64* rs_res_k = nullptr; u32* rs_res_v = nullptr; u64* rs_tmp_k = nullptr; u32* rs_tmp_v = nullptr;   // the partially sorted rows and their scratch twin (sort_oversize)
-    DevBuf smp_keys;               // records: the sample expanded to a key array (16 slots per candidate record, sentinel pads)
-    DevBuf smp_mat, smp_descs, boff;   // sampled level-1 loads: chunk x bin matrix of the sample tiles, their descriptors; per-bin slice offsets
-    DevBuf dbg, l0buf; DevBuf hv_lut, hv_collect, hv_buf; // heavy k-mers: bin -> collect slot, collected sample keys; [keys | counts | rows] of the k-mers counted apart
-    std::vector<unsigned char> h_hv_lut; std::vector<u32> h_hv_cnt, h_hv_step; std::vector<u64> h_hv_coll, h_hv_keys;
-    std::vector<ChunkDesc> h_descs_s; std::vector<u64> h_cbeg; std::vector<u32> h_boff; std::vector<u64> h_mom; std::vector<double> h_load, h_spread, h_seg_work;
-    DevBuf out_w[4], srt_w[4], acc_w[4];   // rows as struct-of-arrays: word i of every row in [i]
-    DevBuf out_ab, srt_ab, srt_tmp, srt_idx, srt_idx2, srt_k, srt_k2, abund2, acc_ab;   // srt_k2: one record per row for the multi-word gather
-    u64 max_keys_per_pass = 0;     // 0 = as many as 32-bit offsets allow
-    // multi-bank mode (solidity kinds, 2-D histogram)
-    std::vector<u64> bank_ends;    // end offset of every declared bank in the read stream
-    DevBuf u_w[4], s_w[4], u_val, s_val, m_flag, m_pos, m_sum, gh2d;
-    std::vector<u64> hist2d;
-    std::vector<u32> h_starts;     // explicit-key exchange: first key of every owner in the send buffer
-    std::vector<u64> h_rstart;     // record exchange: first RECORD of every owner in the send buffer (64-bit: no limit on a rank's shard)
-    std::vector<u32> h_sk_cells;   // ... records per (owner, chunk) as the sizing pass counted them
-    std::vector<u64> h_sk_cb64;    // ... exact layout: their exclusive scan (owner-major) = record index of every (owner, chunk) pair
-    DevBuf sk_cb64;                // ... the same on the device (k_sk_scatter<false>)
-    // multi-GPU exchange as super-k-mer records (superkmer.h)
-    bool enc_keep = false;         // dskgpu_encode_reads: packed / inval hold the 2-bit form of the current reads and the ASCII bytes are gone (d_reads == nullptr)
-    bool enc_fresh = false;        // packed / inval hold the encoding of the current reads, left by dskgpu_mg_sample for the sender's sizing pass of the same step
-    bool sk_mode = false, sk_prepared = false;
-    bool sk_slices = false;        // the prepared send layout is slices from a sampled estimate (else exact offsets)
-    bool sk_exact = false;         // a slice overflowed on these reads: exact counts from now on
-    SkParams sk_sp{};
-    DevBuf sk_sums, sk_cbase, sk_keys, sk_table, sk_load, sk_sent, sk_lay;      // sk_lay: [region base per owner: u64 x 64][slice per owner: u32 x 64] of a record-based level-0 sweep
-    u64 last_rows = 0;             // solid rows of the last count of the current reads (0 = not counted yet): sizes what a multi-pass count keeps free for its rows
-    bool rec_l0_off = false;       // these reads do not take the record-based level 0 (a slice of its sampled layout overflowed)
-    u64 h_sk_sent[SK_MAX_OWNERS] = {0};      // k-mers inside the records the last mg_scatter wrote for every owner
-    u64 h_sk_est[SK_MAX_OWNERS] = {0};       // sampled layout: estimated k-mers per owner (k_sk_hist on every 16th tile, scaled)
-    u32 sk_nslices = 0;                      // dskgpu_mg_slices_prepare: slices of the prepared step (0 = none prepared)
-    u64 rec_hint = 0;                        // dskgpu_mg_count_sized: the caller's k-mer total of the records (0 = none)
-    bool rec_hint_est = false;               // ... an estimate (sliced step): sizes the fast path only, never checked against the result
-    std::vector<u64> rec_slice_end;          // dskgpu_mg_count_sliced: record index where every slice ends; empty = one piece
-    dskgpu_slice_gate rec_gate = nullptr; void* rec_gate_user = nullptr; u32 rec_gated = 0;      // slices whose arrival the stream already waits for
-    bool rec_gate_failed = false;            // a gate said its slice will never arrive: the count stops (DSKGPU_E_STATE)
-    std::vector<u32> h_slice_chunk;          // first level-1 chunk of every slice (+ the end)
-    DevBuf cur_state;                        // parked write cursors of the level-1 blocks between the launches of a sliced receive
-    bool rec_sized = false;                  // per-chunk k-mer sums of the records are on the device (k_sk_count ran)
-    std::vector<uint8_t> h_table;  // the repartition table in use (SK_BUCKETS owners; default: bucket scaled to the world size)
-    bool table_dirty = true;       // h_table not yet copied to sk_table
-    std::vector<u32> h_sk_sums; std::vector<u64> h_sk_cbase;
-    // records handed to dskgpu_mg_count: the level-1 scatter reads them directly (SRC 2); expanded lazily for the exact path
-    const u64* rec_src = nullptr; u64 rec_n = 0; u64 rec_nch = 0, rec_rpc = 0; bool rec_expanded = false;
-    int sort_back = 0; u64* hist_pin = nullptr; size_t hist_pin_n = 0;      // (sort_back: 1 = flag + sub-bucket count still on the device, 2 = flag only; see k_sort_back)
-    u64* land = nullptr;                             // 64 KB of pinned host memory: where the small per-step read-backs land (landing())
-    DevBuf back_dev; u64* back_host = nullptr;      // the count stage's read-back record (k_gather_back) and its pinned landing zone
-    u32 h_back[4] = {0}; u64 h_stats[4] = {0}; u32 h_ovf2 = 0, h_ovf1 = 0, h_ext = 0; u64 h_nvalid = 0; bool have_nvalid = false;
-    u64* fb_src_k = nullptr; u32* fb_src_v = nullptr; u64* fb_dst_k = nullptr; u32* fb_dst_v = nullptr;   // one-word row sort: where the full-width fallback finds a permutation of the rows / leaves them sorted
-    bool sentinel_ok = true;       // the all-ones key is not the mixed form of a canonical k-mer of this k (checked at create)
-    bool opt1_off = false;         // same for the histogram-free level-1 scatter (block-owned slices)
-    bool mw_v3_off = false;        // the top-word table of k_count2v3 met two k-mers it cannot tell apart on these reads: k_count_mw from now on
-    bool opt2_off = false;         // the fixed-capacity level-2 scatter overflowed on these reads: use the exact path   // host landing zone of the async size read-back
-    std::vector<ChunkDesc> h_descs1, h_descs2;
-    std::vector<const void*> big_lds_fns;   // kernels whose dynamic-LDS limit this context has raised (allow_big_lds)
-    u32 h_sc[SC_COUNT] = {0};      // host mirror of the device scalars (kept alive across async copies)
-
-    // the solid rows of a single one-word pass where the count kernel left them (run_one_pass): the row sort's first step reads them there
-    // instead of a dense copy made by k_compact (rowsort.h: RsSparse)
-    u32 job_passes = 1;            // passes of the running count as run_pipeline sees them (a pass of a record-based multi-pass count runs as "pass 0 of 1" inside run_one_pass)
-    struct SparseRows { bool valid = false; RsSparse s{}; u64 n_sparse = 0; const u64* tail_k = nullptr; const u32* tail_v = nullptr; u32 n_tail = 0; } sp_rows;
-    // multi-pass jobs: where a pass may put its dense rows straight away -- the job's accumulators, from row `rows` on (run_pipeline sets it
-    // once they are sized; run_one_pass sets `took` when it did: the pass's rows are then already appended)
-    struct RowSink { bool active = false, took = false; u32* ab = nullptr; u64* w[4] = {nullptr, nullptr, nullptr, nullptr}; u64 rows = 0, cap = 0; } sink;
-    struct SparseRows2 { bool valid = false; Rs2Sparse s{}; u64 n_sparse = 0; Rows2C tail{nullptr, nullptr, nullptr}; u32 n_tail = 0; } sp_rows2;      // (two-word rows)
-    // results
-    bool have_result = false;
-    bool sort_partial = false;
-    // DSKGPU_F_PARTITION_ORDER (partsort.h): the rows ascending inside each output partition only.  part_mode: the last result is laid
-    // out that way, h_part_off[p] = first row of partition p (n_parts + 1 entries, pinned); part_off_this_count: the flag was raised
-    // (a partition or a bin above what a block orders) and this count takes the global sort instead
-    bool part_mode = false, part_off_this_count = false; u32 n_parts = 0; u32* h_part_off = nullptr; size_t h_part_cap = 0; DevBuf part_off;
-    SparseRows sp_rows_saved; SparseRows2 sp_rows2_saved;
-    // ... and for the passes of a multi-pass count: every pass orders its rows partition by partition straight into the job's row arrays
-    // (one k_part_sort launch instead of k_compact), the offsets of its partitions -- relative to the pass's first row -- go to
-    // mp_part_off[off_index ..], one flag (mp_flag) serves the whole job; at the end the offsets become 64-bit row numbers (h_part_off64)
-    struct MpPart { u64 row_base; u32 nparts, off_index; };
-    std::vector<MpPart> mp_parts; DevBuf mp_part_off, mp_flag; u32 mp_off_used = 0; bool mp_part_ok = false;
-    std::vector<u64> h_part_off64; std::vector<u32> h_mp_off;
-    bool rows2_in_scratch = false; Rows2 rows2_scratch{};      // two-word rows above RS_MAX_ROWS: the result (and the fallback's input) is the scratch copy
-    u64 n_rows = 0;
-    const u64* res_w[4] = {nullptr, nullptr, nullptr, nullptr}; const u32* res_ab = nullptr;
-    dskgpu_stats stats{};
-    std::vector<u64> hist;
-
-    // timing
-    std::vector<Stage> marks;
-    std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
-    std::vector<const char*> st_names; std::vector<float> st_ms;
-
-    void mark(const char* name) {
-        if (!(cfg.flags & DSKGPU_F_TIMING)) return;
-        if (ev_used == ev_pool.size()) { hipEvent_t e; (void)hipEventCreate(&e); ev_pool.push_back(e); }
-        hipEvent_t e = ev_pool[ev_used++];
-        (void)hipEventRecord(e, stream);
-        marks.push_back({name, e});
-    }
-    void resolve_marks() {   // after a stream sync; appends to st_names/st_ms
-        for (size_t i = 0; i + 1 < marks.size(); ++i) {
-            float ms = 0; (void)hipEventElapsedTime(&ms, marks[i].ev, marks[i + 1].ev);
-            // one entry per stage name: the passes of a multi-pass count (and the retries of a pass) add up
-            size_t at = 0;
-            while (at < st_names.size() && std::strcmp(st_names[at], marks[i + 1].name) != 0) ++at;
-            if (at == st_names.size()) { st_names.push_back(marks[i + 1].name); st_ms.push_back(ms); } else st_ms[at] += ms;
-        }
-        marks.clear(); ev_used = 0;
-    }
-};
-
 namespace {
-
-#define CK(expr)                                                                             \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            ctx->err = std::string(#expr) + ": " + hipGetErrorString(e_);                    \
-            return (e_ == hipErrorOutOfMemory) ? DSKGPU_E_NOMEM : DSKGPU_E_DEVICE;           \
-        }                                                                                    \
-    } while (0)
-
-#define CKL(what)                                                                            \
-    do {                                                                                     \
-        hipError_t e_ = hipGetLastError();                                                   \
-        if (e_ != hipSuccess) {                                                              \
-            ctx->err = std::string(what) + ": " + hipGetErrorString(e_);                     \
-            return DSKGPU_E_DEVICE;                                                          \
-        }                                                                                    \
-    } while (0)
-
-int fail(dskgpu_ctx* ctx, int code, const std::string& msg) { ctx->err = msg; return code; }
 
 // Pinned host memory for the small read-backs a step waits on (a copy into pageable memory is staged by the runtime: ~10 us more of idle
 // GPU per host round trip).  nullptr when the allocation fails or the request is larger: the caller then copies into its own buffer.
@@ -412,6 +161,8 @@ int encode_current(dskgpu_ctx* ctx, u64* nwords_out) {
     return run_encode(ctx, ctx->d_reads, ctx->n_bytes, nwords_out);
 }
 
+}  // namespace
+
 // ---- scan launcher: exclusive scan of a[0..*d_len) in place, total -> a[*d_len]
 int run_scan(dskgpu_ctx* ctx, u32* a, const u32* d_len, u64 max_len) {
     const u64 nb = std::max<u64>(1, (max_len + SCAN_BLK - 1) / SCAN_BLK);
@@ -425,12 +176,14 @@ int run_scan(dskgpu_ctx* ctx, u32* a, const u32* d_len, u64 max_len) {
 
 // Kernels that stage a whole tile need more dynamic LDS than the 64 KB default: raise the limit once per context
 // (a context is bound to one device and driven by one thread, so no process-wide flag is involved).
-int allow_big_lds(dskgpu_ctx* ctx, const void* fn, int bytes = 160 * 1024) {      // (bytes: kernels with static LDS next to the dynamic block ask for what they use)
+int allow_big_lds(dskgpu_ctx* ctx, const void* fn, int bytes) {
     for (const void* f : ctx->big_lds_fns) if (f == fn) return DSKGPU_OK;
     CK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
     ctx->big_lds_fns.push_back(fn);
     return DSKGPU_OK;
 }
+
+namespace {
 
 size_t scatter_lds(int W, u32 P, bool opt = false) { return (size_t)SC_NT * (16 / W) * 8 * W + (size_t)P * (opt ? 20 : 16) + 4 + 17 * 4 + 16 + (opt ? 8 + L0_MAX_PASSES * 8 : 0); }   // opt: + the slice ends (+ the region bases of a level-0 sweep)
 
@@ -662,835 +415,6 @@ void build_descs1_slices(dskgpu_ctx* ctx, u64 tile, u64 max_chunks, u32* nch_out
     ctx->h_slice_chunk[S] = (u32)ctx->h_descs1.size();
     for (auto& d : ctx->h_descs1) d.stride = (u32)ctx->h_descs1.size();
     *nch_out = (u32)ctx->h_descs1.size();
-}
-
-}  // namespace
-
-namespace {
-
-// Index permutation that sorts n rows of W words (struct-of-arrays in `rows`) ascending: W stable 64-bit
-// radix passes, least significant word first.  Result in ctx->srt_idx.
-int sort_index_multiword(dskgpu_ctx* ctx, const u64* const* rows, u64 n, int W);
-int sort_index_multiword(dskgpu_ctx* ctx, DevBuf* rows, u64 n, int W) {
-    const u64* p[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int x = 0; x < W; ++x) p[x] = rows[x].as<u64>();
-    return sort_index_multiword(ctx, p, n, W);
-}
-int sort_index_multiword(dskgpu_ctx* ctx, const u64* const* rows, u64 n, int W) {
-    CK(ctx->srt_k.ensure(n * 8));
-    CK(ctx->srt_idx.ensure(n * 4));
-    CK(ctx->srt_idx2.ensure(n * 4));
-    DevBuf& keys_sorted = ctx->s_val;           // scratch for the sorted keys of a pass (not needed afterwards)
-    CK(keys_sorted.ensure(n * 8));
-    const unsigned gb = (unsigned)((n + 255) / 256);
-    const unsigned top_bits = std::min(64u, std::max(1u, 2u * ctx->cfg.kmer_size - 64u * (unsigned)(W - 1)));
-    u32* idx = ctx->srt_idx.as<u32>(); u32* idx2 = ctx->srt_idx2.as<u32>();
-    hipLaunchKernelGGL(k_iota, dim3(gb), dim3(256), 0, ctx->stream, idx, n);
-    size_t tmp = 0, tmp2 = 0;
-    // LIBRARY SORT (rocprim), labelled FALLBACK: index permutation of multi-word rows in full-width order (W stable passes), behind a raised flag only
-    CK(rocprim::radix_sort_pairs(nullptr, tmp, ctx->srt_k.as<u64>(), keys_sorted.as<u64>(), idx, idx2, (size_t)n, 0u, 64u, ctx->stream));
-    CK(rocprim::radix_sort_pairs(nullptr, tmp2, ctx->srt_k.as<u64>(), keys_sorted.as<u64>(), idx, idx2, (size_t)n, 0u, top_bits, ctx->stream));
-    CK(ctx->srt_tmp.ensure(std::max(tmp, tmp2)));
-    for (int x = 0; x < W; ++x) {
-        const u64* src = rows[x];
-        const unsigned bits = x == W - 1 ? top_bits : 64u;
-        if (x == 0) {
-            CK(rocprim::radix_sort_pairs(ctx->srt_tmp.p, tmp, src, keys_sorted.as<u64>(), idx, idx2, (size_t)n, 0u, bits, ctx->stream));
-        } else {
-            hipLaunchKernelGGL(k_gather<u64>, dim3(gb), dim3(256), 0, ctx->stream, ctx->srt_k.as<u64>(), src, idx, n);
-            size_t t = x == W - 1 ? tmp2 : tmp;
-            CK(rocprim::radix_sort_pairs(ctx->srt_tmp.p, t, ctx->srt_k.as<u64>(), keys_sorted.as<u64>(), idx, idx2, (size_t)n, 0u, bits, ctx->stream));
-        }
-        std::swap(idx, idx2);
-    }
-    if (idx != ctx->srt_idx.as<u32>()) std::swap(ctx->srt_idx, ctx->srt_idx2);
-    CKL("sort_index_multiword");
-    return DSKGPU_OK;
-}
-
-// full-width order of multi-word rows: W stable radix passes over an index permutation, then gathers
-int sort_rows_full_multiword(dskgpu_ctx* ctx, u64 n) {
-    const int W = ctx->W;
-    int rc = sort_index_multiword(ctx, ctx->out_w, n, W);
-    if (rc) return rc;
-    const unsigned gb = (unsigned)((n + 255) / 256);
-    const u32* idx = ctx->srt_idx.as<u32>();
-    CK(ctx->srt_ab.ensure(n * 4));
-    for (int x = 0; x < W; ++x) {
-        CK(ctx->srt_w[x].ensure(n * 8));
-        hipLaunchKernelGGL(k_gather<u64>, dim3(gb), dim3(256), 0, ctx->stream, ctx->srt_w[x].as<u64>(), ctx->out_w[x].as<u64>(), idx, n);
-        ctx->res_w[x] = ctx->srt_w[x].as<u64>();
-    }
-    hipLaunchKernelGGL(k_gather<u32>, dim3(gb), dim3(256), 0, ctx->stream, ctx->srt_ab.as<u32>(), ctx->out_ab.as<u32>(), idx, n);
-    CKL("sort_rows");
-    ctx->res_ab = ctx->srt_ab.as<u32>();
-    return DSKGPU_OK;
-}
-
-// ---- hand-written MSD radix sort (rowsort.h) of n (64-bit key, 32-bit value) pairs on the `total` low bits of the key, in place
-// (tk / tv: scratch of the same size).  One-word rows: (k-mer value, abundance); multi-word rows: (top 63 bits of the value,
-// row index).  Whatever the kernels do not order themselves raises SC_SORTFLAG (zeroed here): the caller falls back to a
-// full-width library sort (k / v and tk / tv each hold a complete permutation of the pairs either way).
-int msd_sort_pairs(dskgpu_ctx* ctx, u64* k, u32* v, u64* tk, u32* tv, u64 n, int total, bool reset_flags = true, u32 base = 0, const dskgpu_ctx::SparseRows* spr = nullptr) {
-    // second digit: 8 bits up to 96 M rows, 9 up to 192 M, 10 beyond (sub-buckets stay near 200 rows: one wave each in step C)
-    int wantB = n <= (96ull << 20) ? 8 : n <= (192ull << 20) ? 9 : 10;
-    if (ctx->tune.rs_bbits >= 8 && ctx->tune.rs_bbits <= 10) wantB = (int)ctx->tune.rs_bbits;      // tests
-    const int bA = std::min(RS_ABITS, total), r1 = total - bA, bB = std::min(wantB, r1), r2 = r1 - bB, bC = std::min(8, r2), r3 = r2 - bC;
-    const u32 BB = 1u << wantB;
-    RsSpec sp{r1, r2, r3, (1u << bA) - 1u, (1u << bB) - 1u, (1u << bC) - 1u};
-    // chunks of step A: about 64 K rows each, a multiple of the CU count of them (whole rounds of blocks), at least one tile each
-    const u64 ncu = (u64)ctx->num_cu;
-    u64 nch = (n + 65535) / 65536;
-    nch = (nch + ncu - 1) / ncu * ncu;
-    nch = std::max<u64>(1, std::min<u64>(nch, (n + RS_TILE - 1) / RS_TILE));
-    u64 chunk = (n + nch - 1) / nch;
-    nch = (n + chunk - 1) / chunk;
-    // sparse source (spr: the rows still lie in the count kernel's regions): chunks = groups of qpc consecutive sub-partitions (about 64 K
-    // rows, at most RS_SP_MAXQ sub-partitions), + one chunk for the dense tail (the rows of the k-mers counted apart)
-    RsSparse sps{}; u64 nch_sp = 0;
-    if (spr) {
-        sps = spr->s;
-        const u64 F = sps.F;
-        u64 want = std::max<u64>(1, (spr->n_sparse + 65535) / 65536);
-        want = (want + ncu - 1) / ncu * ncu;
-        u64 qpc = std::max<u64>(1, (F + want - 1) / want);
-        if (qpc > RS_SP_MAXQ) qpc = RS_SP_MAXQ;
-        nch_sp = (F + qpc - 1) / qpc;
-        sps.qpc = (u32)qpc;
-        nch = nch_sp + (spr->n_tail ? 1 : 0);
-        chunk = spr->n_tail;                                              // (the tail is one chunk)
-    }
-    const u64 M = (u64)RS_ABINS * nch;
-    if (M >= 0xFFFFFFF0ull) return fail(ctx, DSKGPU_E_ARG, "row sort: chunk matrix too large");
-    const u64 nsubw = (u64)RS_ABINS * (BB + 1);                           // sub-bucket starts; behind them the list of large sub-buckets
-    CK(ctx->srt_tmp.ensure((M + 2 + 2 * nsubw + 16) * 4));
-    u32* matrix = static_cast<u32*>(ctx->srt_tmp.p);
-    u32* sub = matrix + M + 2;
-    u32* biglist = sub + nsubw;
-    u32* sc = ctx->scalars.as<u32>();
-    CK(ctx->rs_ovs.ensure((1 + 3 * RS_OVS_CAP) * 4));
-    hipLaunchKernelGGL(k_set_rs_scalars, dim3(1), dim3(64), 0, ctx->stream, sc + SC_RSLEN, (u32)M, reset_flags ? 4u : 3u,      // (length, two work counters [, ties seen])
-                       reset_flags ? sc + SC_SORTFLAG : (u32*)nullptr, reset_flags ? ctx->rs_ovs.as<u32>() : (u32*)nullptr);
-    const size_t ldsA = RsLds<RS_ABINS, RS_TILE>::bytes;
-    const size_t ldsB = BB == 256 ? RsLds<256, RS_BTILE>::bytes : BB == 512 ? RsLds<512, RS_BTILE>::bytes : RsLds<1024, RS_BTILE>::bytes;
-    { const int e = allow_big_lds(ctx, reinterpret_cast<const void*>(&k_rs_scatter<false>)); if (e) return e; }
-    if (spr) {
-        const size_t ldsS = ldsA + ((size_t)RS_SP_MAXQ + 1) * 4;
-        { const int e = allow_big_lds(ctx, reinterpret_cast<const void*>(&k_rs_scatter_sp)); if (e) return e; }
-        hipLaunchKernelGGL(k_rs_hist_sp, dim3((unsigned)nch_sp), dim3(RS_NT), 0, ctx->stream, sps, (u32)nch, matrix, sp);
-        if (spr->n_tail) hipLaunchKernelGGL(k_rs_hist, dim3(1), dim3(RS_NT), 0, ctx->stream, spr->tail_k, (u64)spr->n_tail, (u32)chunk, (u32)nch, matrix, sp, (u32)nch_sp);
-        CKL("k_rs_hist_sp");
-        { const int e = run_scan(ctx, matrix, sc + SC_RSLEN, M); if (e) return e; }
-        hipLaunchKernelGGL(k_rs_scatter_sp, dim3((unsigned)nch_sp), dim3(RS_NT), ldsS, ctx->stream, sps, (u32)nch, (const u32*)matrix, tk, tv, sp);
-        if (spr->n_tail) hipLaunchKernelGGL(k_rs_scatter<false>, dim3(1), dim3(RS_NT), ldsA, ctx->stream, spr->tail_k, spr->tail_v, (u64)spr->n_tail, (u32)chunk, (u32)nch, (const u32*)matrix, tk, tv, sp, (const u64*)nullptr, (u32)nch_sp);
-        CKL("k_rs_scatter_sp");
-    } else {
-        hipLaunchKernelGGL(k_rs_hist, dim3((unsigned)nch), dim3(RS_NT), 0, ctx->stream, k, n, (u32)chunk, (u32)nch, matrix, sp, 0u);
-        CKL("k_rs_hist");
-        { const int e = run_scan(ctx, matrix, sc + SC_RSLEN, M); if (e) return e; }
-        hipLaunchKernelGGL(k_rs_scatter<false>, dim3((unsigned)nch), dim3(RS_NT), ldsA, ctx->stream, k, v, n, (u32)chunk, (u32)nch, matrix, tk, tv, sp, (const u64*)nullptr, 0u);
-        CKL("k_rs_scatter");
-    }
-    // a bucket above 64 x the mean (+ 256 K rows) is not a k-mer spectrum any more (canonical k-mers: at most ~2 x; a low-complexity stretch of
-    // 200 kb puts 180 K rows under AAAAA: that is still one block's 0.2 ms -- the limit was 16 x + 64 K until seeds 208 / 292 / 319 of
-    // tools/stress_random.py took the 12 ms library fallback for it): one block would
-    // walk it alone, so it goes to the full-width fallback instead
-    u32 heavy = (u32)std::min<u64>(0xFFFFFFFFull, n / RS_ABINS * 64 + 262144);
-    if (ctx->tune.rs_heavy) heavy = ctx->tune.rs_heavy;
-    const unsigned gridB = (unsigned)std::min<u64>(ncu * (160 * 1024 / (ldsB + 1024)), RS_ABINS);
-    auto split = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(gridB), dim3(RS_BNT), ldsB, ctx->stream, tk, tv, (u32)nch, matrix, k, v, sub, sp, sc + SC_RSWORK2, heavy, sc + SC_SORTFLAG);
-    };
-    if (BB == 1024 && ldsB > 64 * 1024) { const int e = allow_big_lds(ctx, reinterpret_cast<const void*>(&k_rs_split<1024>)); if (e) return e; }
-    if (BB == 256) split(k_rs_split<256>); else if (BB == 512) split(k_rs_split<512>); else split(k_rs_split<1024>);
-    CKL("k_rs_split");
-    const u32 nsub = RS_ABINS * BB;
-    hipLaunchKernelGGL(k_rs_cells, dim3(nsub / (RS_CNT / 64)), dim3(RS_CNT), 0, ctx->stream, k, v, sub, nsub, BB, sp, biglist, sc + SC_RSWORK, sc + SC_SORTFLAG, sc + SC_RSTIES);
-    CKL("k_rs_cells");
-    const u32 block_rows = ctx->tune.rs_block_rows ? std::min<u32>(ctx->tune.rs_block_rows, RS_BLOCK_ROWS) : RS_BLOCK_ROWS;
-    hipLaunchKernelGGL(k_rs_big, dim3((unsigned)std::min<u64>(ncu, 256)), dim3(RS_NT), 0, ctx->stream, k, v, sub, sp, biglist, sc + SC_RSWORK, sc + SC_SORTFLAG, block_rows, sc + SC_RSTIES, base, ctx->rs_ovs.as<u32>());
-    CKL("k_rs_big");
-    return DSKGPU_OK;
-}
-
-// ---- the same sort for two-word rows (rowsort2.h): the rows themselves -- (hi, lo, abundance) in three arrays -- ordered in place on
-// the `total` low bits of hi:lo (t: scratch of the same size).  What it lists (sub-buckets above RS_BLOCK_ROWS rows) is left in
-// ctx->rs_ovs for the caller's next round; a heavy first-digit bucket or a full list raises SC_SORTFLAG.  k holds a complete
-// permutation of the rows either way.
-// spr: step A reads the rows in the count kernel's regions (+ a dense tail: the rows of the k-mers counted apart), as in msd_sort_pairs
-int msd_sort_rows2(dskgpu_ctx* ctx, Rows2 k, Rows2 t, u64 n, int total, bool reset_flags, u32 base, const dskgpu_ctx::SparseRows2* spr = nullptr) {
-    int wantB = n <= (96ull << 20) ? 8 : n <= (192ull << 20) ? 9 : 10;
-    if (ctx->tune.rs_bbits >= 8 && ctx->tune.rs_bbits <= 10) wantB = (int)ctx->tune.rs_bbits;      // tests
-    const int bA = std::min(RS2_ABITS, total), r1 = total - bA, bB = std::min(wantB, r1), r2 = r1 - bB, bC = std::min(8, r2), r3 = r2 - bC;
-    const u32 BB = 1u << wantB;
-    RsSpec sp{r1, r2, r3, (1u << bA) - 1u, (1u << bB) - 1u, (1u << bC) - 1u};
-    const u64 ncu = (u64)ctx->num_cu;
-    u64 nch = (n + 65535) / 65536;
-    nch = (nch + ncu - 1) / ncu * ncu;
-    nch = std::max<u64>(1, std::min<u64>(nch, (n + RS2_TILE - 1) / RS2_TILE));
-    u64 chunk = (n + nch - 1) / nch;
-    nch = (n + chunk - 1) / chunk;
-    Rs2Sparse sps{}; u64 nch_sp = 0;
-    if (spr) {      // chunks = groups of qpc consecutive sub-partitions (about 64 K rows, at most RS_SP_MAXQ of them) + one chunk for the dense tail
-        sps = spr->s;
-        const u64 F = sps.F;
-        u64 want = std::max<u64>(1, (spr->n_sparse + 65535) / 65536);
-        want = (want + ncu - 1) / ncu * ncu;
-        u64 qpc = std::max<u64>(1, (F + want - 1) / want);
-        if (qpc > RS_SP_MAXQ) qpc = RS_SP_MAXQ;
-        nch_sp = (F + qpc - 1) / qpc;
-        sps.qpc = (u32)qpc;
-        nch = nch_sp + (spr->n_tail ? 1 : 0);
-        chunk = spr->n_tail;
-    }
-    const u64 M = (u64)RS2_ABINS * nch;
-    const u64 nsubw = (u64)RS2_ABINS * (BB + 1);
-    CK(ctx->srt_tmp.ensure((M + 2 + 2 * nsubw + 16) * 4));
-    u32* matrix = static_cast<u32*>(ctx->srt_tmp.p);
-    u32* sub = matrix + M + 2;
-    u32* biglist = sub + nsubw;
-    u32* sc = ctx->scalars.as<u32>();
-    CK(ctx->rs_ovs.ensure((1 + 3 * RS_OVS_CAP) * 4));
-    hipLaunchKernelGGL(k_set_rs_scalars, dim3(1), dim3(64), 0, ctx->stream, sc + SC_RSLEN, (u32)M, reset_flags ? 4u : 3u,
-                       reset_flags ? sc + SC_SORTFLAG : (u32*)nullptr, reset_flags ? ctx->rs_ovs.as<u32>() : (u32*)nullptr);
-    const size_t ldsA = Rs2Lds<RS2_ABINS, RS2_TILE>::bytes;
-    const size_t ldsB = BB == 256 ? Rs2Lds<256, RS2_BTILE>::bytes : BB == 512 ? Rs2Lds<512, RS2_BTILE>::bytes : Rs2Lds<1024, RS2_BTILE>::bytes;
-    const size_t ldsBig = (size_t)RS_BLOCK_ROWS * 20 + 2 * RS_CELLS * 4;
-    { const int e = allow_big_lds(ctx, reinterpret_cast<const void*>(&k2_scatter<false>)); if (e) return e; }
-    { const int e = allow_big_lds(ctx, reinterpret_cast<const void*>(&k2_big), (int)ldsBig); if (e) return e; }
-    const Rows2C kc{k.hi, k.lo, k.ab}, tc{t.hi, t.lo, t.ab};
-    if (spr) {
-        const size_t ldsS = ldsA + ((size_t)RS_SP_MAXQ + 1) * 4;
-        { const int e = allow_big_lds(ctx, reinterpret_cast<const void*>(&k2_scatter_sp)); if (e) return e; }
-        hipLaunchKernelGGL(k2_hist_sp, dim3((unsigned)nch_sp), dim3(RS_NT), 0, ctx->stream, sps, (u32)nch, matrix, sp);
-        if (spr->n_tail) hipLaunchKernelGGL(k2_hist, dim3(1), dim3(RS_NT), 0, ctx->stream, spr->tail, (u64)spr->n_tail, (u32)chunk, (u32)nch, matrix, sp, (u32)nch_sp);
-        CKL("k2_hist_sp");
-        { const int e = run_scan(ctx, matrix, sc + SC_RSLEN, M); if (e) return e; }
-        hipLaunchKernelGGL(k2_scatter_sp, dim3((unsigned)nch_sp), dim3(RS_NT), ldsS, ctx->stream, sps, (u32)nch, (const u32*)matrix, t, sp);
-        if (spr->n_tail) hipLaunchKernelGGL(k2_scatter<false>, dim3(1), dim3(RS_NT), ldsA, ctx->stream, spr->tail, (u64)spr->n_tail, (u32)chunk, (u32)nch, matrix, t, sp, (const u64*)nullptr, (u32)nch_sp);
-        CKL("k2_scatter_sp");
-    } else {
-        hipLaunchKernelGGL(k2_hist, dim3((unsigned)nch), dim3(RS_NT), 0, ctx->stream, kc, n, (u32)chunk, (u32)nch, matrix, sp, 0u);
-        CKL("k2_hist");
-        { const int e = run_scan(ctx, matrix, sc + SC_RSLEN, M); if (e) return e; }
-        hipLaunchKernelGGL(k2_scatter<false>, dim3((unsigned)nch), dim3(RS_NT), ldsA, ctx->stream, kc, n, (u32)chunk, (u32)nch, matrix, t, sp, (const u64*)nullptr, 0u);
-        CKL("k2_scatter");
-    }
-    u32 heavy = (u32)std::min<u64>(0xFFFFFFFFull, n / RS2_ABINS * 64 + 262144);
-    if (ctx->tune.rs_heavy) heavy = ctx->tune.rs_heavy;
-    const unsigned gridB = (unsigned)std::min<u64>(ncu * (160 * 1024 / (ldsB + 1024)), RS2_ABINS);
-    auto split = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(gridB), dim3(RS_BNT), ldsB, ctx->stream, tc, (u32)nch, matrix, k, sub, sp, sc + SC_RSWORK2, heavy, sc + SC_SORTFLAG);
-    };
-    if (BB == 256) split(k2_split<256>); else if (BB == 512) split(k2_split<512>); else split(k2_split<1024>);
-    CKL("k2_split");
-    const u32 nsub = RS2_ABINS * BB;
-    hipLaunchKernelGGL(k2_cells, dim3(nsub / (RS_CNT / 64)), dim3(RS_CNT), 0, ctx->stream, k, sub, nsub, BB, sp, biglist, sc + SC_RSWORK);
-    CKL("k2_cells");
-    const u32 block_rows = ctx->tune.rs_block_rows ? std::min<u32>(ctx->tune.rs_block_rows, RS_BLOCK_ROWS) : RS_BLOCK_ROWS;
-    hipLaunchKernelGGL(k2_big, dim3((unsigned)std::min<u64>(ncu, 256)), dim3(RS_NT), ldsBig, ctx->stream, k, sub, sp, biglist, sc + SC_RSWORK, sc + SC_SORTFLAG, block_rows, base, ctx->rs_ovs.as<u32>());
-    CKL("k2_big");
-    return DSKGPU_OK;
-}
-
-// the sub-buckets a two-word sort listed (ctx->rs_ovs; offsets are absolute rows of R, the array that holds the result; S = scratch of
-// the same shape): every listed range goes round again on the bits it has not used, until nothing is listed any more
-int rows2_rounds(dskgpu_ctx* ctx, Rows2 R, Rows2 S) {
-    u32* sc = ctx->scalars.as<u32>();
-    std::vector<u32> list;
-    for (int round = 0; ; ++round) {
-        u32 cnt = 0;
-        CK(hipMemcpyAsync(&ctx->h_back[3], sc + SC_SORTFLAG, 4, hipMemcpyDeviceToHost, ctx->stream));
-        CK(hipMemcpyAsync(&cnt, ctx->rs_ovs.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-        CK(hipStreamSynchronize(ctx->stream));
-        if (ctx->h_back[3] || cnt == 0) break;
-        if (cnt > RS2_OVS_CAP || round >= 8) { ctx->h_back[3] = 1; CK(hipMemsetAsync(sc + SC_SORTFLAG, 0xFF, 4, ctx->stream)); break; }
-        list.resize(3 * (size_t)cnt);
-        CK(hipMemcpyAsync(list.data(), ctx->rs_ovs.as<u32>() + 1, list.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-        CK(hipStreamSynchronize(ctx->stream));
-        CK(hipMemsetAsync(ctx->rs_ovs.p, 0, 4, ctx->stream));
-        if (ctx->tune.verbose) fprintf(stderr, "[dskgpu] two-word row sort, round %d: %u sub-bucket(s) above %u rows go round again (first: %u rows, %u bits left)\n", round + 1, cnt, (u32)RS_BLOCK_ROWS, list[1], list[2]);
-        for (u32 r = 0; r < cnt; ++r) {
-            const u64 off = list[3 * r]; const u32 len = list[3 * r + 1], bits = list[3 * r + 2];
-            const Rows2 k2{R.hi + off, R.lo + off, R.ab + off}, t2{S.hi + off, S.lo + off, S.ab + off};
-            const int e = msd_sort_rows2(ctx, k2, t2, len, (int)bits, false, (u32)off);
-            if (e) return e;
-        }
-    }
-    return DSKGPU_OK;
-}
-
-// two-word rows, <= RS_MAX_ROWS: out_* ordered in place; the sub-buckets the sort lists go round again on their remaining bits,
-// range by range (a handful on real reads; each round consumes 26-28 bits: at most ceil(128 / 18) rounds).  Leaves the flag
-// read-back in flight like the other sorts (ctx->h_back[3] != 0 after the caller's sync: the full-width fallback, which reads out_*)
-int sort_rows2_msd(dskgpu_ctx* ctx, u64 n) {
-    for (int x = 0; x < 2; ++x) CK(ctx->srt_w[x].ensure(n * 8));
-    CK(ctx->srt_ab.ensure(n * 4));
-    const Rows2 K{ctx->out_w[1].as<u64>(), ctx->out_w[0].as<u64>(), ctx->out_ab.as<u32>()};
-    const Rows2 T{ctx->srt_w[1].as<u64>(), ctx->srt_w[0].as<u64>(), ctx->srt_ab.as<u32>()};
-    u32* sc = ctx->scalars.as<u32>();
-    { const int e = msd_sort_rows2(ctx, K, T, n, 2 * (int)ctx->cfg.kmer_size, true, 0u, ctx->sp_rows2.valid ? &ctx->sp_rows2 : nullptr); ctx->sp_rows2.valid = false; if (e) return e; }
-    { const int e = rows2_rounds(ctx, K, T); if (e) return e; }
-    (void)sc;
-    ctx->h_ovs.assign(1, 0);
-    ctx->sort_back = 2;
-    ctx->sort_partial = true;
-    return DSKGPU_OK;
-}
-
-// two-word row sets above RS_MAX_ROWS (all of configs[3]'s volume on one GPU: 7 * 10^8 rows): sort_rows_big's scheme with the
-// rowsort2.h kernels -- step A once over all rows (out_* -> scratch), then the groups of 10-bit buckets that share their top `sb` bits
-// are ordered one by one (in the scratch copy, out_* their scratch), then the listed sub-buckets' rounds.  Result: ctx->res_* = the
-// scratch copy; on a raised flag the caller copies it back to out_* for the full-width fallback (ctx->rows2_in_scratch).
-int sort_rows2_big(dskgpu_ctx* ctx, u64 n) {
-    const Rows2 K{ctx->out_w[1].as<u64>(), ctx->out_w[0].as<u64>(), ctx->out_ab.as<u32>()};
-    const size_t n_al = (size_t)((n + 31) & ~(u64)31), need = n_al * 20 + 256;
-    Rows2 T;
-    if (ctx->l0buf.cap >= need) { T.hi = ctx->l0buf.as<u64>(); T.lo = T.hi + n_al; T.ab = reinterpret_cast<u32*>(T.lo + n_al); }
-    else {
-        size_t free_b = 0, total_b = 0;
-        CK(hipMemGetInfo(&free_b, &total_b));
-        if (ctx->srt_w[0].cap + ctx->srt_w[1].cap + ctx->srt_ab.cap + free_b < need + ((size_t)2 << 30)) { ctx->l0buf.release(); ctx->bufA.release(); ctx->bufB.release(); }
-        for (int x = 0; x < 2; ++x) CK(ctx->srt_w[x].ensure(n * 8));
-        CK(ctx->srt_ab.ensure(n * 4));
-        T = Rows2{ctx->srt_w[1].as<u64>(), ctx->srt_w[0].as<u64>(), ctx->srt_ab.as<u32>()};
-    }
-    const int total = 2 * (int)ctx->cfg.kmer_size;
-    const int bA = std::min(RS2_ABITS, total);
-    RsSpec sp{total - bA, 0, 0, (1u << bA) - 1u, 0u, 0u};
-    const u64 ncu = (u64)ctx->num_cu;
-    u64 nch = (n + 65535) / 65536;
-    nch = (nch + ncu - 1) / ncu * ncu;
-    const u64 chunk = (n + nch - 1) / nch;
-    nch = (n + chunk - 1) / chunk;
-    const u64 M = (u64)RS2_ABINS * nch;
-    if (M >= 0xFFFFFFF0ull) return fail(ctx, DSKGPU_E_ARG, "row sort: too many rows");
-    CK(ctx->mat2.ensure((M + 2) * 4));
-    u32* matrix = ctx->mat2.as<u32>();
-    u32* sc = ctx->scalars.as<u32>();
-    CK(ctx->rs_ovs.ensure((1 + 3 * RS_OVS_CAP) * 4));
-    hipLaunchKernelGGL(k_set_rs_scalars, dim3(1), dim3(64), 0, ctx->stream, sc + SC_RSLEN, (u32)M, 4u, sc + SC_SORTFLAG, ctx->rs_ovs.as<u32>());
-    ctx->h_ovs.assign(1, 0);
-    { const int e = allow_big_lds(ctx, reinterpret_cast<const void*>(&k2_scatter<false>)); if (e) return e; }
-    const Rows2C kc{K.hi, K.lo, K.ab};
-    hipLaunchKernelGGL(k2_hist, dim3((unsigned)nch), dim3(RS_NT), 0, ctx->stream, kc, n, (u32)chunk, (u32)nch, matrix, sp);
-    CKL("k2_hist");
-    { const int e = run_scan(ctx, matrix, sc + SC_RSLEN, M); if (e) return e; }
-    const size_t ldsA = Rs2Lds<RS2_ABINS, RS2_TILE>::bytes;
-    hipLaunchKernelGGL(k2_scatter<false>, dim3((unsigned)nch), dim3(RS_NT), ldsA, ctx->stream, kc, n, (u32)chunk, (u32)nch, matrix, T, sp, (const u64*)nullptr);
-    CKL("k2_scatter");
-    std::vector<u32> start(RS2_ABINS + 1);
-    CK(hipMemcpy2DAsync(start.data(), 4, matrix, nch * 4, 4, RS2_ABINS + 1, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    start[RS2_ABINS] = (u32)n;
-    const u64 rs_max = ctx->tune.rs_max_rows ? std::min<u64>(ctx->tune.rs_max_rows, RS_MAX_ROWS) : RS_MAX_ROWS;
-    int sb = -1;
-    for (int bits = 0; bits <= bA && sb < 0; ++bits) {
-        const u32 per = (1u << bA) >> bits;
-        bool ok = true;
-        for (u32 g0 = 0; g0 < (1u << bA) && ok; g0 += per) ok = (u64)start[g0 + per] - start[g0] <= rs_max;
-        if (ok) sb = bits;
-    }
-    ctx->res_w[1] = T.hi; ctx->res_w[0] = T.lo; ctx->res_ab = T.ab; ctx->sort_partial = true;
-    ctx->rows2_in_scratch = true; ctx->rows2_scratch = T;
-    if (sb < 0) { ctx->h_back[3] = 1; return DSKGPU_OK; }
-    const u32 per = (1u << bA) >> sb;
-    for (u32 g0 = 0; g0 < (1u << bA); g0 += per) {
-        const u64 b = start[g0], e = start[g0 + per];
-        if (e - b < 2 || total - sb < 1) continue;
-        const Rows2 r2{T.hi + b, T.lo + b, T.ab + b}, s2{K.hi + b, K.lo + b, K.ab + b};
-        const int rc = msd_sort_rows2(ctx, r2, s2, e - b, total - sb, false, (u32)b);
-        if (rc) return rc;
-    }
-    { const int e = rows2_rounds(ctx, T, K); if (e) return e; }
-    CK(hipMemcpyAsync(&ctx->h_back[3], sc + SC_SORTFLAG, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (ctx->tune.verbose) fprintf(stderr, "[dskgpu] two-word row sort: %llu rows in %u groups on their top %d bits, MSD sort per group\n", (unsigned long long)n, 1u << sb, sb);
-    return DSKGPU_OK;
-}
-
-// one-word rows: out_* ordered in place (srt_* = scratch and, for run_pipeline's fallback, a complete permutation of the rows)
-int sort_rows_msd(dskgpu_ctx* ctx, u64 n) {
-    const int e = msd_sort_pairs(ctx, ctx->out_w[0].as<u64>(), ctx->out_ab.as<u32>(), ctx->srt_w[0].as<u64>(), ctx->srt_ab.as<u32>(), n,
-                                 (int)std::min(64u, 2u * ctx->cfg.kmer_size), true, 0u, ctx->sp_rows.valid ? &ctx->sp_rows : nullptr);
-    ctx->sp_rows.valid = false; ctx->sp_rows2.valid = false;
-    if (e) return e;
-    ctx->h_ovs.assign(1, 0);
-    ctx->sort_back = 1;      // (flag and sub-bucket count travel with the histogram: run_pipeline)
-    ctx->sort_partial = true;
-    ctx->res_w[0] = ctx->out_w[0].as<u64>(); ctx->res_ab = ctx->out_ab.as<u32>();
-    ctx->rs_res_k = ctx->out_w[0].as<u64>(); ctx->rs_res_v = ctx->out_ab.as<u32>(); ctx->rs_tmp_k = ctx->srt_w[0].as<u64>(); ctx->rs_tmp_v = ctx->srt_ab.as<u32>();
-    return DSKGPU_OK;
-}
-
-// The sub-buckets a row sort listed instead of ordering them (k_rs_big: more than RS_BLOCK_ROWS rows share two digits -- the error
-// variants of a k-mer with 10^8 occurrences share 13 and more leading bases): the rows of all listed ranges are gathered under
-// the composite key (range number, value bits the range has not used yet), ordered by ONE more MSD sort and put back
-// (k_ovs_gather / k_ovs_scatter) -- which may list ranges of the gathered array again: a few rounds at most, the rows of a range
-// share ever longer prefixes.  Called after the host has seen a non-zero count (ctx->h_ovs[0]); synchronous.  Leaves
-// ctx->h_back[3] != 0 when rounds or list run out: the caller's full-width fallback.
-int sort_oversize_round(dskgpu_ctx* ctx, u64* res_k, u32* res_v, int depth) {
-    u32* sc = ctx->scalars.as<u32>();
-    const u32 cnt = ctx->h_ovs[0];
-    if (cnt == 0) return DSKGPU_OK;
-    if (cnt > RS_OVS_CAP || depth >= 4) { ctx->h_back[3] = 1; return DSKGPU_OK; }
-    std::vector<u32> list(3 * (size_t)cnt), starts(cnt + 1, 0);
-    CK(hipMemcpyAsync(list.data(), ctx->rs_ovs.as<u32>() + 1, list.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    u64 tot = 0; u32 maxbits = 1;
-    for (u32 i = 0; i < cnt; ++i) { starts[i] = (u32)tot; tot += list[3 * i + 1]; maxbits = std::max(maxbits, list[3 * i + 2]); }
-    if (tot >= 0xFFFF0000ull || maxbits > RS_OVS_SHIFT) { ctx->h_back[3] = 1; return DSKGPU_OK; }
-    if (ctx->tune.verbose) fprintf(stderr, "[dskgpu] row sort: %u sub-bucket(s) above %u rows (%llu rows in all, up to %u bits left) go round again\n", cnt, (u32)RS_BLOCK_ROWS, (unsigned long long)tot, maxbits);
-    DevBuf& g = ctx->rs_g[depth];
-    const size_t n_al = (size_t)((tot + 31) & ~(u64)31);
-    const size_t meta = ((size_t)cnt * 4 * 4 + (size_t)cnt * 8 + 255) & ~size_t(255);      // list (3 words) + starts, then the prefixes
-    CK(g.ensure(2 * n_al * 12 + meta + 256));
-    u64* gk = g.as<u64>(); u64* tk = gk + n_al; u32* gv = reinterpret_cast<u32*>(tk + n_al); u32* tv = gv + n_al;
-    u32* d_list = tv + n_al; u32* d_starts = d_list + 3 * (size_t)cnt;
-    u64* d_prefix = reinterpret_cast<u64*>(reinterpret_cast<char*>(d_list) + (((size_t)cnt * 16 + 7) & ~size_t(7)));
-    CK(hipMemcpyAsync(d_list, list.data(), list.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    CK(hipMemcpyAsync(d_starts, starts.data(), (size_t)cnt * 4, hipMemcpyHostToDevice, ctx->stream));
-    const unsigned gridr = (unsigned)std::min<u64>(cnt, (u64)ctx->num_cu * 8);
-    hipLaunchKernelGGL(k_ovs_gather, dim3(gridr), dim3(256), 0, ctx->stream, (const u64*)res_k, (const u32*)res_v, (const u32*)d_list, (const u32*)d_starts, cnt, gk, gv, d_prefix, maxbits);
-    CKL("k_ovs_gather");
-    CK(hipStreamSynchronize(ctx->stream));          // (list / starts were read from host vectors)
-    CK(hipMemsetAsync(ctx->rs_ovs.p, 0, 4, ctx->stream));
-    int idbits = 1; while ((1u << idbits) < cnt) ++idbits;
-    { const int rc = msd_sort_pairs(ctx, gk, gv, tk, tv, tot, (int)maxbits + idbits, false, 0u); if (rc) return rc; }
-    ctx->h_ovs.assign(1, 0);
-    CK(hipMemcpyAsync(ctx->h_ovs.data(), ctx->rs_ovs.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipMemcpyAsync(&ctx->h_back[3], sc + SC_SORTFLAG, 4, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    if (!ctx->h_back[3] && ctx->h_ovs[0]) { const int rc = sort_oversize_round(ctx, gk, gv, depth + 1); if (rc) return rc; }
-    if (ctx->h_back[3]) return DSKGPU_OK;
-    hipLaunchKernelGGL(k_ovs_scatter, dim3(gridr), dim3(256), 0, ctx->stream, res_k, res_v, (const u32*)d_list, (const u32*)d_starts, cnt, (const u64*)gk, (const u32*)gv, (const u64*)d_prefix, maxbits);
-    CKL("k_ovs_scatter");
-    return DSKGPU_OK;
-}
-int sort_oversize(dskgpu_ctx* ctx) { return sort_oversize_round(ctx, ctx->rs_res_k, ctx->rs_res_v, 0); }
-
-// Row sets above RS_MAX_ROWS (one-word rows; the 3 * 10^9 solid k-mers of a 30x human run, the 6 * 10^8 of 200 M reads): step A of
-// the MSD sort ONCE over all rows -- 1024 buckets on the top 10 value bits, exact offsets (rows < 2^32) -- then the rows that
-// share their top `sb` bits (sb = the fewest bits for which every such group holds <= RS_MAX_ROWS rows: 3-5 for those inputs)
-// are ordered group by group with the MSD sort on the remaining bits.  No library kernel; what the MSD kernels do not order
-// themselves raises the same flag as for small row sets (full-width fallback in run_pipeline).  Scratch for the second copy of
-// the rows: the level-0 buffer of a multi-pass count when it is large enough (its key arrays are dead by now), else srt_* --
-// after giving back the partition buffers when HBM is short (the next count allocates them again).
-// In: rows in out_w[0] / out_ab.  Out: ctx->res_* (the scratch copy), ctx->fb_*: where the fallback finds a permutation of the rows.
-int sort_rows_big(dskgpu_ctx* ctx, u64 n) {
-    u64* k = ctx->out_w[0].as<u64>(); u32* v = ctx->out_ab.as<u32>();
-    const size_t n_al = (size_t)((n + 31) & ~(u64)31), need = n_al * 12 + 256;
-    u64* tk; u32* tv;
-    if (ctx->l0buf.cap >= need) { tk = ctx->l0buf.as<u64>(); tv = reinterpret_cast<u32*>(tk + n_al); }
-    else {
-        size_t free_b = 0, total_b = 0;
-        CK(hipMemGetInfo(&free_b, &total_b));
-        if (ctx->srt_w[0].cap + ctx->srt_ab.cap + free_b < need + ((size_t)2 << 30)) { ctx->l0buf.release(); ctx->bufA.release(); ctx->bufB.release(); }
-        CK(ctx->srt_w[0].ensure(n * 8)); CK(ctx->srt_ab.ensure(n * 4));
-        tk = ctx->srt_w[0].as<u64>(); tv = ctx->srt_ab.as<u32>();
-    }
-    const int total = (int)std::min(64u, 2u * ctx->cfg.kmer_size);
-    const int bA = std::min(RS_ABITS, total);
-    RsSpec sp{total - bA, 0, 0, (1u << bA) - 1u, 0u, 0u};
-    const u64 ncu = (u64)ctx->num_cu;
-    u64 nch = (n + 65535) / 65536;
-    nch = (nch + ncu - 1) / ncu * ncu;
-    const u64 chunk = (n + nch - 1) / nch;
-    nch = (n + chunk - 1) / chunk;
-    const u64 M = (u64)RS_ABINS * nch;
-    if (M >= 0xFFFFFFF0ull) return fail(ctx, DSKGPU_E_ARG, "row sort: too many rows");
-    CK(ctx->mat2.ensure((M + 2) * 4));
-    u32* matrix = ctx->mat2.as<u32>();
-    u32* sc = ctx->scalars.as<u32>();
-    CK(ctx->rs_ovs.ensure((1 + 3 * RS_OVS_CAP) * 4));
-    hipLaunchKernelGGL(k_set_rs_scalars, dim3(1), dim3(64), 0, ctx->stream, sc + SC_RSLEN, (u32)M, 4u, sc + SC_SORTFLAG, ctx->rs_ovs.as<u32>());
-    ctx->h_ovs.assign(1, 0);
-    ctx->rs_res_k = tk; ctx->rs_res_v = tv; ctx->rs_tmp_k = k; ctx->rs_tmp_v = v;
-    { const int e = allow_big_lds(ctx, reinterpret_cast<const void*>(&k_rs_scatter<false>)); if (e) return e; }
-    hipLaunchKernelGGL(k_rs_hist, dim3((unsigned)nch), dim3(RS_NT), 0, ctx->stream, k, n, (u32)chunk, (u32)nch, matrix, sp, 0u);
-    CKL("k_rs_hist");
-    { const int e = run_scan(ctx, matrix, sc + SC_RSLEN, M); if (e) return e; }
-    const size_t ldsA = RsLds<RS_ABINS, RS_TILE>::bytes;
-    hipLaunchKernelGGL(k_rs_scatter<false>, dim3((unsigned)nch), dim3(RS_NT), ldsA, ctx->stream, k, v, n, (u32)chunk, (u32)nch, matrix, tk, tv, sp, (const u64*)nullptr, 0u);
-    CKL("k_rs_scatter");
-    // bucket starts -> host (entry b * nch of the scanned matrix; the scan leaves the total behind the last entry)
-    std::vector<u32> start(RS_ABINS + 1);
-    CK(hipMemcpy2DAsync(start.data(), 4, matrix, nch * 4, 4, RS_ABINS + 1, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    start[RS_ABINS] = (u32)n;
-    const u64 rs_max = ctx->tune.rs_max_rows ? std::min<u64>(ctx->tune.rs_max_rows, RS_MAX_ROWS) : RS_MAX_ROWS;
-    int sb = -1;
-    for (int bits = 0; bits <= bA && sb < 0; ++bits) {
-        const u32 per = (1u << bA) >> bits;               // 10-bit buckets per group
-        bool ok = true;
-        for (u32 g0 = 0; g0 < (1u << bA) && ok; g0 += per) ok = (u64)start[g0 + per] - start[g0] <= rs_max;
-        if (ok) sb = bits;
-    }
-    ctx->fb_src_k = tk; ctx->fb_src_v = tv; ctx->fb_dst_k = k; ctx->fb_dst_v = v;
-    ctx->res_w[0] = tk; ctx->res_ab = tv; ctx->sort_partial = true;
-    if (sb < 0) {                                          // one 10-bit bucket alone exceeds the MSD sort: not a k-mer spectrum -> full-width fallback
-        ctx->h_back[3] = 1;
-        return DSKGPU_OK;
-    }
-    const u32 per = (1u << bA) >> sb;
-    bool first = true;
-    for (u32 g0 = 0; g0 < (1u << bA); g0 += per) {
-        const u64 b = start[g0], e = start[g0 + per];
-        if (e - b < 2 || total - sb < 1) continue;
-        const int rc = msd_sort_pairs(ctx, tk + b, tv + b, k + b, v + b, e - b, total - sb, false, (u32)b);      // (in place in tk / tv; k / v = its scratch)
-        if (rc) return rc;
-        first = false;
-    }
-    (void)first;
-    CK(hipMemcpyAsync(&ctx->h_back[3], sc + SC_SORTFLAG, 4, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipMemcpyAsync(ctx->h_ovs.data(), ctx->rs_ovs.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (ctx->tune.verbose) fprintf(stderr, "[dskgpu] row sort: %llu rows in %u groups on their top %d bits, MSD sort per group\n", (unsigned long long)n, 1u << sb, sb);
-    return DSKGPU_OK;
-}
-
-
-// ---- row sets of 2^32 rows and more (one- and two-word rows): `-abundance-min 1` on a 200 M-read input, the solid k-mers of a deeper
-// human run.  The reference streams rows to Partition<Count> without any such bound (utils/dsk2ascii.cpp:61,77).  The MSD kernels
-// index rows with 32 bits, so step A runs SLAB by slab (2^31 rows each): per slab the first-digit histogram and its (32-bit, slab-
-// local) scan, then the host lays the 1024 buckets out over ALL rows in 64 bits -- bucket b = [B[b], B[b + 1]), inside it the slabs'
-// shares in slab order -- and hands every slab's scatter a 64-bit offset per bin (k_rs_scatter<true>: output index = slab-local
-// index + gdel[bin]).  After that every bucket is far below 2^32 rows and the groups of buckets that share their top bits (<= RS_MAX_ROWS
-// rows each) are ordered one by one with the ordinary MSD sort, each group with its own flag / list round trip: what a group's sort
-// does not order itself goes through the library radix sort FOR THAT GROUP (one-word rows; a group is < 2^32 rows) -- exact for any
-// value distribution.  Scratch = a second copy of the rows (the level-0 buffer of the multi-pass count when it is large enough).
-template <int W>
-int sort_rows_huge(dskgpu_ctx* ctx, u64 n) {
-    static_assert(W == 1 || W == 2, "one- and two-word rows");
-    constexpr int ABITS = W == 1 ? RS_ABITS : RS2_ABITS;       // first digit of the one- / two-word kernels
-    constexpr u32 ABINS = 1u << ABITS;
-    const size_t n_al = (size_t)((n + 31) & ~(u64)31), row_bytes = W == 1 ? 12 : 20, need = n_al * row_bytes + 256;
-    u64* k = ctx->out_w[0].as<u64>(); u32* v = ctx->out_ab.as<u32>();
-    u64* tk = nullptr; u32* tv = nullptr;              // one-word rows: the scratch copy (becomes the result)
-    Rows2 K{nullptr, nullptr, nullptr}, T{nullptr, nullptr, nullptr};
-    if (W == 2) K = Rows2{ctx->out_w[1].as<u64>(), ctx->out_w[0].as<u64>(), ctx->out_ab.as<u32>()};
-    if (ctx->l0buf.cap >= need) {
-        u64* base = ctx->l0buf.as<u64>();
-        if (W == 1) { tk = base; tv = reinterpret_cast<u32*>(tk + n_al); }
-        else { T.hi = base; T.lo = T.hi + n_al; T.ab = reinterpret_cast<u32*>(T.lo + n_al); }
-    } else {
-        ctx->l0buf.release(); ctx->bufA.release(); ctx->bufB.release();       // (the next count allocates them again)
-        for (int x = 0; x < W; ++x) CK(ctx->srt_w[x].ensure(n * 8));
-        CK(ctx->srt_ab.ensure(n * 4));
-        if (W == 1) { tk = ctx->srt_w[0].as<u64>(); tv = ctx->srt_ab.as<u32>(); }
-        else T = Rows2{ctx->srt_w[1].as<u64>(), ctx->srt_w[0].as<u64>(), ctx->srt_ab.as<u32>()};
-    }
-    const int total = W == 1 ? (int)std::min(64u, 2u * ctx->cfg.kmer_size) : 2 * (int)ctx->cfg.kmer_size;
-    const int bA = std::min(ABITS, total);
-    const u32 NB = 1u << bA;
-    RsSpec sp{total - bA, 0, 0, NB - 1u, 0u, 0u};
-    const u64 ncu = (u64)ctx->num_cu;
-    const u64 slab = ctx->tune.rs_slab_rows ? std::max<u64>(ctx->tune.rs_slab_rows, 1024) : (1ull << 31);
-    const u32 S = (u32)((n + slab - 1) / slab);
-    // per slab: chunks of ~64 K rows (a multiple of the CU count of them), matrix of ABINS x nch counters
-    std::vector<u64> s_n(S), s_nch(S), s_chunk(S), s_moff(S + 1, 0);
-    for (u32 sl = 0; sl < S; ++sl) {
-        const u64 ns = std::min<u64>(slab, n - (u64)sl * slab);
-        u64 nch = (ns + 65535) / 65536;
-        nch = (nch + ncu - 1) / ncu * ncu;
-        const u64 tile = W == 1 ? RS_TILE : RS2_TILE;
-        nch = std::max<u64>(1, std::min<u64>(nch, (ns + tile - 1) / tile));
-        const u64 chunk = (ns + nch - 1) / nch;
-        nch = (ns + chunk - 1) / chunk;
-        s_n[sl] = ns; s_nch[sl] = nch; s_chunk[sl] = chunk;
-        s_moff[sl + 1] = s_moff[sl] + (u64)ABINS * nch + 2;
-    }
-    CK(ctx->mat2.ensure(s_moff[S] * 4));
-    CK(ctx->rs_lens.ensure((size_t)S * 4));
-    ctx->h_rs_lens.resize(S);
-    for (u32 sl = 0; sl < S; ++sl) ctx->h_rs_lens[sl] = (u32)((u64)ABINS * s_nch[sl]);
-    CK(hipMemcpyAsync(ctx->rs_lens.p, ctx->h_rs_lens.data(), (size_t)S * 4, hipMemcpyHostToDevice, ctx->stream));
-    u32* sc = ctx->scalars.as<u32>();
-    CK(ctx->rs_ovs.ensure((1 + 3 * RS_OVS_CAP) * 4));
-    ctx->h_rs_lin.assign((size_t)S * (ABINS + 1), 0);
-    for (u32 sl = 0; sl < S; ++sl) {
-        const u64 r0 = (u64)sl * slab;
-        u32* matrix = ctx->mat2.as<u32>() + s_moff[sl];
-        if (W == 1) hipLaunchKernelGGL(k_rs_hist, dim3((unsigned)s_nch[sl]), dim3(RS_NT), 0, ctx->stream, (const u64*)(k + r0), s_n[sl], (u32)s_chunk[sl], (u32)s_nch[sl], matrix, sp, 0u);
-        else { const Rows2C kc{K.hi + r0, K.lo + r0, K.ab + r0}; hipLaunchKernelGGL(k2_hist, dim3((unsigned)s_nch[sl]), dim3(RS_NT), 0, ctx->stream, kc, s_n[sl], (u32)s_chunk[sl], (u32)s_nch[sl], matrix, sp); }
-        CKL("k_rs_hist(slab)");
-        { const int e = run_scan(ctx, matrix, ctx->rs_lens.as<u32>() + sl, (u64)ABINS * s_nch[sl]); if (e) return e; }
-        // bucket starts inside the slab (entry b * nch of the scanned matrix; the scan leaves the slab's total behind the last entry)
-        CK(hipMemcpy2DAsync(ctx->h_rs_lin.data() + (size_t)sl * (ABINS + 1), 4, matrix, s_nch[sl] * 4, 4, ABINS + 1, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    CK(hipStreamSynchronize(ctx->stream));
-    // the buckets over all rows, and every (slab, bin) pair's place inside its bucket
-    std::vector<u64> B(ABINS + 1, 0);
-    for (u32 b = 0; b < ABINS; ++b) {
-        u64 t = 0;
-        for (u32 sl = 0; sl < S; ++sl) { const u32* lin = ctx->h_rs_lin.data() + (size_t)sl * (ABINS + 1); t += (u64)(lin[b + 1] - lin[b]); }
-        B[b + 1] = B[b] + t;
-    }
-    if (B[ABINS] != n) return fail(ctx, DSKGPU_E_DEVICE, "row sort: the slabs' histograms do not add up to the rows");
-    ctx->h_rs_del.assign((size_t)S * ABINS, 0);
-    {
-        std::vector<u64> at(B.begin(), B.end() - 1);              // next free row of every bucket
-        for (u32 sl = 0; sl < S; ++sl) {
-            const u32* lin = ctx->h_rs_lin.data() + (size_t)sl * (ABINS + 1);
-            for (u32 b = 0; b < ABINS; ++b) { ctx->h_rs_del[(size_t)sl * ABINS + b] = at[b] - (u64)lin[b]; at[b] += (u64)(lin[b + 1] - lin[b]); }      // (wraps in 64 bits: added back by the kernel)
-        }
-    }
-    CK(ctx->rs_del.ensure(ctx->h_rs_del.size() * 8));
-    CK(hipMemcpyAsync(ctx->rs_del.p, ctx->h_rs_del.data(), ctx->h_rs_del.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (W == 1) { const int e = allow_big_lds(ctx, reinterpret_cast<const void*>(&k_rs_scatter<true>)); if (e) return e; }
-    else { const int e = allow_big_lds(ctx, reinterpret_cast<const void*>(&k2_scatter<true>)); if (e) return e; }
-    const size_t ldsA1 = RsLds<RS_ABINS, RS_TILE>::bytes, ldsA2 = Rs2Lds<RS2_ABINS, RS2_TILE>::bytes;
-    for (u32 sl = 0; sl < S; ++sl) {
-        const u64 r0 = (u64)sl * slab;
-        const u32* matrix = ctx->mat2.as<u32>() + s_moff[sl];
-        const u64* gdel = ctx->rs_del.as<u64>() + (size_t)sl * ABINS;
-        if (W == 1) hipLaunchKernelGGL(k_rs_scatter<true>, dim3((unsigned)s_nch[sl]), dim3(RS_NT), ldsA1, ctx->stream, (const u64*)(k + r0), (const u32*)(v + r0), s_n[sl],
-                                       (u32)s_chunk[sl], (u32)s_nch[sl], matrix, tk, tv, sp, gdel, 0u);
-        else { const Rows2C kc{K.hi + r0, K.lo + r0, K.ab + r0};
-               hipLaunchKernelGGL(k2_scatter<true>, dim3((unsigned)s_nch[sl]), dim3(RS_NT), ldsA2, ctx->stream, kc, s_n[sl], (u32)s_chunk[sl], (u32)s_nch[sl], matrix, T, sp, gdel); }
-        CKL("k_rs_scatter(slab)");
-    }
-    CK(hipStreamSynchronize(ctx->stream));                    // (h_rs_del / h_rs_lens were read from host vectors)
-    // groups of buckets that share their top sb bits, each <= RS_MAX_ROWS rows; a single bucket above that stands alone (library sort)
-    const u64 rs_max = ctx->tune.rs_max_rows ? std::min<u64>(ctx->tune.rs_max_rows, RS_MAX_ROWS) : RS_MAX_ROWS;
-    int sb = bA;
-    for (int bits = 0; bits <= bA; ++bits) {
-        const u32 per = NB >> bits;
-        bool ok = true;
-        for (u32 g0 = 0; g0 < NB && ok; g0 += per) ok = B[g0 + per] - B[g0] <= rs_max;
-        if (ok) { sb = bits; break; }
-    }
-    const u32 per = NB >> sb;
-    ctx->h_ovs.assign(1, 0);
-    u32 ngroups = 0, nlib = 0;
-    for (u32 g0 = 0; g0 < NB; g0 += per) {
-        const u64 b = B[g0], e = B[g0 + per], m = e - b;
-        if (m < 2 || total - sb < 1) continue;
-        ++ngroups;
-        bool lib = m > rs_max;
-        if (!lib) {
-            CK(hipMemsetAsync(sc + SC_SORTFLAG, 0, 4, ctx->stream)); CK(hipMemsetAsync(ctx->rs_ovs.p, 0, 4, ctx->stream));
-            if (W == 1) {
-                const int rc = msd_sort_pairs(ctx, tk + b, tv + b, k + b, v + b, m, total - sb, false, 0u);
-                if (rc) return rc;
-                ctx->h_ovs.assign(1, 0);
-                CK(hipMemcpyAsync(&ctx->h_back[3], sc + SC_SORTFLAG, 4, hipMemcpyDeviceToHost, ctx->stream));
-                CK(hipMemcpyAsync(ctx->h_ovs.data(), ctx->rs_ovs.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-                CK(hipStreamSynchronize(ctx->stream));
-                if (!ctx->h_back[3] && ctx->h_ovs[0]) { const int e2 = sort_oversize_round(ctx, tk + b, tv + b, 0); if (e2) return e2; CK(hipStreamSynchronize(ctx->stream)); }
-            } else {
-                const Rows2 r2{T.hi + b, T.lo + b, T.ab + b}, s2{K.hi + b, K.lo + b, K.ab + b};
-                const int rc = msd_sort_rows2(ctx, r2, s2, m, total - sb, false, 0u);
-                if (rc) return rc;
-                { const int e2 = rows2_rounds(ctx, r2, s2); if (e2) return e2; }      // (synchronises; leaves the flag in h_back[3])
-            }
-            lib = ctx->h_back[3] != 0;
-        }
-        if (lib && m >= 0xFFFF0000ull) return fail(ctx, DSKGPU_E_OVERFLOW, "row sort: one value range of the >= 2^32 rows holds 2^32 rows itself (not a k-mer spectrum)");
-        if (lib && W == 2) {
-            // two-word rows of this group in full-width order: W stable radix passes over an index permutation, gathered into the
-            // other copy and copied back (the group's rows in T are a complete permutation whatever the MSD kernels did to them)
-            const u64* src[2] = {T.lo + b, T.hi + b};
-            { const int rc = sort_index_multiword(ctx, src, m, 2); if (rc) return rc; }
-            const unsigned gb = (unsigned)((m + 255) / 256);
-            const u32* idx = ctx->srt_idx.as<u32>();
-            hipLaunchKernelGGL(k_gather<u64>, dim3(gb), dim3(256), 0, ctx->stream, K.lo + b, (const u64*)(T.lo + b), idx, m);
-            hipLaunchKernelGGL(k_gather<u64>, dim3(gb), dim3(256), 0, ctx->stream, K.hi + b, (const u64*)(T.hi + b), idx, m);
-            hipLaunchKernelGGL(k_gather<u32>, dim3(gb), dim3(256), 0, ctx->stream, K.ab + b, (const u32*)(T.ab + b), idx, m);
-            CKL("row sort: group gather");
-            CK(hipMemcpyAsync(T.lo + b, K.lo + b, m * 8, hipMemcpyDeviceToDevice, ctx->stream));
-            CK(hipMemcpyAsync(T.hi + b, K.hi + b, m * 8, hipMemcpyDeviceToDevice, ctx->stream));
-            CK(hipMemcpyAsync(T.ab + b, K.ab + b, m * 4, hipMemcpyDeviceToDevice, ctx->stream));
-            CK(hipStreamSynchronize(ctx->stream));
-            ctx->stats.sort_fallback = 1; ++nlib;
-        } else if (lib) {
-            size_t tmp = 0;
-            const unsigned end_bit = (unsigned)(total - sb);
-            // LIBRARY SORT (rocprim), labelled FALLBACK: one group of a >= 2^32-row set that the MSD kernels gave up on (or that exceeds them alone)
-            CK(rocprim::radix_sort_pairs(nullptr, tmp, tk + b, k + b, tv + b, v + b, (size_t)m, 0u, end_bit, ctx->stream));
-            CK(ctx->srt_tmp.ensure(tmp));
-            CK(rocprim::radix_sort_pairs(ctx->srt_tmp.p, tmp, tk + b, k + b, tv + b, v + b, (size_t)m, 0u, end_bit, ctx->stream));
-            CK(hipMemcpyAsync(tk + b, k + b, m * 8, hipMemcpyDeviceToDevice, ctx->stream));
-            CK(hipMemcpyAsync(tv + b, v + b, m * 4, hipMemcpyDeviceToDevice, ctx->stream));
-            CK(hipStreamSynchronize(ctx->stream));
-            ctx->stats.sort_fallback = 1; ++nlib;
-        }
-    }
-    if (ctx->tune.verbose) fprintf(stderr, "[dskgpu] row sort: %llu rows (>= 2^32 path) in %u slab(s), %u group(s) on their top %d bits, %u through the library sort\n", (unsigned long long)n, S, ngroups, sb, nlib);
-    ctx->h_back[3] = 0; ctx->h_ovs.assign(1, 0);
-    ctx->sort_partial = false; ctx->rows2_in_scratch = false;
-    if (W == 1) { ctx->res_w[0] = tk; ctx->res_ab = tv; }
-    else { ctx->res_w[1] = T.hi; ctx->res_w[0] = T.lo; ctx->res_ab = T.ab; }
-    return DSKGPU_OK;
-}
-
-// ---- DSKGPU_F_PARTITION_ORDER: one-word rows of a single pass, ordered inside output partitions of <= PS_CAP rows by one LDS pass
-// (partsort.h).  In: the sparse rows (ctx->sp_rows).  Out: srt_w[0] / srt_ab dense, partition after partition; part_off on the device
-// and (after the caller's synchronisation) in h_part_off; SC_SORTFLAG raised when a block could not order its partition.
-// one launch: the sparse rows `spr` / `spr2` (W = 1 / 2) -> dense rows at ov / o2, partition offsets (relative to the first row) at d_part_off
-// [0 .. *nparts], *d_flag raised when a block could not order its partition (the rows are complete either way)
-int launch_part_sort(dskgpu_ctx* ctx, int W, const dskgpu_ctx::SparseRows& spr, const dskgpu_ctx::SparseRows2& spr2, u64* ov, u32* oab, Rows2 o2,
-                     u32* d_part_off, u32* d_flag, u32* nparts_out, u32* qpp_out) {
-    const u64 F = W == 1 ? spr.s.F : spr2.s.F, n_sparse = W == 1 ? spr.n_sparse : spr2.n_sparse;
-    const u32 n_tail = W == 1 ? spr.n_tail : spr2.n_tail;
-    const u64 cap_rows = W == 1 ? PS_CAP : PS2_CAP;
-    const u64 mean = std::max<u64>(1, (n_sparse + F - 1) / std::max<u64>(F, 1));
-    const u32 qpp = (u32)std::min<u64>(std::max<u64>(1, (cap_rows * 3 / 4) / mean), PS_MAXQ);
-    const u32 nps = (u32)((F + qpp - 1) / qpp), nparts = nps + (n_tail ? 1u : 0u);
-    const int sh = std::max(0, 2 * (int)ctx->cfg.kmer_size - 12);
-    const PsParams pp{qpp, nps, W == 1 ? std::min(sh, 52) : sh, n_tail, ctx->tune.ps_maxc ? std::min<u32>(ctx->tune.ps_maxc, PS_MAXC) : PS_MAXC};
-    if (W == 1) hipLaunchKernelGGL(k_part_sort, dim3(nparts), dim3(PS_NT), 0, ctx->stream, spr.s, spr.tail_k, spr.tail_v, pp, ov, oab, d_part_off, d_flag);
-    else hipLaunchKernelGGL(k_part_sort2, dim3(nparts), dim3(PS_NT), 0, ctx->stream, spr2.s, spr2.tail, pp, o2, d_part_off, d_flag);
-    CKL("k_part_sort");
-    *nparts_out = nparts; if (qpp_out) *qpp_out = qpp;
-    return DSKGPU_OK;
-}
-// partitions a launch will make for F sub-partitions holding n_sparse rows (+ a tail)
-u32 part_sort_nparts(int W, u64 F, u64 n_sparse, u32 n_tail) {
-    const u64 cap_rows = W == 1 ? PS_CAP : PS2_CAP;
-    const u64 mean = std::max<u64>(1, (n_sparse + F - 1) / std::max<u64>(F, 1));
-    const u32 qpp = (u32)std::min<u64>(std::max<u64>(1, (cap_rows * 3 / 4) / mean), PS_MAXQ);
-    return (u32)((F + qpp - 1) / qpp) + (n_tail ? 1u : 0u);
-}
-int sort_rows_partition_order(dskgpu_ctx* ctx, u64 n) {
-    const int W = ctx->W;
-    const dskgpu_ctx::SparseRows spr = ctx->sp_rows;
-    const dskgpu_ctx::SparseRows2 spr2 = ctx->sp_rows2;
-    ctx->sp_rows_saved = spr; ctx->sp_rows2_saved = spr2;
-    ctx->sp_rows.valid = false; ctx->sp_rows2.valid = false;
-    const u32 nparts = part_sort_nparts(W, W == 1 ? spr.s.F : spr2.s.F, W == 1 ? spr.n_sparse : spr2.n_sparse, W == 1 ? spr.n_tail : spr2.n_tail);
-    for (int x = 0; x < W; ++x) CK(ctx->srt_w[x].ensure(n * 8));
-    CK(ctx->srt_ab.ensure(n * 4));
-    CK(ctx->part_off.ensure(((size_t)nparts + 2) * 4));
-    if (ctx->h_part_cap < (size_t)nparts + 2) {
-        if (ctx->h_part_off) CK(hipHostFree(ctx->h_part_off));
-        ctx->h_part_off = nullptr; ctx->h_part_cap = 0;
-        CK(hipHostMalloc(reinterpret_cast<void**>(&ctx->h_part_off), ((size_t)nparts + 2) * 4 * 2, hipHostMallocDefault));
-        ctx->h_part_cap = ((size_t)nparts + 2) * 2;
-    }
-    u32* sc = ctx->scalars.as<u32>();
-    hipLaunchKernelGGL(k_set_rs_scalars, dim3(1), dim3(64), 0, ctx->stream, sc + SC_RSLEN, 0u, 1u, sc + SC_SORTFLAG, (u32*)nullptr);
-    u32 np = 0;
-    { const int rc = launch_part_sort(ctx, W, spr, spr2, ctx->srt_w[0].as<u64>(), ctx->srt_ab.as<u32>(), Rows2{ctx->srt_w[1].as<u64>(), ctx->srt_w[0].as<u64>(), ctx->srt_ab.as<u32>()},
-                                      ctx->part_off.as<u32>(), sc + SC_SORTFLAG, &np, nullptr); if (rc) return rc; }
-    CK(hipMemcpyAsync(ctx->h_part_off, ctx->part_off.p, ((size_t)nparts + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
-    ctx->part_mode = true; ctx->n_parts = nparts; ctx->h_part_off64.clear();
-    ctx->h_ovs.assign(1, 0);
-    ctx->sort_back = 2;            // (the flag travels with the histogram: run_pipeline)
-    ctx->sort_partial = false;
-    for (int x = 0; x < W; ++x) ctx->res_w[x] = ctx->srt_w[x].as<u64>();
-    ctx->res_ab = ctx->srt_ab.as<u32>();
-    return DSKGPU_OK;
-}
-
-// ---- result post-processing: sort rows by k-mer value
-int sort_rows(dskgpu_ctx* ctx, u64 n) {
-    const int W = ctx->W;
-    for (int x = 0; x < 4; ++x) ctx->res_w[x] = x < W ? ctx->out_w[x].as<u64>() : nullptr;
-    ctx->res_ab = ctx->out_ab.as<u32>();
-    ctx->sort_partial = false;
-    ctx->rows2_in_scratch = false;
-    ctx->part_mode = false;
-    ctx->h_ovs.assign(1, 0);
-    if ((ctx->sp_rows.valid && (n == 0 || (ctx->cfg.flags & DSKGPU_F_NO_SORT) || W != 1)) || (ctx->sp_rows2.valid && (n == 0 || (ctx->cfg.flags & DSKGPU_F_NO_SORT) || W != 2)))
-        return fail(ctx, DSKGPU_E_STATE, "row sort: sparse rows on a path that cannot read them");
-    if (n == 0 || (ctx->cfg.flags & DSKGPU_F_NO_SORT)) return DSKGPU_OK;
-    if ((ctx->sp_rows.valid || ctx->sp_rows2.valid) && (ctx->cfg.flags & DSKGPU_F_PARTITION_ORDER) && !ctx->part_off_this_count && n < 0xFFFF0000ull) return sort_rows_partition_order(ctx, n);
-    if (ctx->sp_rows.valid) {      // the rows of a single one-word pass, still in the count kernel's regions (run_one_pass made sure this sort takes them)
-        CK(ctx->srt_w[0].ensure(n * 8)); CK(ctx->srt_ab.ensure(n * 4));
-        ctx->fb_src_k = ctx->srt_w[0].as<u64>(); ctx->fb_src_v = ctx->srt_ab.as<u32>(); ctx->fb_dst_k = ctx->out_w[0].as<u64>(); ctx->fb_dst_v = ctx->out_ab.as<u32>();
-        return sort_rows_msd(ctx, n);
-    }
-    if (ctx->sp_rows2.valid) return sort_rows2_msd(ctx, n);      // (the two-word twin)
-    const u64 rs_max = ctx->tune.rs_max_rows ? std::min<u64>(ctx->tune.rs_max_rows, RS_MAX_ROWS) : RS_MAX_ROWS;
-    // 2^32 rows and more (or DSKGPU_RS_SLAB_ROWS: tests): step A slab by slab with 64-bit bucket offsets
-    if ((n >= 0xFFFF0000ull || ctx->tune.rs_slab_rows) && W <= 2 && (W == 1 || 2u * ctx->cfg.kmer_size > 64u)) return W == 1 ? sort_rows_huge<1>(ctx, n) : sort_rows_huge<2>(ctx, n);
-    if (n >= 0xFFFF0000ull) return fail(ctx, DSKGPU_E_ARG, "row sort: 2^32 rows and more are supported for k <= 64");
-    if (W == 1 && n > rs_max && n < 0xFFFF0000ull) return sort_rows_big(ctx, n);
-    CK(ctx->srt_w[0].ensure(n * 8));
-    CK(ctx->srt_ab.ensure(n * 4));
-    ctx->fb_src_k = ctx->srt_w[0].as<u64>(); ctx->fb_src_v = ctx->srt_ab.as<u32>(); ctx->fb_dst_k = ctx->out_w[0].as<u64>(); ctx->fb_dst_v = ctx->out_ab.as<u32>();
-    size_t tmp = 0;
-    // one-word rows: the hand-written MSD sort (rowsort.h) -- in one piece here, group by group / slab by slab above
-    if (W == 1) return sort_rows_msd(ctx, n);
-    // two-word rows: the rows themselves through the MSD sort (rowsort2.h)
-    if (W == 2 && n < 0xFFFF0000ull)
-        return n <= rs_max ? sort_rows2_msd(ctx, n) : sort_rows2_big(ctx, n);
-    // four-word rows (k > 64): (top 63 bits of the value, row index) pairs through the MSD sort, gather, then the runs of equal prefix are
-    // ordered in place by full comparison (exact fallback: sort_rows_full_multiword).  Row sets above RS_MAX_ROWS: the pairs through the
-    // LIBRARY radix sort on their top 32 bits instead (rocprim: the one library sort on a non-fallback path; 384 M four-word rows are 14 GB)
-    {
-        CK(ctx->srt_k.ensure(n * 8)); CK(ctx->s_val.ensure(n * 8));
-        CK(ctx->srt_idx.ensure(n * 4)); CK(ctx->srt_idx2.ensure(n * 4));
-        const unsigned gb = (unsigned)((n + 255) / 256);
-        RowsIn ri{}; RowsOut ro{};
-        for (int x = 0; x < W; ++x) { CK(ctx->srt_w[x].ensure(n * 8)); ri.w[x] = ctx->out_w[x].as<u64>(); ro.w[x] = ctx->srt_w[x].as<u64>(); }
-        const int bits = 2 * (int)ctx->cfg.kmer_size;
-        const bool msd = n <= RS_MAX_ROWS;
-        u64* aos = nullptr;
-        if (msd) {      // + one record per row for the gather (the full-width fallback buffers are free until then)
-            CK(ctx->srt_k2.ensure(n * 8 * (size_t)(W == 2 ? AosRow<2>::WORDS : AosRow<4>::WORDS)));
-            aos = ctx->srt_k2.as<u64>();
-            if (W == 2) hipLaunchKernelGGL(k_top_key_aos<2>, dim3(gb), dim3(256), 0, ctx->stream, ri, ctx->out_ab.as<u32>(), n, bits, ctx->srt_k.as<u64>(), ctx->srt_idx.as<u32>(), aos);
-            else hipLaunchKernelGGL(k_top_key_aos<4>, dim3(gb), dim3(256), 0, ctx->stream, ri, ctx->out_ab.as<u32>(), n, bits, ctx->srt_k.as<u64>(), ctx->srt_idx.as<u32>(), aos);
-        } else if (W == 2) hipLaunchKernelGGL(k_top_key<2>, dim3(gb), dim3(256), 0, ctx->stream, ri, n, bits, ctx->srt_k.as<u64>(), ctx->srt_idx.as<u32>());
-        else hipLaunchKernelGGL(k_top_key<4>, dim3(gb), dim3(256), 0, ctx->stream, ri, n, bits, ctx->srt_k.as<u64>(), ctx->srt_idx.as<u32>());
-        u32* flag = ctx->scalars.as<u32>() + SC_SORTFLAG;
-        const u32* ties = nullptr;                     // MSD path: the tie pass returns at once unless the sort met equal keys
-        const u32* idx; const u64* skey; int run_shift;
-        if (msd) {
-            // the hand-written MSD sort on (top 63 bits, row index): fully ordered by those 63 bits, what is left to k_fix_runs_multi
-            // are the rows that share all of them
-            const int e = msd_sort_pairs(ctx, ctx->srt_k.as<u64>(), ctx->srt_idx.as<u32>(), ctx->s_val.as<u64>(), ctx->srt_idx2.as<u32>(), n, 63);
-            if (e) return e;
-            // sub-buckets the sort listed for another round (thousands of rows sharing 26 and more leading bits): ordered before the rows are
-            // gathered by index (one host round trip; a 63-bit prefix leaves ties to k_fix_runs_multi either way)
-            CK(hipMemcpyAsync(&ctx->h_back[3], flag, 4, hipMemcpyDeviceToHost, ctx->stream));
-            CK(hipMemcpyAsync(ctx->h_ovs.data(), ctx->rs_ovs.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-            CK(hipStreamSynchronize(ctx->stream));
-            if (!ctx->h_back[3] && ctx->h_ovs[0]) {
-                ctx->rs_res_k = ctx->srt_k.as<u64>(); ctx->rs_res_v = ctx->srt_idx.as<u32>(); ctx->rs_tmp_k = ctx->s_val.as<u64>(); ctx->rs_tmp_v = ctx->srt_idx2.as<u32>();
-                const int e2 = sort_oversize(ctx);
-                if (e2) return e2;
-                ctx->h_ovs.assign(1, 0);
-            }
-            idx = ctx->srt_idx.as<u32>(); skey = ctx->srt_k.as<u64>(); run_shift = 0; ties = ctx->scalars.as<u32>() + SC_RSTIES;
-        } else {
-            const unsigned begin_bit = 63u - SORT_TOP_BITS;
-            // LIBRARY SORT (rocprim), labelled: four-word rows (k > 64) above RS_MAX_ROWS = 384 M rows -- the (63-bit key, index) pairs on their top 32 bits
-            CK(rocprim::radix_sort_pairs(nullptr, tmp, ctx->srt_k.as<u64>(), ctx->s_val.as<u64>(), ctx->srt_idx.as<u32>(), ctx->srt_idx2.as<u32>(),
-                                         (size_t)n, begin_bit, 63u, ctx->stream));
-            CK(ctx->srt_tmp.ensure(tmp));
-            CK(rocprim::radix_sort_pairs(ctx->srt_tmp.p, tmp, ctx->srt_k.as<u64>(), ctx->s_val.as<u64>(), ctx->srt_idx.as<u32>(), ctx->srt_idx2.as<u32>(),
-                                         (size_t)n, begin_bit, 63u, ctx->stream));
-            CK(hipMemsetAsync(flag, 0, 4, ctx->stream));
-            idx = ctx->srt_idx2.as<u32>(); skey = ctx->s_val.as<u64>(); run_shift = (int)begin_bit;
-        }
-        if (aos) {
-            if (W == 2) hipLaunchKernelGGL(k_gather_aos<2>, dim3(gb), dim3(256), 0, ctx->stream, ro, ctx->srt_ab.as<u32>(), aos, idx, n);
-            else hipLaunchKernelGGL(k_gather_aos<4>, dim3(gb), dim3(256), 0, ctx->stream, ro, ctx->srt_ab.as<u32>(), aos, idx, n);
-        } else {
-            const unsigned gb4 = (unsigned)((n + 1023) / 1024);
-            if (W == 2) hipLaunchKernelGGL(k_gather_rows<2>, dim3(gb4), dim3(256), 0, ctx->stream, ro, ctx->srt_ab.as<u32>(), ri, ctx->out_ab.as<u32>(), idx, n);
-            else hipLaunchKernelGGL(k_gather_rows<4>, dim3(gb4), dim3(256), 0, ctx->stream, ro, ctx->srt_ab.as<u32>(), ri, ctx->out_ab.as<u32>(), idx, n);
-        }
-        const unsigned gfix = (unsigned)std::min<u64>(gb, (u64)ctx->num_cu * 32);      // grid-stride kernel: when there are no ties its blocks leave at once
-        CK(ctx->fix_list.ensure((1 + 2 * (size_t)FIX_LIST_CAP) * 4));
-        CK(hipMemsetAsync(ctx->fix_list.p, 0, 4, ctx->stream));
-        u32* fl = ctx->fix_list.as<u32>();
-        const unsigned glong = (unsigned)ctx->num_cu;
-        if (W == 2) {
-            hipLaunchKernelGGL(k_fix_runs_multi<2>, dim3(gfix), dim3(256), 0, ctx->stream, ro, ctx->srt_ab.as<u32>(), skey, n, run_shift, flag, ties, fl);
-            hipLaunchKernelGGL(k_fix_long_runs<2>, dim3(glong), dim3(1024), 0, ctx->stream, ro, ctx->srt_ab.as<u32>(), (const u32*)fl, ties);
-        } else {
-            hipLaunchKernelGGL(k_fix_runs_multi<4>, dim3(gfix), dim3(256), 0, ctx->stream, ro, ctx->srt_ab.as<u32>(), skey, n, run_shift, flag, ties, fl);
-            hipLaunchKernelGGL(k_fix_long_runs<4>, dim3(glong), dim3(1024), 0, ctx->stream, ro, ctx->srt_ab.as<u32>(), (const u32*)fl, ties);
-        }
-        CKL("sort_rows");
-        CK(hipMemcpyAsync(&ctx->h_back[3], flag, 4, hipMemcpyDeviceToHost, ctx->stream));
-        ctx->sort_partial = true;
-        for (int x = 0; x < W; ++x) ctx->res_w[x] = ctx->srt_w[x].as<u64>();
-        ctx->res_ab = ctx->srt_ab.as<u32>();
-        return DSKGPU_OK;
-    }
 }
 
 // k-mers per chunk of received records (k_sk_count) -> chunk bases for the expansion, and the total.  Needed up front only when
@@ -2174,7 +1098,7 @@ int run_one_pass(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_
         // (k_compact: 0.5 GB read + 0.5 GB written, 0.30 ms of a 14 ms step).  Several passes accumulate dense rows as before.
         bool sparse_sort = false;
         if constexpr (W == 1) {
-            const u64 rs_max = ctx->tune.rs_max_rows ? std::min<u64>(ctx->tune.rs_max_rows, RS_MAX_ROWS) : RS_MAX_ROWS;
+            const u64 rs_max = rs_max_rows(ctx);
             sparse_sort = npass == 1 && ctx->job_passes == 1 && ns > 0 && ns <= rs_max && !(ctx->cfg.flags & DSKGPU_F_NO_SORT) &&
                           !ctx->tune.rs_slab_rows && !ctx->bank_job.active;
             if (sparse_sort) {
@@ -2187,7 +1111,7 @@ int run_one_pass(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_
             }
         }
         if constexpr (W == 2) {      // (two-word rows: the same, through rowsort2.h's sparse step A -- sort_rows2_msd is what sort_rows picks under these conditions)
-            const u64 rs_max = ctx->tune.rs_max_rows ? std::min<u64>(ctx->tune.rs_max_rows, RS_MAX_ROWS) : RS_MAX_ROWS;
+            const u64 rs_max = rs_max_rows(ctx);
             sparse_sort = npass == 1 && ctx->job_passes == 1 && ns > 0 && ns <= rs_max && !(ctx->cfg.flags & DSKGPU_F_NO_SORT) &&
                           !ctx->tune.rs_slab_rows && !ctx->bank_job.active && 2u * ctx->cfg.kmer_size > 64u;
             if (sparse_sort) {
@@ -2660,93 +1584,12 @@ int run_pipeline(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_
             if (seen + (1u << 20) < 0xFFFF0000ull && seen > cap_floor) cap_floor = seen + (1u << 20); else { npass *= 2; cap_floor = 0; }
             continue;
         }
-        // ---------------- partition order over all passes: every pass ordered its partitions on the way in -- nothing left to sort unless a block gave up
-        bool mp_done = false;
-        if (npass > 1 && ctx->mp_part_ok && !ctx->mp_parts.empty()) {
-            u32 h_flag = 1;
-            ctx->h_mp_off.resize(ctx->mp_off_used);
-            CK(hipMemcpyAsync(&h_flag, ctx->mp_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-            CK(hipMemcpyAsync(ctx->h_mp_off.data(), ctx->mp_part_off.p, (size_t)ctx->mp_off_used * 4, hipMemcpyDeviceToHost, ctx->stream));
-            CK(hipStreamSynchronize(ctx->stream));
-            if (!h_flag) {
-                ctx->h_part_off64.clear();
-                for (const auto& mp : ctx->mp_parts)
-                    for (u32 i = 0; i < mp.nparts; ++i) ctx->h_part_off64.push_back(mp.row_base + ctx->h_mp_off[mp.off_index + i]);
-                ctx->h_part_off64.push_back(tot_rows);
-                ctx->part_mode = true; ctx->n_parts = (u32)(ctx->h_part_off64.size() - 1);
-                for (int x = 0; x < 4; ++x) ctx->res_w[x] = x < W ? ctx->acc_w[x].as<u64>() : nullptr;
-                ctx->res_ab = ctx->acc_ab.as<u32>();
-                ctx->sort_partial = false; ctx->sp_rows.valid = false; ctx->sp_rows2.valid = false;
-                ctx->h_back[3] = 0; ctx->h_ovs.assign(1, 0);
-                mp_done = true;
-            } else if (ctx->tune.verbose) fprintf(stderr, "[dskgpu] row order: a partition of one pass exceeds what one block orders -- global order over all passes instead\n");
-        }
-        // ---------------- row sort over all passes
-        if (npass > 1 && !mp_done) {      // make the accumulated rows the sort input
+        // ---------------- row order over all passes
+        if (npass > 1) {      // make the accumulated rows the sort input
             std::swap(ctx->out_ab, ctx->acc_ab);
             for (int x = 0; x < W; ++x) std::swap(ctx->out_w[x], ctx->acc_w[x]);
         }
-        int rc;
-        ctx->part_off_this_count = false;
-        if (mp_done) goto sort_done;
-      sort_again:
-        ctx->sort_back = 0;
-        if ((rc = sort_rows(ctx, tot_rows))) return rc;
-        ctx->mark("sort");
-        if (ctx->sort_back) {      // histogram + the sort's two words: one copy into pinned memory (three pageable ones were ~25 us of idle GPU each)
-            const size_t nh = ctx->hist.size();
-            if (ctx->hist_pin_n < nh + 2) {
-                if (ctx->hist_pin) CK(hipHostFree(ctx->hist_pin));
-                ctx->hist_pin = nullptr; ctx->hist_pin_n = 0;
-                CK(hipHostMalloc(reinterpret_cast<void**>(&ctx->hist_pin), (nh + 2) * 8, hipHostMallocDefault));
-                ctx->hist_pin_n = nh + 2;
-            }
-            u64* gh = ctx->ghist.as<u64>();
-            hipLaunchKernelGGL(k_sort_back, dim3(1), dim3(64), 0, ctx->stream, (const u32*)ctx->scalars.as<u32>(),
-                               ctx->sort_back == 1 ? (const u32*)ctx->rs_ovs.as<u32>() : (const u32*)nullptr, gh + nh);
-            CKL("k_sort_back");
-            const size_t from = npass == 1 ? 0 : nh;
-            CK(hipMemcpyAsync(ctx->hist_pin + from, gh + from, (nh + 2 - from) * 8, hipMemcpyDeviceToHost, ctx->stream));
-            CK(hipStreamSynchronize(ctx->stream));
-            ctx->h_back[3] = (u32)ctx->hist_pin[nh]; ctx->h_ovs.assign(1, (u32)ctx->hist_pin[nh + 1]);
-            if (npass == 1) memcpy(ctx->hist.data(), ctx->hist_pin, nh * 8);
-            ctx->sort_back = 0;
-        } else {
-            if (npass == 1) CK(hipMemcpyAsync(ctx->hist.data(), ctx->ghist.p, ctx->hist.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-            CK(hipStreamSynchronize(ctx->stream));
-        }
-        if (ctx->part_mode && ctx->h_back[3]) {      // a partition (or a value bin of one) above what a block orders in LDS: the global sort, on the same sparse rows
-            if (ctx->tune.verbose) fprintf(stderr, "[dskgpu] row sort: a partition exceeds what one block orders -- global order instead of partition order\n");
-            ctx->part_mode = false; ctx->part_off_this_count = true; ctx->h_back[3] = 0;
-            ctx->sp_rows = ctx->sp_rows_saved; ctx->sp_rows2 = ctx->sp_rows2_saved;
-            goto sort_again;
-        }
-        if (W == 1 && ctx->sort_partial && tot_rows && !ctx->h_back[3] && !ctx->h_ovs.empty() && ctx->h_ovs[0]) {
-            if ((rc = sort_oversize(ctx))) return rc;      // sub-buckets the sort listed for another round on their remaining bits
-        } else if (W > 1 && ctx->sort_partial && !ctx->h_ovs.empty() && ctx->h_ovs[0]) ctx->h_back[3] = 1;      // (index pairs of multi-word rows: the full-width order)
-        if (W == 1 && ctx->sort_partial && tot_rows && ctx->h_back[3]) {
-            // a run of equal 32-bit prefixes was too long for the in-place fix-up: sort full width
-            // (srt_* holds a permutation of the rows; sort it back into out_*)
-            size_t tmp = 0;
-            const unsigned end_bit = std::min(64u, 2u * ctx->cfg.kmer_size);
-            // LIBRARY SORT (rocprim), labelled FALLBACK: the one-word row sort raised its flag (a value distribution no k-mer spectrum has): full-width order of all rows
-            CK(rocprim::radix_sort_pairs(nullptr, tmp, ctx->fb_src_k, ctx->fb_dst_k, ctx->fb_src_v, ctx->fb_dst_v, (size_t)tot_rows, 0u, end_bit, ctx->stream));
-            CK(ctx->srt_tmp.ensure(tmp));
-            CK(rocprim::radix_sort_pairs(ctx->srt_tmp.p, tmp, ctx->fb_src_k, ctx->fb_dst_k, ctx->fb_src_v, ctx->fb_dst_v, (size_t)tot_rows, 0u, end_bit, ctx->stream));
-            CK(hipStreamSynchronize(ctx->stream));
-            ctx->res_w[0] = ctx->fb_dst_k; ctx->res_ab = ctx->fb_dst_v;
-            ctx->stats.sort_fallback = 1;
-        } else if (W > 1 && ctx->sort_partial && tot_rows && ctx->h_back[3]) {
-            if (ctx->rows2_in_scratch) {      // (two-word rows above RS_MAX_ROWS: the complete permutation is the scratch copy)
-                CK(hipMemcpyAsync(ctx->out_w[1].p, ctx->rows2_scratch.hi, tot_rows * 8, hipMemcpyDeviceToDevice, ctx->stream));
-                CK(hipMemcpyAsync(ctx->out_w[0].p, ctx->rows2_scratch.lo, tot_rows * 8, hipMemcpyDeviceToDevice, ctx->stream));
-                CK(hipMemcpyAsync(ctx->out_ab.p, ctx->rows2_scratch.ab, tot_rows * 4, hipMemcpyDeviceToDevice, ctx->stream));
-            }
-            if ((rc = sort_rows_full_multiword(ctx, tot_rows))) return rc;      // out_w holds the unsorted rows
-            CK(hipStreamSynchronize(ctx->stream));
-            ctx->stats.sort_fallback = 1;
-        }
-      sort_done:
+        if (const int rc = order_rows(ctx, tot_rows, npass)) return rc;
         ctx->resolve_marks();
         ctx->n_rows = tot_rows;
         ctx->stats.n_bytes = from_reads ? ctx->n_bytes : 0;
@@ -2758,13 +1601,11 @@ int run_pipeline(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_
         ctx->stats.n_passes = npass;
         ctx->stats.n_read_sweeps = npass > 1 ? sweeps : (from_reads ? 1 : 0);
         if (from_reads) ctx->last_rows = tot_rows;
-        if (npass > 1 && !mp_done) {      // the names go back: acc_* stays the job-sized buffer (it holds the result now), out_* the pass-sized one --
+        if (npass > 1) {      // the names go back: acc_* stays the job-sized buffer (it holds the result now), out_* the pass-sized one --
             std::swap(ctx->out_ab, ctx->acc_ab);      // left swapped, the next count grew the small one to job size again (10 GB of hipMalloc + hipFree per call)
             for (int x = 0; x < W; ++x) std::swap(ctx->out_w[x], ctx->acc_w[x]);
         }
-        u32 np = ctx->cfg.nb_partitions ? ctx->cfg.nb_partitions : 4u;
-        if (ctx->part_mode) np = ctx->n_parts;      // (partition order: the partitions are what the blocks of k_part_sort ordered)
-        ctx->stats.n_partitions = np;
+        ctx->stats.n_partitions = rows_partitions(ctx);
         ctx->have_result = true;
         return DSKGPU_OK;
     }
@@ -3134,7 +1975,9 @@ int banks_finish(dskgpu_ctx* ctx) {
             CK(ctx->srt_tmp.ensure(tmp));
             CK(rocprim::radix_sort_pairs(ctx->srt_tmp.p, tmp, ctx->u_w[0].as<u64>(), ctx->s_w[0].as<u64>(), ctx->u_val.as<u64>(), ctx->s_val.as<u64>(), (size_t)nu, 0u, end_bit, ctx->stream));
         } else {
-            if ((rc = sort_index_multiword(ctx, ctx->u_w, nu, W))) return rc;
+            const u64* rows[4] = {nullptr, nullptr, nullptr, nullptr};
+            for (int x = 0; x < W; ++x) rows[x] = ctx->u_w[x].as<u64>();
+            if ((rc = sort_index_multiword(ctx, rows, nu, W))) return rc;
             const u32* idx = ctx->srt_idx.as<u32>();
             for (int x = 0; x < W; ++x) {
                 CK(ctx->s_w[x].ensure((nu + 1) * 8));
@@ -3291,13 +2134,12 @@ void dskgpu_destroy(dskgpu_ctx* ctx) {
                       &ctx->out_ab, &ctx->srt_ab, &ctx->srt_tmp,
                       &ctx->srt_idx, &ctx->srt_idx2, &ctx->srt_k, &ctx->srt_k2, &ctx->abund2, &ctx->acc_ab, &ctx->u_val,
                       &ctx->s_val, &ctx->m_flag, &ctx->m_pos, &ctx->m_sum, &ctx->gh2d,
-                      &ctx->sk_sums, &ctx->sk_cbase, &ctx->sk_keys, &ctx->sk_table, &ctx->sk_load, &ctx->sk_sent, &ctx->cur_state, &ctx->rs_ovs, &ctx->smp_keys, &ctx->sk_lay, &ctx->fix_list, &ctx->sk_cb64, &ctx->rs_del, &ctx->rs_lens, &ctx->back_dev};
+                      &ctx->sk_sums, &ctx->sk_cbase, &ctx->sk_keys, &ctx->sk_table, &ctx->sk_load, &ctx->sk_sent, &ctx->cur_state, &ctx->smp_keys, &ctx->sk_lay, &ctx->sk_cb64, &ctx->back_dev};
     if (ctx->back_host) (void)hipHostFree(ctx->back_host);
-    if (ctx->hist_pin) (void)hipHostFree(ctx->hist_pin);
-    if (ctx->h_part_off) (void)hipHostFree(ctx->h_part_off);
+    ctx->rs.release();
     if (ctx->land) (void)hipHostFree(ctx->land);
     for (DevBuf* b : bufs) b->release();
-    for (int i = 0; i < 4; ++i) { ctx->rs_g[i].release(); ctx->out_w[i].release(); ctx->srt_w[i].release(); ctx->acc_w[i].release(); ctx->u_w[i].release(); ctx->s_w[i].release(); }
+    for (int i = 0; i < 4; ++i) { ctx->out_w[i].release(); ctx->srt_w[i].release(); ctx->acc_w[i].release(); ctx->u_w[i].release(); ctx->s_w[i].release(); }
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     for (int i = 0; i < 2; ++i) { if (ctx->pin[i]) (void)hipHostFree(ctx->pin[i]); if (ctx->pin_ev[i]) (void)hipEventDestroy(ctx->pin_ev[i]); }
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
@@ -3784,26 +2626,16 @@ int dskgpu_set_row_order(dskgpu_ctx* ctx, int partition_order) {
 
 uint32_t dskgpu_num_partitions(const dskgpu_ctx* ctx) { return (ctx && ctx->have_result) ? ctx->stats.n_partitions : 0; }
 
-static void part_range(const dskgpu_ctx* ctx, uint32_t p, u64* b, u64* e) {
-    if (ctx->part_mode) {
-        if (!ctx->h_part_off64.empty()) { *b = ctx->h_part_off64[p]; *e = ctx->h_part_off64[p + 1]; }      // (several passes: 64-bit row numbers)
-        else { *b = ctx->h_part_off[p]; *e = ctx->h_part_off[p + 1]; }
-        return;
-    }
-    const u64 P = ctx->stats.n_partitions, n = ctx->n_rows;
-    *b = n * p / P; *e = n * (p + 1) / P;
-}
-
 uint64_t dskgpu_partition_size(const dskgpu_ctx* ctx, uint32_t p) {
     if (!ctx || !ctx->have_result || p >= ctx->stats.n_partitions) return 0;
-    u64 b, e; part_range(ctx, p, &b, &e); return e - b;
+    u64 b, e; rows_partition_range(ctx, p, &b, &e); return e - b;
 }
 
 int dskgpu_partition_offsets(const dskgpu_ctx* ctx, uint64_t* offsets) {
     if (!ctx || !offsets) return DSKGPU_E_ARG;
     if (!ctx->have_result) return DSKGPU_E_STATE;
     const u32 P = ctx->stats.n_partitions;
-    for (u32 p = 0; p < P; ++p) { u64 b, e; part_range(ctx, p, &b, &e); offsets[p] = b; if (p + 1 == P) offsets[P] = e; }
+    for (u32 p = 0; p < P; ++p) { u64 b, e; rows_partition_range(ctx, p, &b, &e); offsets[p] = b; if (p + 1 == P) offsets[P] = e; }
     if (P == 0) offsets[0] = 0;
     return DSKGPU_OK;
 }
@@ -3813,7 +2645,7 @@ int dskgpu_partition_copy(const dskgpu_ctx* cctx, uint32_t p, uint64_t* kmers, u
     if (!ctx) return DSKGPU_E_ARG;
     if (!ctx->have_result) return DSKGPU_E_STATE;
     if (p >= ctx->stats.n_partitions) return DSKGPU_E_ARG;
-    u64 b, e; part_range(ctx, p, &b, &e);
+    u64 b, e; rows_partition_range(ctx, p, &b, &e);
     const u64 n = e - b;
     if (n == 0) return DSKGPU_OK;
     CK(hipSetDevice(ctx->cfg.device));

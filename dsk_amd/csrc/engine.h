@@ -1,0 +1,267 @@
+// engine.h -- what the two host translation units of libdskgpu share: the context (dskgpu_ctx) with its buffers and switches,
+// the error macros, and the functions one of them calls in the other.  dskgpu.hip runs the count path and the C-ABI;
+// rowsort.hip orders the solid rows (order_rows) and owns the row sort's state (dskgpu_ctx::rs).  Private to the library.
+#pragma once
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/dskgpu.h"
+#include "layouts.h"
+
+hipError_t placed_malloc(void** out, size_t bytes);      // (dskgpu.hip: DSKGPU_PLACE)
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t cap = 0;
+    hipError_t ensure(size_t bytes) {
+        if (bytes <= cap) return hipSuccess;
+        // growing a buffer that exists: 6 % on top, so that a size that wobbles by a few per cent from pass to pass (slices from
+        // sampled loads) does not free and allocate tens of GB again -- near a full HBM that took a second
+        size_t want = ((p ? bytes + bytes / 16 : bytes) + 255) & ~size_t(255);
+        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+        hipError_t e = placed_malloc(&p, want);
+        if (e == hipSuccess) cap = want; else p = nullptr;
+        return e;
+    }
+    // grow, keeping the first `keep` bytes (device-to-device copy on `stream`); returns 0 on success
+    int ensure_keep(size_t bytes, size_t keep, hipStream_t stream) {
+        if (bytes <= cap) return 0;
+        void* np = nullptr;
+        size_t want = ((std::max(bytes, cap + cap / 2) + 255) & ~size_t(255));
+        if (hipMalloc(&np, want) != hipSuccess) return -1;
+        if (keep && p) {
+            if (hipMemcpyAsync(np, p, keep, hipMemcpyDeviceToDevice, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess) { (void)hipFree(np); return -1; }
+        }
+        if (p) (void)hipFree(p);
+        p = np; cap = want;
+        return 0;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+enum Scalar { SC_NCH1 = 0, SC_MLEN1, SC_NCH2, SC_MLEN2, SC_OVERFLOW, SC_F, SC_SORTFLAG, SC_OVF2, SC_OVF1, SC_RSLEN, SC_RSWORK, SC_RSWORK2, SC_RSTIES, SC_EXT, SC_NCHAINED, SC_NCH_S, SC_MLEN_S, SC_WORK2, SC_COUNT = 24 };
+
+struct Stage { const char* name; hipEvent_t ev; };
+
+// Test / experiment switches (NOTEBOOK.md "Environment switches"): read ONCE from the environment when a context is
+// created; none of them changes results.  The launch paths only look at this struct.
+struct Tuning {
+    bool no_opt1 = false, no_opt2 = false;      // DSKGPU_NO_OPT1 / _NO_OPT2: exact histogram + scan path at level 1 / at both levels
+    bool no_aligned = false;                    // DSKGPU_NO_ALIGNED: plain write-out for key-array scatters
+    u32 rs_heavy = 0;                           // DSKGPU_RS_HEAVY: rows of a first-digit bucket above which the row sort gives up (tests)
+    u32 rs_bbits = 0;                           // DSKGPU_RS_BBITS: forced width of the row sort's second digit (8..10; tests)
+    u32 rs_block_rows = 0;                      // DSKGPU_RS_BLOCK_ROWS: largest sub-bucket the hand-written row sort orders itself (tests: provoke its fallback)
+    bool sk_exact = false, no_recsrc = false;   // DSKGPU_SK_EXACT, DSKGPU_NO_RECSRC (multi-GPU sender layout / receiver source)
+    u32 opt_cap = 0;                            // DSKGPU_OPT_CAP: forced level-2 region size (keys)
+    u64 opt_slice = 0;                          // DSKGPU_OPT_SLICE: forced level-1 slice size (keys)
+    u64 sk_slice = 0, sk_minslice = 2000;       // DSKGPU_SK_SLICE, DSKGPU_SK_MINSLICE
+    u32 table_maxload = 0;                      // DSKGPU_TABLE_MAXLOAD: distinct keys a count table may hold (forces the finer-partition retry)
+    long long max_ext = -1;                     // DSKGPU_MAX_EXT: size of the extension-region pool of the level-2 scatter (tests: 0 = no chains)
+    bool no_sample = false;                     // DSKGPU_NO_SAMPLE: level-1 slices from the mean load instead of the sampled per-bin loads
+    bool no_heavy = false;                      // DSKGPU_NO_HEAVY: no k-mer is counted apart by the level-1 scatter
+    bool verbose = false;                       // DSKGPU_VERBOSE: trace of the plan decisions on stderr
+    bool no_level0 = false; u32 l0_passes = 0;  // DSKGPU_NO_LEVEL0: every pass of a multi-pass count re-generates its keys; DSKGPU_L0_PASSES=n: passes per level-0 sweep (tests)
+    u64 rs_max_rows = 0;                        // DSKGPU_RS_MAX_ROWS: most rows the MSD row sort takes in one piece (tests: the group-wise path of huge row sets on a small input)
+    u32 ps_maxc = 0;                            // DSKGPU_PS_MAXC: rows sharing a value bin that the partition-order sort still orders (tests: 1 provokes its fallback to the global order)
+    bool sk_generic = false;                    // DSKGPU_SK_GENERIC: the sender kernels with k and m at run time even for k = 31 / 63 (tests: both forms write the same records)
+    bool l0_keys = false;                       // DSKGPU_L0_KEYS: level 0 as key arrays (k_level0) even where the record-based one applies (experiments, tests)
+    u32 mp_pass_mkeys = 0;                      // DSKGPU_MP_PASS_MKEYS: keys (millions) per pass of an input that needs several passes (default 1000)
+    u64 rs_slab_rows = 0;                       // DSKGPU_RS_SLAB_ROWS: rows per slab of the row sort for >= 2^32 rows (tests: forces that path, with small slabs, on a small input)
+    void read() {
+        auto on = [](const char* n) { return getenv(n) != nullptr; };
+        auto num = [](const char* n, u64 dflt) { const char* e = getenv(n); return e ? (u64)atoll(e) : dflt; };
+        no_opt1 = on("DSKGPU_NO_OPT1"); no_opt2 = on("DSKGPU_NO_OPT2"); no_aligned = on("DSKGPU_NO_ALIGNED");
+        sk_exact = on("DSKGPU_SK_EXACT");
+        no_recsrc = on("DSKGPU_NO_RECSRC");
+        opt_cap = (u32)num("DSKGPU_OPT_CAP", 0) & ~7u; opt_slice = num("DSKGPU_OPT_SLICE", 0) & ~7ull;
+        sk_slice = num("DSKGPU_SK_SLICE", 0); sk_minslice = num("DSKGPU_SK_MINSLICE", 2000);
+        table_maxload = (u32)num("DSKGPU_TABLE_MAXLOAD", 0);
+        max_ext = getenv("DSKGPU_MAX_EXT") ? atoll(getenv("DSKGPU_MAX_EXT")) : -1;
+        no_sample = on("DSKGPU_NO_SAMPLE"); no_heavy = on("DSKGPU_NO_HEAVY"); verbose = on("DSKGPU_VERBOSE"); no_level0 = on("DSKGPU_NO_LEVEL0"); l0_passes = (u32)num("DSKGPU_L0_PASSES", 0); mp_pass_mkeys = (u32)num("DSKGPU_MP_PASS_MKEYS", 0); rs_max_rows = num("DSKGPU_RS_MAX_ROWS", 0); l0_keys = on("DSKGPU_L0_KEYS"); sk_generic = on("DSKGPU_SK_GENERIC"); ps_maxc = (u32)num("DSKGPU_PS_MAXC", 0);
+        rs_slab_rows = num("DSKGPU_RS_SLAB_ROWS", 0);
+        rs_block_rows = (u32)num("DSKGPU_RS_BLOCK_ROWS", 0); rs_bbits = (u32)num("DSKGPU_RS_BBITS", 0); rs_heavy = (u32)num("DSKGPU_RS_HEAVY", 0);
+    }
+};
+
+// The row sort's state between calls (order_rows below owns it; the partition accessors read its layout)
+struct RowSort {
+    DevBuf fix_list;               // multi-word row sort: [count | (first row, rows) x FIX_LIST_CAP] of the prefix runs above FIX_CAP rows
+    DevBuf g[4];                   // the gathered rows of the listed sub-buckets, one buffer per round (sort_oversize)
+    DevBuf del, lens;              // >= 2^32 rows: per (slab, bin) 64-bit output offsets; the slabs' matrix lengths
+    std::vector<u64> h_del; std::vector<u32> h_lens, h_lin;
+    DevBuf ovs;                    // [count | (offset, rows, bits left) x RS_OVS_CAP] of the sub-buckets listed for another round
+    u32 flag = 0, listed = 0;      // host copies of SC_SORTFLAG ("could not finish in place") and of the listed count ovs[0]
+    u64* hist_pin = nullptr; size_t hist_pin_n = 0;      // pinned landing of the end-of-step read-back: histogram + k_sort_back's two words
+    // DSKGPU_F_PARTITION_ORDER (partsort.h): the rows ascending inside each output partition only.  part_mode: the last result is laid
+    // out that way, h_part_off[p] = first row of partition p (n_parts + 1 entries, pinned; several passes: h_part_off64)
+    bool part_mode = false; u32 n_parts = 0; u32* h_part_off = nullptr; size_t h_part_cap = 0; DevBuf part_off;
+    std::vector<u64> h_part_off64;
+    void release() {
+        for (DevBuf* b : {&fix_list, &g[0], &g[1], &g[2], &g[3], &del, &lens, &ovs, &part_off}) b->release();
+        if (hist_pin) (void)hipHostFree(hist_pin);
+        if (h_part_off) (void)hipHostFree(h_part_off);
+        hist_pin = nullptr; h_part_off = nullptr;
+    }
+};
+
+// state of a per-bank count in steps (banks_begin .. banks_finish below)
+struct BankJob { dskgpu_config cfg; const uint8_t* base; u64 total; std::vector<u64> ends; u64 nu, tot_kmers; u32 passes, retries; bool active = false; };
+
+struct dskgpu_ctx {
+    dskgpu_config cfg{};
+    BankJob bank_job{};
+    Tuning tune;
+    int W = 1;
+    int words_out = 1;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    int num_cu = 256;
+    std::string err;
+
+    // input
+    DevBuf reads_own; u64 reads_len = 0;
+    void* pin[2] = {nullptr, nullptr}; hipEvent_t pin_ev[2] = {nullptr, nullptr}; bool pin_used[2] = {false, false}; int pin_next = 0;   // pinned H2D staging
+    const uint8_t* d_reads = nullptr; u64 n_bytes = 0;
+    // dskgpu_push_raw: file text parsed on the device; the stream's length is on the device (RawState) until raw_finish reads it back
+    DevBuf raw_in, raw_blk, raw_boff, raw_bstate, raw_state;
+    bool raw_pending = false; u64 raw_base = 0, raw_ub = 0;      // the stream's length before the raw pushes / an upper bound of it now
+
+    DevBuf packed, inval;          // K1 output
+    DevBuf bufA, bufB;             // partition ping-pong
+    DevBuf mat1, mat2, sums, descs1, descs2, seg, fstart, nsolid, scalars, ghist, gstats, chain_next;
+    RowSort rs;
+    DevBuf smp_keys;               // records: the sample expanded to a key array (16 slots per candidate record, sentinel pads)
+    DevBuf smp_mat, smp_descs, boff;   // sampled level-1 loads: chunk x bin matrix of the sample tiles, their descriptors; per-bin slice offsets
+    DevBuf dbg, l0buf; DevBuf hv_lut, hv_collect, hv_buf; // heavy k-mers: bin -> collect slot, collected sample keys; [keys | counts | rows] of the k-mers counted apart
+    std::vector<unsigned char> h_hv_lut; std::vector<u32> h_hv_cnt, h_hv_step; std::vector<u64> h_hv_coll, h_hv_keys;
+    std::vector<ChunkDesc> h_descs_s; std::vector<u64> h_cbeg; std::vector<u32> h_boff; std::vector<u64> h_mom; std::vector<double> h_load, h_spread, h_seg_work;
+    DevBuf out_w[4], srt_w[4], acc_w[4];   // rows as struct-of-arrays: word i of every row in [i]
+    DevBuf out_ab, srt_ab, srt_tmp, srt_idx, srt_idx2, srt_k, srt_k2, abund2, acc_ab;   // srt_k2: one record per row for the multi-word gather
+    u64 max_keys_per_pass = 0;     // 0 = as many as 32-bit offsets allow
+    // multi-bank mode (solidity kinds, 2-D histogram)
+    std::vector<u64> bank_ends;    // end offset of every declared bank in the read stream
+    DevBuf u_w[4], s_w[4], u_val, s_val, m_flag, m_pos, m_sum, gh2d;
+    std::vector<u64> hist2d;
+    std::vector<u32> h_starts;     // explicit-key exchange: first key of every owner in the send buffer
+    std::vector<u64> h_rstart;     // record exchange: first RECORD of every owner in the send buffer (64-bit: no limit on a rank's shard)
+    std::vector<u32> h_sk_cells;   // ... records per (owner, chunk) as the sizing pass counted them
+    std::vector<u64> h_sk_cb64;    // ... exact layout: their exclusive scan (owner-major) = record index of every (owner, chunk) pair
+    DevBuf sk_cb64;                // ... the same on the device (k_sk_scatter<false>)
+    // multi-GPU exchange as super-k-mer records (superkmer.h)
+    bool enc_keep = false;         // dskgpu_encode_reads: packed / inval hold the 2-bit form of the current reads and the ASCII bytes are gone (d_reads == nullptr)
+    bool enc_fresh = false;        // packed / inval hold the encoding of the current reads, left by dskgpu_mg_sample for the sender's sizing pass of the same step
+    bool sk_mode = false, sk_prepared = false;
+    bool sk_slices = false;        // the prepared send layout is slices from a sampled estimate (else exact offsets)
+    bool sk_exact = false;         // a slice overflowed on these reads: exact counts from now on
+    SkParams sk_sp{};
+    DevBuf sk_sums, sk_cbase, sk_keys, sk_table, sk_load, sk_sent, sk_lay;      // sk_lay: [region base per owner: u64 x 64][slice per owner: u32 x 64] of a record-based level-0 sweep
+    u64 last_rows = 0;             // solid rows of the last count of the current reads (0 = not counted yet): sizes what a multi-pass count keeps free for its rows
+    bool rec_l0_off = false;       // these reads do not take the record-based level 0 (a slice of its sampled layout overflowed)
+    u64 h_sk_sent[SK_MAX_OWNERS] = {0};      // k-mers inside the records the last mg_scatter wrote for every owner
+    u64 h_sk_est[SK_MAX_OWNERS] = {0};       // sampled layout: estimated k-mers per owner (k_sk_hist on every 16th tile, scaled)
+    u32 sk_nslices = 0;                      // dskgpu_mg_slices_prepare: slices of the prepared step (0 = none prepared)
+    u64 rec_hint = 0;                        // dskgpu_mg_count_sized: the caller's k-mer total of the records (0 = none)
+    bool rec_hint_est = false;               // ... an estimate (sliced step): sizes the fast path only, never checked against the result
+    std::vector<u64> rec_slice_end;          // dskgpu_mg_count_sliced: record index where every slice ends; empty = one piece
+    dskgpu_slice_gate rec_gate = nullptr; void* rec_gate_user = nullptr; u32 rec_gated = 0;      // slices whose arrival the stream already waits for
+    bool rec_gate_failed = false;            // a gate said its slice will never arrive: the count stops (DSKGPU_E_STATE)
+    std::vector<u32> h_slice_chunk;          // first level-1 chunk of every slice (+ the end)
+    DevBuf cur_state;                        // parked write cursors of the level-1 blocks between the launches of a sliced receive
+    bool rec_sized = false;                  // per-chunk k-mer sums of the records are on the device (k_sk_count ran)
+    std::vector<uint8_t> h_table;  // the repartition table in use (SK_BUCKETS owners; default: bucket scaled to the world size)
+    bool table_dirty = true;       // h_table not yet copied to sk_table
+    std::vector<u32> h_sk_sums; std::vector<u64> h_sk_cbase;
+    // records handed to dskgpu_mg_count: the level-1 scatter reads them directly (SRC 2); expanded lazily for the exact path
+    const u64* rec_src = nullptr; u64 rec_n = 0; u64 rec_nch = 0, rec_rpc = 0; bool rec_expanded = false;
+    u64* land = nullptr;                             // 64 KB of pinned host memory: where the small per-step read-backs land (landing())
+    DevBuf back_dev; u64* back_host = nullptr;      // the count stage's read-back record (k_gather_back) and its pinned landing zone
+    u32 h_back[3] = {0}; u64 h_stats[4] = {0}; u32 h_ovf2 = 0, h_ovf1 = 0, h_ext = 0; u64 h_nvalid = 0; bool have_nvalid = false;
+    bool sentinel_ok = true;       // the all-ones key is not the mixed form of a canonical k-mer of this k (checked at create)
+    bool opt1_off = false;         // same for the histogram-free level-1 scatter (block-owned slices)
+    bool mw_v3_off = false;        // the top-word table of k_count2v3 met two k-mers it cannot tell apart on these reads: k_count_mw from now on
+    bool opt2_off = false;         // the fixed-capacity level-2 scatter overflowed on these reads: use the exact path   // host landing zone of the async size read-back
+    std::vector<ChunkDesc> h_descs1, h_descs2;
+    std::vector<const void*> big_lds_fns;   // kernels whose dynamic-LDS limit this context has raised (allow_big_lds)
+    u32 h_sc[SC_COUNT] = {0};      // host mirror of the device scalars (kept alive across async copies)
+
+    // the solid rows of a single one-word pass where the count kernel left them (run_one_pass): the row sort's first step reads them there
+    // instead of a dense copy made by k_compact (rowsort.h: RsSparse)
+    u32 job_passes = 1;            // passes of the running count as run_pipeline sees them (a pass of a record-based multi-pass count runs as "pass 0 of 1" inside run_one_pass)
+    struct SparseRows { bool valid = false; RsSparse s{}; u64 n_sparse = 0; const u64* tail_k = nullptr; const u32* tail_v = nullptr; u32 n_tail = 0; } sp_rows;
+    // multi-pass jobs: where a pass may put its dense rows straight away -- the job's accumulators, from row `rows` on (run_pipeline sets it
+    // once they are sized; run_one_pass sets `took` when it did: the pass's rows are then already appended)
+    struct RowSink { bool active = false, took = false; u32* ab = nullptr; u64* w[4] = {nullptr, nullptr, nullptr, nullptr}; u64 rows = 0, cap = 0; } sink;
+    struct SparseRows2 { bool valid = false; Rs2Sparse s{}; u64 n_sparse = 0; Rows2C tail{nullptr, nullptr, nullptr}; u32 n_tail = 0; } sp_rows2;      // (two-word rows)
+    // results
+    bool have_result = false;
+    // DSKGPU_F_PARTITION_ORDER for the passes of a multi-pass count: every pass orders its rows partition by partition straight into the job's row arrays
+    // (one k_part_sort launch instead of k_compact), the offsets of its partitions -- relative to the pass's first row -- go to
+    // mp_part_off[off_index ..], one flag (mp_flag) serves the whole job; at the end the offsets become 64-bit row numbers (h_part_off64)
+    struct MpPart { u64 row_base; u32 nparts, off_index; };
+    std::vector<MpPart> mp_parts; DevBuf mp_part_off, mp_flag; u32 mp_off_used = 0; bool mp_part_ok = false;
+    std::vector<u32> h_mp_off;
+    u64 n_rows = 0;
+    const u64* res_w[4] = {nullptr, nullptr, nullptr, nullptr}; const u32* res_ab = nullptr;
+    dskgpu_stats stats{};
+    std::vector<u64> hist;
+
+    // timing
+    std::vector<Stage> marks;
+    std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
+    std::vector<const char*> st_names; std::vector<float> st_ms;
+
+    void mark(const char* name) {
+        if (!(cfg.flags & DSKGPU_F_TIMING)) return;
+        if (ev_used == ev_pool.size()) { hipEvent_t e; (void)hipEventCreate(&e); ev_pool.push_back(e); }
+        hipEvent_t e = ev_pool[ev_used++];
+        (void)hipEventRecord(e, stream);
+        marks.push_back({name, e});
+    }
+    void resolve_marks() {   // after a stream sync; appends to st_names/st_ms
+        for (size_t i = 0; i + 1 < marks.size(); ++i) {
+            float ms = 0; (void)hipEventElapsedTime(&ms, marks[i].ev, marks[i + 1].ev);
+            // one entry per stage name: the passes of a multi-pass count (and the retries of a pass) add up
+            size_t at = 0;
+            while (at < st_names.size() && std::strcmp(st_names[at], marks[i + 1].name) != 0) ++at;
+            if (at == st_names.size()) { st_names.push_back(marks[i + 1].name); st_ms.push_back(ms); } else st_ms[at] += ms;
+        }
+        marks.clear(); ev_used = 0;
+    }
+};
+
+#define CK(expr)                                                                             \
+    do {                                                                                     \
+        hipError_t e_ = (expr);                                                              \
+        if (e_ != hipSuccess) {                                                              \
+            ctx->err = std::string(#expr) + ": " + hipGetErrorString(e_);                    \
+            return (e_ == hipErrorOutOfMemory) ? DSKGPU_E_NOMEM : DSKGPU_E_DEVICE;           \
+        }                                                                                    \
+    } while (0)
+
+#define CKL(what)                                                                            \
+    do {                                                                                     \
+        hipError_t e_ = hipGetLastError();                                                   \
+        if (e_ != hipSuccess) {                                                              \
+            ctx->err = std::string(what) + ": " + hipGetErrorString(e_);                     \
+            return DSKGPU_E_DEVICE;                                                          \
+        }                                                                                    \
+    } while (0)
+
+inline int fail(dskgpu_ctx* ctx, int code, const std::string& msg) { ctx->err = msg; return code; }
+
+// dskgpu.hip
+int run_scan(dskgpu_ctx* ctx, u32* a, const u32* d_len, u64 max_len);
+int allow_big_lds(dskgpu_ctx* ctx, const void* fn, int bytes = 160 * 1024);      // (bytes: kernels with static LDS next to the dynamic block ask for what they use)
+
+// rowsort.hip
+int order_rows(dskgpu_ctx* ctx, u64 n, u32 npass);
+u64 rs_max_rows(const dskgpu_ctx* ctx);
+int sort_index_multiword(dskgpu_ctx* ctx, const u64* const* rows, u64 n, int W);
+u32 part_sort_nparts(int W, u64 F, u64 n_sparse, u32 n_tail);
+int launch_part_sort(dskgpu_ctx* ctx, int W, const dskgpu_ctx::SparseRows& spr, const dskgpu_ctx::SparseRows2& spr2, u64* ov, u32* oab, Rows2 o2,
+                     u32* d_part_off, u32* d_flag, u32* nparts_out, u32* qpp_out);
+u32 rows_partitions(const dskgpu_ctx* ctx);
+void rows_partition_range(const dskgpu_ctx* ctx, u32 p, u64* b, u64* e);

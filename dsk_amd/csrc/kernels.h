@@ -20,7 +20,7 @@
 // every (segment, bin, chunk) destination offset: no global atomics, and the
 // output order of each level is deterministic.
 #pragma once
-#include "kmer_device.h"
+#include "layouts.h"
 
 #ifndef SC_NT
 #define SC_NT 1024           // threads of hist/scatter blocks: one block per CU stages a 128 KB tile in LDS
@@ -34,19 +34,6 @@ template <int W> struct Tile {
 };
 #define MAX_BINS 2048
 
-// Workgroup barrier that orders LDS traffic only.  HIP's __syncthreads() also
-// drains every outstanding global load (s_waitcnt vmcnt(0)), which would kill
-// the register prefetch of the next tile / sub-partition; this one waits for
-// LDS (lgkmcnt) and leaves HBM reads in flight across the barrier
-// (cdna_hip_programming.md "Pipelining across barriers").  Global data is never
-// exchanged between threads inside these kernels, so no vmcnt wait is needed.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-struct ChunkDesc {
-    u64 begin, end;          // source range: packed words (reads) or keys
-    u32 flat_base;           // matrix entry of bin 0
-    u32 stride;              // matrix stride between bins (= chunks in the segment)
-};
 
 // ------------------------------------------------------------------ K1
 // One thread encodes 32 bases (two 16-byte loads) into one packed word.
@@ -343,54 +330,7 @@ __global__ __launch_bounds__(SCAN_NT) void k_scan_apply(u32* __restrict__ a, con
 // histogram, stage the tile bin-sorted in LDS, then write runs to HBM so that
 // consecutive lanes hit consecutive addresses.  Per-chunk cursors live in LDS.
 // The next tile's keys are loaded (key array) before the current tile enters
-// its LDS phases, so HBM reads stay in flight across the barriers.
-
-// Exclusive scan of cnt[0..P) fused with the cursor bookkeeping of the tile:
-//   off[b]   = start of bin b inside the staged tile
-//   delta[b] = cur[b] - off[b]   (HBM index of staged element i of bin b is delta[b] + i)
-//   cur[b]  += cnt[b];  cnt[b] = 0
-// sg.lim (block-owned slices): bin b may only be written below lim[b], the end of the block's slice of that bin; a bin whose keys
-// of this tile would not fit is redirected, for this tile, to the dump zone [dump, dump + tile) behind the last slice (never read) -- the
-// check costs a few instructions per BIN and tile instead of per key, and nothing is ever written outside the block's own
-// slices or the dump zone.  The cursor of such a bin is parked at end + 1, so the overflow shows at the end of the launch.
-struct SliceGuard { const u32* lim; u32 dump; u32 uslice, first; };      // lim[b] (LDS): end of the block's slice of bin b; or uniform slices of uslice keys from `first` (no array); neither = no guard
-template <int NT>
-__device__ __forceinline__ void tile_scan(u32* cnt, u32* off, u32* delta, u32* cur, int P, u32* wsum, u32* tot, SliceGuard sg = SliceGuard{nullptr, 0u, 0u, 0u}) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int ipt = (P + NT - 1) / NT;
-    const int base = tid * ipt;
-    u32 v[4]; u32 s = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int idx = base + j;
-        v[j] = (j < ipt && idx < P) ? cnt[idx] : 0u;
-        s += v[j];
-    }
-    const u32 inc = wave_incl_scan(s);
-    if (lane == 63) wsum[wave] = inc;
-    lds_barrier();
-    if (wave == 0) {
-        const u32 x = lane < NT / 64 ? wsum[lane] : 0u;
-        const u32 y = wave_incl_scan(x);
-        if (lane < NT / 64) wsum[lane] = y - x;
-        if (lane == NT / 64 - 1) { *tot = y; off[P] = y; }        // off[P]: the dummy bin (invalid windows) is staged behind the keys
-    }
-    lds_barrier();
-    u32 run = wsum[wave] + inc - s;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int idx = base + j;
-        if (j < ipt && idx < P) {
-            const u32 c = cur[idx];
-            // (a cursor that left its slice stays at end + 1: it marks the overflow for the end of the launch and cannot wrap 2^32
-            //  however many keys the bin still receives; below the end, c + v <= 0xFFFF0000 + a tile)
-            const u32 end = sg.lim ? sg.lim[idx] : sg.uslice ? sg.first + (u32)(idx + 1) * sg.uslice : 0xFFFFFFFFu;
-            const bool fits = (sg.lim || sg.uslice) ? c + v[j] <= end : true;
-            off[idx] = run; delta[idx] = fits ? c - run : sg.dump; cur[idx] = fits ? c + v[j] : end + 1u; cnt[idx] = 0;
-            run += v[j];
-        }
-    }
-}
+// its LDS phases, so HBM reads stay in flight across the barriers.  (tile_scan: layouts.h)
 
 struct OptSpec { u32 cap; u32* subcnt; u32* ovf; const u32* fill; u32 slice, nsl; u64 sstride;     // fill/slice/nsl/sstride: SLICED input (below)
                  u32 F, max_ext; u32* next; u32* ext_cursor; u32* chain_list; u32* chain_cnt;     // region chains (below)
@@ -2224,8 +2164,6 @@ __global__ __launch_bounds__(CNT_NT) void k_count_chained_mw(const KN<W>* __rest
 // One wave per sub-partition: copy its solid rows to the dense output and
 // restore the k-mer from the mixed key.  soff = exclusive scan of the per-
 // sub-partition solid counts (F+1 entries).
-struct RowsOut { u64* w[4]; };                    // struct-of-arrays rows: word i of row r at w[i][r]
-struct RowsIn { const u64* w[4]; };
 
 template <int W>
 __global__ __launch_bounds__(256) void k_compact(const typename KeyT<W>::T* __restrict__ keys, const u32* __restrict__ abund,
@@ -2257,74 +2195,6 @@ __global__ __launch_bounds__(256) void k_compact<1>(const u64* __restrict__ keys
         out.w[0][o + i] = kunmix(keys[b + i]);
         out_ab[o + i] = abund[b + i];
     }
-}
-
-// helpers of the two-word row sort (two stable 64-bit radix passes over an index permutation)
-__global__ void k_iota(u32* __restrict__ idx, u64 n) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) idx[i] = (u32)i;
-}
-template <class T>
-__global__ void k_gather(T* __restrict__ dst, const T* __restrict__ src, const u32* __restrict__ idx, u64 n) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = src[idx[i]];
-}
-
-// Gathering the rows of a multi-word sort by index costs W + 1 random reads per row from the per-word arrays -- more than
-// the sort itself.  k_top_key_aos therefore also packs every row into ONE record (W value words + the abundance, padded to a
-// multiple of 16 bytes: 32 bytes for two words, 48 for four) while it reads the words anyway, and k_gather_aos fetches a row
-// with one random access of that record.
-template <int W> struct AosRow { static constexpr int WORDS = (W + 1 + 1) & ~1; };      // u64 words per record
-template <int W>
-__global__ __launch_bounds__(256) void k_top_key_aos(RowsIn rows, const u32* __restrict__ ab, u64 n, int bits, u64* __restrict__ key,
-                                                     u32* __restrict__ idx, u64* __restrict__ aos) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int sh = bits - 63, ws = sh >> 6, b = sh & 63;     // bits > 64 for multi-word values
-    u64 w[W], lo = 0, hi = 0;
-#pragma unroll
-    for (int x = 0; x < W; ++x) { w[x] = rows.w[x][i]; if (x == ws) lo = w[x]; if (x == ws + 1) hi = w[x]; }
-    key[i] = b ? (lo >> b) | (hi << (64 - b)) : lo;
-    idx[i] = (u32)i;
-    ulonglong2* rec = reinterpret_cast<ulonglong2*>(aos + i * AosRow<W>::WORDS);
-#pragma unroll
-    for (int x = 0; x < AosRow<W>::WORDS; x += 2)
-        rec[x / 2] = make_ulonglong2(x < W ? w[x] : (x == W ? (u64)ab[i] : 0ull), x + 1 < W ? w[x + 1] : (x + 1 == W ? (u64)ab[i] : 0ull));
-}
-template <int W>
-__global__ __launch_bounds__(256) void k_gather_aos(RowsOut dst, u32* __restrict__ dab, const u64* __restrict__ aos, const u32* __restrict__ idx, u64 n) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const ulonglong2* rec = reinterpret_cast<const ulonglong2*>(aos + (u64)idx[i] * AosRow<W>::WORDS);
-    u64 w[AosRow<W>::WORDS];
-#pragma unroll
-    for (int x = 0; x < AosRow<W>::WORDS; x += 2) { const ulonglong2 v = rec[x / 2]; w[x] = v.x; w[x + 1] = v.y; }
-#pragma unroll
-    for (int x = 0; x < W; ++x) dst.w[x][i] = w[x];
-    dab[i] = (u32)w[W];
-}
-
-// whole rows in one pass: every thread takes four rows, reads their indices once and has all its W + 1 loads per row in flight
-template <int W>
-__global__ __launch_bounds__(256) void k_gather_rows(RowsOut dst, u32* __restrict__ dab, RowsIn src, const u32* __restrict__ sab,
-                                                     const u32* __restrict__ idx, u64 n) {
-    const u64 b0 = (u64)blockIdx.x * 1024 + threadIdx.x;          // rows b0, b0 + 256, ..: consecutive lanes, consecutive rows
-    u32 id[4]; u64 v[4][W]; u32 a[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) id[r] = b0 + r * 256 < n ? idx[b0 + r * 256] : 0u;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-#pragma unroll
-        for (int x = 0; x < W; ++x) v[r][x] = src.w[x][id[r]];
-        a[r] = sab[id[r]];
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-        if (b0 + r * 256 < n) {
-#pragma unroll
-            for (int x = 0; x < W; ++x) dst.w[x][b0 + r * 256] = v[r][x];
-            dab[b0 + r * 256] = a[r];
-        }
 }
 
 // ------------------------------------------------------------------ test kernels
@@ -2397,122 +2267,6 @@ __global__ __launch_bounds__(256) void k_minimizers(const u64* __restrict__ pack
         if (v) for (int e = halo + j - (k - m); e <= halo + j; ++e) best = cm[e] < best ? cm[e] : best;
         minim[p] = v ? best : 0u;
         valid[p] = v ? 1 : 0;
-    }
-}
-
-#define FIX_CAP 32
-// Multi-word rows: the same two-step order.  k_top_key builds the top 63 bits of every value (bit 63 stays clear:
-// rocPRIM's partial-range sort misbehaves when end_bit == 64) next to the identity permutation; after a radix sort
-// of (key, index) on the key's top 32 bits and a gather of the rows, k_fix_runs_multi orders the runs of equal
-// prefix by full multi-word comparison.
-template <int W>
-__global__ __launch_bounds__(256) void k_top_key(RowsIn rows, u64 n, int bits, u64* __restrict__ key, u32* __restrict__ idx) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int sh = bits - 63, ws = sh >> 6, b = sh & 63;     // bits > 64 for multi-word values
-    u64 lo = 0, hi = 0;
-#pragma unroll
-    for (int x = 0; x < W; ++x) { if (x == ws) lo = rows.w[x][i]; if (x == ws + 1) hi = rows.w[x][i]; }
-    key[i] = b ? (lo >> b) | (hi << (64 - b)) : lo;
-    idx[i] = (u32)i;
-}
-template <int W>
-__device__ __forceinline__ bool row_less(const u64 (&a)[W], const RowsOut& r, u64 j) {     // a < row j ?
-#pragma unroll
-    for (int x = W - 1; x >= 0; --x) { const u64 v = r.w[x][j]; if (a[x] != v) return a[x] < v; }
-    return false;
-}
-// Runs of 33 .. FIX_BLOCK_ROWS rows (16384: the one- and two-error variants of a 63-mer are 4300; the error variants of a k-mer with 10^5 and more occurrences share their first 63 bits) are
-// LISTED -- list[0] = how many, then (first row, rows) pairs -- and ordered by k_fix_long_runs, one block per run; beyond that, or
-// when the list is full, *flag (the full-width fallback).
-#define FIX_LIST_CAP 4096
-#define FIX_BLOCK_ROWS 16384
-template <int W>
-__global__ __launch_bounds__(256) void k_fix_runs_multi(RowsOut rows, u32* __restrict__ ab, const u64* __restrict__ key, u64 n, int sh, u32* __restrict__ flag,
-                                                        const u32* __restrict__ ties, u32* __restrict__ list) {
-    if (ties && *ties == 0u) return;                         // the sort saw no two equal keys: nothing to order
-    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {      // (grid-stride: the launch may be capped)
-        const u64 p = key[i] >> sh;
-        if (i > 0 && (key[i - 1] >> sh) == p) continue;         // not a run head
-        u64 e = i + 1;
-        while (e < n && e - i <= FIX_BLOCK_ROWS && (key[e] >> sh) == p) ++e;
-        const u64 L = e - i;
-        if (L == 1) continue;
-        if (L > FIX_CAP) {
-            if (L > FIX_BLOCK_ROWS || i + L >= 0xFFFFFFFFull || list == nullptr) { *flag = 1; continue; }
-            const u32 at = atomicAdd(&list[0], 1u);
-            if (at < FIX_LIST_CAP) { list[1 + 2 * at] = (u32)i; list[2 + 2 * at] = (u32)L; } else *flag = 1;
-            continue;
-        }
-        for (u64 a = i + 1; a < e; ++a) {
-            u64 kv[W]; const u32 av = ab[a];
-#pragma unroll
-            for (int x = 0; x < W; ++x) kv[x] = rows.w[x][a];
-            u64 b = a;
-            while (b > i && row_less<W>(kv, rows, b - 1)) {
-#pragma unroll
-                for (int x = 0; x < W; ++x) rows.w[x][b] = rows.w[x][b - 1];
-                ab[b] = ab[b - 1]; --b;
-            }
-#pragma unroll
-            for (int x = 0; x < W; ++x) rows.w[x][b] = kv[x];
-            ab[b] = av;
-        }
-    }
-}
-// one block per listed run: a bitonic network over the run's row numbers in LDS (rows compared word by word in HBM / L2 -- the run
-// is a few hundred KB), then every thread fetches the rows of its final positions, and after a barrier writes them there
-template <int W>
-__global__ __launch_bounds__(1024) void k_fix_long_runs(RowsOut rows, u32* __restrict__ ab, const u32* __restrict__ list, const u32* __restrict__ ties) {
-    if (ties && *ties == 0u) return;
-    __shared__ unsigned short idx[FIX_BLOCK_ROWS];
-    const u32 nl = list[0] < FIX_LIST_CAP ? list[0] : FIX_LIST_CAP;
-    for (u32 r = blockIdx.x; r < nl; r += gridDim.x) {
-        const u64 base = list[1 + 2 * r]; const u32 L = list[2 + 2 * r];
-        u32 np2 = 2; while (np2 < L) np2 <<= 1;
-        __syncthreads();
-        for (u32 j = threadIdx.x; j < np2; j += 1024) idx[j] = (unsigned short)(j < L ? j : 0xFFFFu);      // (pads order behind every row)
-        __syncthreads();
-        auto less = [&](u32 a, u32 b) {          // row a < row b (row numbers inside the run; a pad is larger than any row)
-            if (a == 0xFFFFu || b == 0xFFFFu) return a != 0xFFFFu && b == 0xFFFFu;
-#pragma unroll
-            for (int x = W - 1; x >= 0; --x) { const u64 va = rows.w[x][base + a], vb = rows.w[x][base + b]; if (va != vb) return va < vb; }
-            return false;
-        };
-        for (u32 kk = 2; kk <= np2; kk <<= 1)
-            for (u32 jj = kk >> 1; jj > 0; jj >>= 1) {
-                for (u32 x = threadIdx.x; x < np2; x += 1024) {
-                    const u32 y = x ^ jj;
-                    if (y > x) {
-                        const u32 a0 = idx[x], a1 = idx[y];
-                        const bool up = (x & kk) == 0;
-                        if (less(a1, a0) == up) { idx[x] = (unsigned short)a1; idx[y] = (unsigned short)a0; }
-                    }
-                }
-                __syncthreads();
-            }
-        constexpr int RPT = FIX_BLOCK_ROWS / 1024;
-        u64 kv[RPT][W]; u32 av[RPT];
-#pragma unroll
-        for (int t = 0; t < RPT; ++t) {
-            const u32 j = threadIdx.x + 1024 * t;
-            if (j < L) {
-                const u32 src = idx[j];
-#pragma unroll
-                for (int x = 0; x < W; ++x) kv[t][x] = rows.w[x][base + src];
-                av[t] = ab[base + src];
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < RPT; ++t) {
-            const u32 j = threadIdx.x + 1024 * t;
-            if (j < L) {
-#pragma unroll
-                for (int x = 0; x < W; ++x) rows.w[x][base + j] = kv[t][x];
-                ab[base + j] = av[t];
-            }
-        }
     }
 }
 

@@ -19,7 +19,7 @@
 // size are ordered here: above 64 rows by a block (k_rs_big), there above 16 with a bitonic network over the sub-bucket (the error
 // variants of a poly-A k-mer share 13 and more leading bases).
 #pragma once
-#include "kernels.h"
+#include "layouts.h"
 
 #define RS_NT 1024                        // step A: one 1024-thread block per chunk, 8192-row tiles
 #define RS_RPT 8
@@ -86,7 +86,6 @@ __global__ __launch_bounds__(RS_NT) void k_rs_hist(const u64* __restrict__ v, u6
 // fstart[q] with exact offsets), keys still MIXED, abundances at the same index of `ab`.  Until round 5 k_compact gathered them into a
 // dense array first (0.5 GB read + 0.5 GB written, 0.30 ms) that step A then read again; here step A reads the regions itself:
 // chunk c = the sub-partitions [c * qpc, (c + 1) * qpc), i.e. the logical rows [soff[c * qpc], soff[(c + 1) * qpc)).
-struct RsSparse { const u64* keys; const u32* ab; const u32* soff; const u32* fstart; u32 cap, F, qpc; };
 __device__ __forceinline__ u64 rs_sp_base(const RsSparse& s, u32 q) { return s.cap ? (u64)q * s.cap : (u64)s.fstart[q]; }
 
 // histogram of the first digit, one wave per sub-partition in turn -> matrix[bin * nch + chunk]
@@ -476,6 +475,186 @@ __global__ __launch_bounds__(256) void k_ovs_scatter(u64* __restrict__ k, u32* _
         for (u32 i = threadIdx.x; i < len; i += 256) {
             k[(u64)off + i] = pre | ((gk[(u64)st + i] & ((1ull << maxbits) - 1ull)) >> (maxbits - bits));
             v[(u64)off + i] = gv[(u64)st + i];
+        }
+    }
+}
+
+// ------------------------------------------------------------------ multi-word rows
+// helpers of the two-word row sort (two stable 64-bit radix passes over an index permutation)
+__global__ void k_iota(u32* __restrict__ idx, u64 n) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) idx[i] = (u32)i;
+}
+
+// Gathering the rows of a multi-word sort by index costs W + 1 random reads per row from the per-word arrays -- more than
+// the sort itself.  k_top_key_aos therefore also packs every row into ONE record (W value words + the abundance, padded to a
+// multiple of 16 bytes: 32 bytes for two words, 48 for four) while it reads the words anyway, and k_gather_aos fetches a row
+// with one random access of that record.
+template <int W> struct AosRow { static constexpr int WORDS = (W + 1 + 1) & ~1; };      // u64 words per record
+template <int W>
+__global__ __launch_bounds__(256) void k_top_key_aos(RowsIn rows, const u32* __restrict__ ab, u64 n, int bits, u64* __restrict__ key,
+                                                     u32* __restrict__ idx, u64* __restrict__ aos) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int sh = bits - 63, ws = sh >> 6, b = sh & 63;     // bits > 64 for multi-word values
+    u64 w[W], lo = 0, hi = 0;
+#pragma unroll
+    for (int x = 0; x < W; ++x) { w[x] = rows.w[x][i]; if (x == ws) lo = w[x]; if (x == ws + 1) hi = w[x]; }
+    key[i] = b ? (lo >> b) | (hi << (64 - b)) : lo;
+    idx[i] = (u32)i;
+    ulonglong2* rec = reinterpret_cast<ulonglong2*>(aos + i * AosRow<W>::WORDS);
+#pragma unroll
+    for (int x = 0; x < AosRow<W>::WORDS; x += 2)
+        rec[x / 2] = make_ulonglong2(x < W ? w[x] : (x == W ? (u64)ab[i] : 0ull), x + 1 < W ? w[x + 1] : (x + 1 == W ? (u64)ab[i] : 0ull));
+}
+template <int W>
+__global__ __launch_bounds__(256) void k_gather_aos(RowsOut dst, u32* __restrict__ dab, const u64* __restrict__ aos, const u32* __restrict__ idx, u64 n) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const ulonglong2* rec = reinterpret_cast<const ulonglong2*>(aos + (u64)idx[i] * AosRow<W>::WORDS);
+    u64 w[AosRow<W>::WORDS];
+#pragma unroll
+    for (int x = 0; x < AosRow<W>::WORDS; x += 2) { const ulonglong2 v = rec[x / 2]; w[x] = v.x; w[x + 1] = v.y; }
+#pragma unroll
+    for (int x = 0; x < W; ++x) dst.w[x][i] = w[x];
+    dab[i] = (u32)w[W];
+}
+
+// whole rows in one pass: every thread takes four rows, reads their indices once and has all its W + 1 loads per row in flight
+template <int W>
+__global__ __launch_bounds__(256) void k_gather_rows(RowsOut dst, u32* __restrict__ dab, RowsIn src, const u32* __restrict__ sab,
+                                                     const u32* __restrict__ idx, u64 n) {
+    const u64 b0 = (u64)blockIdx.x * 1024 + threadIdx.x;          // rows b0, b0 + 256, ..: consecutive lanes, consecutive rows
+    u32 id[4]; u64 v[4][W]; u32 a[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) id[r] = b0 + r * 256 < n ? idx[b0 + r * 256] : 0u;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+#pragma unroll
+        for (int x = 0; x < W; ++x) v[r][x] = src.w[x][id[r]];
+        a[r] = sab[id[r]];
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        if (b0 + r * 256 < n) {
+#pragma unroll
+            for (int x = 0; x < W; ++x) dst.w[x][b0 + r * 256] = v[r][x];
+            dab[b0 + r * 256] = a[r];
+        }
+}
+
+#define FIX_CAP 32
+// Multi-word rows: the same two-step order.  k_top_key builds the top 63 bits of every value (bit 63 stays clear:
+// rocPRIM's partial-range sort misbehaves when end_bit == 64) next to the identity permutation; after a radix sort
+// of (key, index) on the key's top 32 bits and a gather of the rows, k_fix_runs_multi orders the runs of equal
+// prefix by full multi-word comparison.
+template <int W>
+__global__ __launch_bounds__(256) void k_top_key(RowsIn rows, u64 n, int bits, u64* __restrict__ key, u32* __restrict__ idx) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int sh = bits - 63, ws = sh >> 6, b = sh & 63;     // bits > 64 for multi-word values
+    u64 lo = 0, hi = 0;
+#pragma unroll
+    for (int x = 0; x < W; ++x) { if (x == ws) lo = rows.w[x][i]; if (x == ws + 1) hi = rows.w[x][i]; }
+    key[i] = b ? (lo >> b) | (hi << (64 - b)) : lo;
+    idx[i] = (u32)i;
+}
+template <int W>
+__device__ __forceinline__ bool row_less(const u64 (&a)[W], const RowsOut& r, u64 j) {     // a < row j ?
+#pragma unroll
+    for (int x = W - 1; x >= 0; --x) { const u64 v = r.w[x][j]; if (a[x] != v) return a[x] < v; }
+    return false;
+}
+// Runs of 33 .. FIX_BLOCK_ROWS rows (16384: the one- and two-error variants of a 63-mer are 4300; the error variants of a k-mer with 10^5 and more occurrences share their first 63 bits) are
+// LISTED -- list[0] = how many, then (first row, rows) pairs -- and ordered by k_fix_long_runs, one block per run; beyond that, or
+// when the list is full, *flag (the full-width fallback).
+#define FIX_LIST_CAP 4096
+#define FIX_BLOCK_ROWS 16384
+template <int W>
+__global__ __launch_bounds__(256) void k_fix_runs_multi(RowsOut rows, u32* __restrict__ ab, const u64* __restrict__ key, u64 n, int sh, u32* __restrict__ flag,
+                                                        const u32* __restrict__ ties, u32* __restrict__ list) {
+    if (ties && *ties == 0u) return;                         // the sort saw no two equal keys: nothing to order
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {      // (grid-stride: the launch may be capped)
+        const u64 p = key[i] >> sh;
+        if (i > 0 && (key[i - 1] >> sh) == p) continue;         // not a run head
+        u64 e = i + 1;
+        while (e < n && e - i <= FIX_BLOCK_ROWS && (key[e] >> sh) == p) ++e;
+        const u64 L = e - i;
+        if (L == 1) continue;
+        if (L > FIX_CAP) {
+            if (L > FIX_BLOCK_ROWS || i + L >= 0xFFFFFFFFull || list == nullptr) { *flag = 1; continue; }
+            const u32 at = atomicAdd(&list[0], 1u);
+            if (at < FIX_LIST_CAP) { list[1 + 2 * at] = (u32)i; list[2 + 2 * at] = (u32)L; } else *flag = 1;
+            continue;
+        }
+        for (u64 a = i + 1; a < e; ++a) {
+            u64 kv[W]; const u32 av = ab[a];
+#pragma unroll
+            for (int x = 0; x < W; ++x) kv[x] = rows.w[x][a];
+            u64 b = a;
+            while (b > i && row_less<W>(kv, rows, b - 1)) {
+#pragma unroll
+                for (int x = 0; x < W; ++x) rows.w[x][b] = rows.w[x][b - 1];
+                ab[b] = ab[b - 1]; --b;
+            }
+#pragma unroll
+            for (int x = 0; x < W; ++x) rows.w[x][b] = kv[x];
+            ab[b] = av;
+        }
+    }
+}
+// one block per listed run: a bitonic network over the run's row numbers in LDS (rows compared word by word in HBM / L2 -- the run
+// is a few hundred KB), then every thread fetches the rows of its final positions, and after a barrier writes them there
+template <int W>
+__global__ __launch_bounds__(1024) void k_fix_long_runs(RowsOut rows, u32* __restrict__ ab, const u32* __restrict__ list, const u32* __restrict__ ties) {
+    if (ties && *ties == 0u) return;
+    __shared__ unsigned short idx[FIX_BLOCK_ROWS];
+    const u32 nl = list[0] < FIX_LIST_CAP ? list[0] : FIX_LIST_CAP;
+    for (u32 r = blockIdx.x; r < nl; r += gridDim.x) {
+        const u64 base = list[1 + 2 * r]; const u32 L = list[2 + 2 * r];
+        u32 np2 = 2; while (np2 < L) np2 <<= 1;
+        __syncthreads();
+        for (u32 j = threadIdx.x; j < np2; j += 1024) idx[j] = (unsigned short)(j < L ? j : 0xFFFFu);      // (pads order behind every row)
+        __syncthreads();
+        auto less = [&](u32 a, u32 b) {          // row a < row b (row numbers inside the run; a pad is larger than any row)
+            if (a == 0xFFFFu || b == 0xFFFFu) return a != 0xFFFFu && b == 0xFFFFu;
+#pragma unroll
+            for (int x = W - 1; x >= 0; --x) { const u64 va = rows.w[x][base + a], vb = rows.w[x][base + b]; if (va != vb) return va < vb; }
+            return false;
+        };
+        for (u32 kk = 2; kk <= np2; kk <<= 1)
+            for (u32 jj = kk >> 1; jj > 0; jj >>= 1) {
+                for (u32 x = threadIdx.x; x < np2; x += 1024) {
+                    const u32 y = x ^ jj;
+                    if (y > x) {
+                        const u32 a0 = idx[x], a1 = idx[y];
+                        const bool up = (x & kk) == 0;
+                        if (less(a1, a0) == up) { idx[x] = (unsigned short)a1; idx[y] = (unsigned short)a0; }
+                    }
+                }
+                __syncthreads();
+            }
+        constexpr int RPT = FIX_BLOCK_ROWS / 1024;
+        u64 kv[RPT][W]; u32 av[RPT];
+#pragma unroll
+        for (int t = 0; t < RPT; ++t) {
+            const u32 j = threadIdx.x + 1024 * t;
+            if (j < L) {
+                const u32 src = idx[j];
+#pragma unroll
+                for (int x = 0; x < W; ++x) kv[t][x] = rows.w[x][base + src];
+                av[t] = ab[base + src];
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < RPT; ++t) {
+            const u32 j = threadIdx.x + 1024 * t;
+            if (j < L) {
+#pragma unroll
+                for (int x = 0; x < W; ++x) rows.w[x][base + j] = kv[t][x];
+                ab[base + j] = av[t];
+            }
         }
     }
 }

@@ -50,8 +50,6 @@ struct Rs2Lds {
     }
 };
 
-struct Rows2 { u64* hi; u64* lo; u32* ab; };
-struct Rows2C { const u64* hi; const u64* lo; const u32* ab; };
 
 // per-chunk histogram of the first digit -> matrix[bin * nch + chunk]
 // (c0: first matrix column of this launch, as in k_rs_hist)
@@ -77,7 +75,6 @@ __global__ __launch_bounds__(RS_NT) void k2_hist(Rows2C v, u64 n, u32 chunk, u32
 // ---- step A straight from the count kernel's output (two-word rows of a single pass; rowsort.h has the one-word twin): the solid rows
 // of sub-partition q lie where k_count2v3 / k_count_mw left them -- ns_q = soff[q + 1] - soff[q] two-word keys (still MIXED) from key
 // index base(q) on, abundances at the same index of `ab`.  k_compact<2> gathered them into three dense arrays first (0.26 ms at k = 63).
-struct Rs2Sparse { const K2* keys; const u32* ab; const u32* soff; const u32* fstart; u32 cap, F, qpc; };
 __device__ __forceinline__ u64 rs2_sp_base(const Rs2Sparse& s, u32 q) { return s.cap ? (u64)q * s.cap : (u64)s.fstart[q]; }
 __global__ __launch_bounds__(RS_NT) void k2_hist_sp(Rs2Sparse s, u32 nch, u32* __restrict__ matrix, RsSpec sp) {
     __shared__ u32 lh[RS2_ABINS];

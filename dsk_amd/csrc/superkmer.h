@@ -29,40 +29,15 @@
 // holds up to min(32, (64 R - 8) / 2 - k + 1) k-mers -- 30 at k = 31 and k = 63 -- instead of 16: 8.5 k-mers per record on average
 // instead of 6.9, a fifth fewer bytes to write, to send over xGMI and to read back in level 1.
 #pragma once
-#include "kmer_device.h"
+#include "layouts.h"
 
 #define SK_NT 512
 #define SK_HALO 4                         // leading groups of a tile that only contribute m-mer hashes (64 positions >= k - m)
 #define SK_GROUPS (SK_NT - SK_HALO)       // groups (16 window ends each) a tile emits records for
-#define SK_MAX_OWNERS 64
-#define SK_BUCKETS 4096                   // minimizer buckets of the repartition table
 #define SK_DESC 256                       // records a wave deals out per round (k_sk_scatter)
 #define SK_SPLIT 255u                     // table entry: route the window by its k-mer, not by its minimizer
 #define SK_MAXN 32                        // most k-mers of a record (slots per record of the receivers' maps)
 
-struct SkParams {
-    u64 ngroups;          // 2 * packed words
-    u64 ntiles;
-    u32 tiles_per_chunk, nchunks;
-    u32 k, m, G, R;
-    u32 sample_step;      // k_sk_hist: look at every sample_step-th tile only (1 = exact count)
-    u32 slice;            // k_sk_scatter<true>: records per (owner, chunk) slice
-    // k_sk_scatter<true> writes the chunks [c0, c0 + gridDim) of a layout GROUP of clen chunks that starts at chunk c0g and at record
-    // rbase of the send buffer: owner o of the group starts at rbase + o * clen * slice, its chunk c at + (c - c0g) * slice (all 64-bit).
-    // One group = all chunks (c0 = c0g = 0, clen = nchunks, rbase = 0): the layout of a whole step; S groups: a step sent in S
-    // slices, each complete -- and on its way -- before the next is written (dskgpu_mg_scatter_slice).
-    u32 c0, c0g, clen;
-    u64 rbase;                    // (64-bit: a rank's shard of a 90 Gbp job holds more than 2^32 records' worth of slices)
-    const unsigned char* table;   // SK_BUCKETS owners (device memory)
-    u32 has_split;                // the table holds SK_SPLIT entries (set with the table: the kernels skip the split bookkeeping otherwise)
-    // k_sk_scatter<true> for the passes of a multi-pass count on ONE GPU ("virtual owners": owner = pass; dskgpu.hip: rec_l0_*): only
-    // the records of owners [olo, ohi) are written (a sweep materialises as many passes as HBM holds), every owner has its own slice
-    // length oslice[o] (a pass that holds a k-mer with 10^8 occurrences gets longer slices, the others do not pay for it) and its
-    // region starts at record obase[o] of the buffer (64-bit: a sweep holds more than 2^32 records).  oslice == nullptr: the
-    // uniform layout above, all owners.
-    u32 olo, ohi;
-    const u32* oslice; const unsigned long long* obase;
-};
 
 __host__ __device__ __forceinline__ u32 sk_record_words(u32 k) { return (2u * (k + 15u) + 8u + 63u) / 64u; }
 // most k-mers a record of R words holds at this k: n + k - 1 bases + the 8 header bits in 64 R bits, and never more than one word's 32 windows
