@@ -214,39 +214,18 @@ unsigned scatter_grid(const dskgpu_ctx* ctx, int W, u32 P, u64 max_chunks, bool 
     const u64 per_cu = std::max<u64>(1, std::min<u64>(2048 / SC_NT, (160 * 1024) / lds));   // resident blocks per CU
     return (unsigned)std::max<u64>(1, std::min<u64>(max_chunks, (u64)ctx->num_cu * per_cu));
 }
+// SRC 0: the encoded reads; 1: a key array; 2: super-k-mer records (ctx->rec_src: the histogram-free level 1 of one- and two-word keys)
 template <int W, int SRC, int MODE, bool OPT = false, bool HEAVY = false>
 int launch_scatter_m(dskgpu_ctx* ctx, const typename KeyT<W>::T* keys, const ChunkDesc* descs, const u32* d_nch,
                      u64 max_chunks, const u32* scanned, typename KeyT<W>::T* out, DigitSpec ds, u32 P, Opt1Spec o1 = Opt1Spec{nullptr, 0u, 0u, nullptr, nullptr, 0u, nullptr, nullptr, nullptr, 0u, nullptr, 0ull, {0ull, 0ull, 0ull, 0ull}, 0u}) {
     const size_t lds = scatter_lds(W, P, OPT && !o1.uslice);
     const unsigned grid = scatter_grid(ctx, W, P, max_chunks, OPT && !o1.uslice);
     { const int e = allow_big_lds(ctx, reinterpret_cast<const void*>(&k_scatter<W, SRC, MODE, OPT, HEAVY>)); if (e) return e; }
-    hipLaunchKernelGGL((k_scatter<W, SRC, MODE, OPT, HEAVY>), dim3(grid), dim3(SC_NT), lds, ctx->stream, ctx->packed.as<u64>(),
-                       ctx->inval.as<u32>(), keys, descs, d_nch, scanned, out, (int)ctx->cfg.kmer_size, ds, P, o1);
+    hipLaunchKernelGGL((k_scatter<W, SRC, MODE, OPT, HEAVY>), dim3(grid), dim3(SC_NT), lds, ctx->stream, SRC == 2 ? ctx->rec_src : ctx->packed.as<u64>(),
+                       SRC == 2 ? nullptr : ctx->inval.as<u32>(), keys, descs, d_nch, scanned, out, (int)ctx->cfg.kmer_size, ds, P, o1);
     CKL("k_scatter");
     return DSKGPU_OK;
 }
-// super-k-mer records as the source of the histogram-free level-1 scatter (one- and two-word keys); HEAVY: with k-mers counted apart
-// (one-word keys); MODE 3: one of several passes over the records of a multi-GPU receive side (the pass filter on every key)
-template <int W, bool HEAVY = false, int MODE = 1>
-int launch_scatter_rec(dskgpu_ctx* ctx, const ChunkDesc* descs, const u32* d_nch, u64 max_chunks, typename KeyT<W>::T* out, DigitSpec ds, u32 P, Opt1Spec o1) {
-    const size_t lds = scatter_lds(W, P, !o1.uslice);
-    const unsigned grid = scatter_grid(ctx, W, P, max_chunks, !o1.uslice);
-    { const int e = allow_big_lds(ctx, reinterpret_cast<const void*>(&k_scatter<W, 2, MODE, true, HEAVY>)); if (e) return e; }
-    hipLaunchKernelGGL((k_scatter<W, 2, MODE, true, HEAVY>), dim3(grid), dim3(SC_NT), lds, ctx->stream, ctx->rec_src, (const u32*)nullptr,
-                       (const typename KeyT<W>::T*)nullptr, descs, d_nch, (const u32*)nullptr, out, (int)ctx->cfg.kmer_size, ds, P, o1);
-    CKL("k_scatter(records)");
-    return DSKGPU_OK;
-}
-template <int W>
-int launch_scatter_rec_h(dskgpu_ctx* ctx, bool heavy, const ChunkDesc* descs, const u32* d_nch, u64 max_chunks, typename KeyT<W>::T* out, DigitSpec ds, u32 P, Opt1Spec o1) {
-    const bool mp = ds.npass > 1;
-    if constexpr (W <= 2) {
-        if (heavy) return mp ? launch_scatter_rec<W, true, 3>(ctx, descs, d_nch, max_chunks, out, ds, P, o1) : launch_scatter_rec<W, true, 1>(ctx, descs, d_nch, max_chunks, out, ds, P, o1);
-    }
-    if constexpr (W <= 2) return mp ? launch_scatter_rec<W, false, 3>(ctx, descs, d_nch, max_chunks, out, ds, P, o1) : launch_scatter_rec<W, false, 1>(ctx, descs, d_nch, max_chunks, out, ds, P, o1);
-    else return DSKGPU_E_STATE;                     // (records carry k <= 64)
-}
-
 // key-array source with aligned write-out (k_scatter_al) when its LDS footprint fits one CU
 template <int W, int MODE, bool OPT = false, bool SLICED = false>
 int launch_scatter_al(dskgpu_ctx* ctx, const typename KeyT<W>::T* keys, const ChunkDesc* descs, const u32* d_nch,
@@ -479,33 +458,25 @@ template <> int expand_records<4>(dskgpu_ctx*, u64) { return DSKGPU_E_STATE; }  
 // Heavy k-mers of a pass (one-word keys): level-1 bins whose sampled load stands 20 % above the median hold a k-mer that alone is a
 // large share of a bin.  k_collect_heavy gathers about HV_COLLECT sampled keys of up to HV_SLOTS such bins; a k-mer that makes up
 // >= 5 % of a bin's collected keys is heavy: the HV_KEYS heaviest go to hv_buf = [keys | counts | rows], and the level-1
-// scatter counts them apart.  ctx->h_load is reduced by what they take away (slice sizes, order of the level-2 segments).
+// scatter counts them apart.  `load` is reduced by what they take away (slice sizes, order of the level-2 segments).
 // hv_buf (u64 words): [keys: HV_KEYS x W][counts: HV_KEYS][rows, word x of row r at (W + 1 + x) * HV_KEYS + r][abundances: HV_KEYS x u32]
 template <int W> struct HvLayout { static constexpr size_t keys = 0, counts = (size_t)HV_KEYS * W, rows = (size_t)HV_KEYS * (W + 1), ab = (size_t)HV_KEYS * (2 * W + 1), words = (size_t)HV_KEYS * (2 * W + 2); };
 template <int W>
-int find_heavy(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_keys_in, u32 nts, const Plan& pl, u32* nheavy_out) {
+int find_heavy(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_keys_in, u32 nts, const Plan& pl, std::vector<double>& load, u32* nheavy_out) {
     typedef typename KeyT<W>::T Key;
     struct HK { u64 w[W]; bool operator<(const HK& o) const { for (int x = W - 1; x >= 0; --x) if (w[x] != o.w[x]) return w[x] < o.w[x]; return false; }
                 bool operator==(const HK& o) const { for (int x = 0; x < W; ++x) if (w[x] != o.w[x]) return false; return true; } };
     static_assert(sizeof(HK) == sizeof(Key), "host mirror of a device key");
     *nheavy_out = 0;
     const u32 P1 = pl.P1;
-    std::vector<double> sorted(ctx->h_load);
+    std::vector<double> sorted(load);
     std::nth_element(sorted.begin(), sorted.begin() + P1 / 2, sorted.end());
     const double median = sorted[P1 / 2];
     std::vector<u32> flagged;
-    for (u32 b = 0; b < P1; ++b) if (ctx->h_load[b] > 1.2 * median + 4096.0) flagged.push_back(b);
+    for (u32 b = 0; b < P1; ++b) if (load[b] > 1.2 * median + 4096.0) flagged.push_back(b);
     if (ctx->tune.verbose) fprintf(stderr, "[dskgpu] find_heavy: median load %.0f, %zu bins above 1.2 x\n", median, flagged.size());
-    u64* hvb = nullptr;
-    auto reset_buf = [&]() -> int {      // keys all-ones (= unused), counts zero
-        CK(ctx->hv_buf.ensure(HvLayout<W>::words * 8));
-        hvb = ctx->hv_buf.as<u64>();
-        CK(hipMemsetAsync(hvb + HvLayout<W>::keys, 0xFF, (size_t)HV_KEYS * W * 8, ctx->stream));
-        CK(hipMemsetAsync(hvb + HvLayout<W>::counts, 0, HV_KEYS * 8, ctx->stream));
-        return DSKGPU_OK;
-    };
     if (flagged.empty()) return DSKGPU_OK;
-    std::sort(flagged.begin(), flagged.end(), [&](u32 a, u32 b) { return ctx->h_load[a] > ctx->h_load[b]; });
+    std::sort(flagged.begin(), flagged.end(), [&](u32 a, u32 b) { return load[a] > load[b]; });
     if (flagged.size() > HV_SLOTS) flagged.resize(HV_SLOTS);
     ctx->h_hv_lut.assign(P1, 0xFF);
     for (size_t f = 0; f < flagged.size(); ++f) ctx->h_hv_lut[flagged[f]] = (unsigned char)f;
@@ -553,607 +524,683 @@ int find_heavy(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_ke
         for (u32 i = 0; i < n;) {
             u32 j = i + 1;
             while (j < n && kk[j] == kk[i]) ++j;
-            if ((u64)(j - i) * 20 >= n) { cands.push_back({ctx->h_load[bin] * (double)(j - i) / (double)n, kk[i], bin}); ++found; }     // >= 5 % of the bin's collected keys
+            if ((u64)(j - i) * 20 >= n) { cands.push_back({load[bin] * (double)(j - i) / (double)n, kk[i], bin}); ++found; }     // >= 5 % of the bin's collected keys
             i = j;
         }
-        if (ctx->tune.verbose) fprintf(stderr, "[dskgpu]   bin %u load %.0f: %u keys collected, %u dominant\n", bin, ctx->h_load[bin], n, found);
+        if (ctx->tune.verbose) fprintf(stderr, "[dskgpu]   bin %u load %.0f: %u keys collected, %u dominant\n", bin, load[bin], n, found);
     }
     std::sort(cands.begin(), cands.end(), [](const Cand& a, const Cand& b) { return a.est > b.est; });
     if (cands.size() > HV_KEYS) cands.resize(HV_KEYS);
     ctx->h_hv_keys.assign((size_t)HV_KEYS * W, DSK_EMPTY);
     for (size_t x = 0; x < cands.size(); ++x) {
         for (int y = 0; y < W; ++y) ctx->h_hv_keys[x * W + y] = cands[x].key.w[y];
-        ctx->h_load[cands[x].bin] -= cands[x].est;            // they never reach the bin: slices and the order of the level-2 segments follow
-        ctx->h_seg_work[cands[x].bin] -= cands[x].est;
+        load[cands[x].bin] -= cands[x].est;            // they never reach the bin: slices and the order of the level-2 segments follow
     }
     u32 nheavy = (u32)cands.size();
-    if (nheavy) {
-        { const int e = reset_buf(); if (e) return e; }
+    if (nheavy) {      // keys all-ones (= unused), counts zero, then the heavy keys
+        CK(ctx->hv_buf.ensure(HvLayout<W>::words * 8));
+        u64* hvb = ctx->hv_buf.as<u64>();
+        CK(hipMemsetAsync(hvb + HvLayout<W>::keys, 0xFF, (size_t)HV_KEYS * W * 8, ctx->stream));
+        CK(hipMemsetAsync(hvb + HvLayout<W>::counts, 0, HV_KEYS * 8, ctx->stream));
         CK(hipMemcpyAsync(hvb + HvLayout<W>::keys, ctx->h_hv_keys.data(), (size_t)HV_KEYS * W * 8, hipMemcpyHostToDevice, ctx->stream));
     }
     *nheavy_out = nheavy;
     return DSKGPU_OK;
 }
 
-// One pass: partition + count the keys of pass `pass` (of `npass`) and leave its solid rows
-// (unsorted) in out_w[0]/out_w[1]/out_ab.  Returns PASS_TOO_BIG when the pass holds more keys than `cap`.
-#define PASS_TOO_BIG 1000
+// ---------------- one pass, stage by stage
+// A pass's key source: the encoded reads, a key array, or (multi-GPU receive side) super-k-mer records that the histogram-free
+// level-1 scatter reads directly; any other path expands them to a key array first, once for all attempts of the pass.
+template <int W> struct KeySource { bool from_reads, from_rec; const typename KeyT<W>::T* keys; u64 nkeys, nwords; };
+
+// What the stages of one attempt of a pass share
+template <int W>
+struct PassState {
+    typedef typename KeyT<W>::T Key;
+    KeySource<W>& src;
+    u32 pass, npass; u64 cap;        // which pass of how many; the keys it may hold
+    u64 nvalid;                      // keys of all passes: the valid k-mer windows of the reads, or the key array's length
+    u32* sc;                         // the device scalars (Scalar)
+    Plan pl{};
+    u32 opt_cap = 0, max_ext = 0; u64 nregions = 0;      // level 2: keys per sub-partition region (0 = exact offsets); extension regions behind them
+    bool opt1 = false; Opt1Spec o1{}; unsigned grid1 = 0;  // level 1 without a histogram pass (block-owned slices)
+    u32 nch1 = 0, nheavy = 0;        // level-1 chunks; k-mers the level-1 scatter counts apart (find_heavy)
+    std::vector<double> load, spread;   // level-1 keys per bin (sampled or mean) and how far a block's share of them may stray
+    Key* fkeys = nullptr;            // the keys after the last scatter, grouped by sub-partition
+    DevBuf* scratch = nullptr;       // the free ping-pong buffer
+    Key* solid_keys = nullptr; u32* solid_ab = nullptr;      // where the count kernels put the solid rows
+    // the count's read-back (k_gather_back): overflow flags, solid rows, keys of the pass (exact paths), slice / region overflows,
+    // extension regions used, gstats (distinct, heavy rows, keys level 1 placed, ..)
+    u32 flags = 0, nsolid = 0, nkeys = 0, ovf2 = 0, ovf1 = 0, ext = 0; u64 stats[4] = {0, 0, 0, 0};
+    bool too_big = false; u64 rows = 0;      // the exact level 1 counted more than `cap` keys (nkeys); rows the pass left
+};
+
+template <int W>
+int upload_descs1(dskgpu_ctx* ctx, PassState<W>& ps) {
+    const KeySource<W>& src = ps.src;
+    const u64 max_chunks1 = (u64)ctx->num_cu * 8;
+    if (src.from_reads) build_descs1(ctx, src.nwords, Tile<W>::WORDS, max_chunks1, &ps.nch1);
+    else if (src.from_rec && ctx->rec_slice_end.size() > 1) build_descs1_slices(ctx, RecTile<W>::NR, max_chunks1, &ps.nch1);
+    else if (src.from_rec) build_descs1(ctx, ctx->rec_n, RecTile<W>::NR, max_chunks1, &ps.nch1);
+    else build_descs1(ctx, src.nkeys, Tile<W>::KEYS, max_chunks1, &ps.nch1);
+    CK(ctx->descs1.ensure(ctx->h_descs1.size() * sizeof(ChunkDesc)));
+    CK(hipMemcpyAsync(ctx->descs1.p, ctx->h_descs1.data(), ctx->h_descs1.size() * sizeof(ChunkDesc), hipMemcpyHostToDevice, ctx->stream));
+    return DSKGPU_OK;
+}
+
+// leave the records path: expand once, then it is a key array
+template <int W>
+int records_to_keys(dskgpu_ctx* ctx, PassState<W>& ps) {
+    const int e = expand_records<W>(ctx, ps.src.nkeys);
+    if (e) return e;
+    ps.src.keys = ctx->sk_keys.template as<typename KeyT<W>::T>(); ps.src.from_rec = false;
+    return upload_descs1(ctx, ps);
+}
+
+// A positional sample: the digit histogram of <= 1024 tiles spread evenly over `units` (hist(descs, d_nch, n, matrix) launches it),
+// reduced to (sum, sum of squares) of every bin over the tiles in ctx->h_mom.  -> tiles of the source, tiles sampled, sampled keys
+template <class Hist>
+int positional_sample(dskgpu_ctx* ctx, u64 units, u64 tile, u32 P, Hist&& hist, u64* ntiles_out, u64* nts_out, u64* stot_out) {
+    u32* sc = ctx->scalars.as<u32>();
+    const u64 ntiles = std::max<u64>(1, (units + tile - 1) / tile);
+    const u64 nts = std::min<u64>(ntiles, 1024);
+    ctx->h_descs_s.resize(nts);
+    for (u64 i = 0; i < nts; ++i) {
+        const u64 t = i * ntiles / nts;
+        ChunkDesc d; d.begin = t * tile; d.end = std::min<u64>(units, (t + 1) * tile); d.flat_base = (u32)i; d.stride = (u32)nts;
+        ctx->h_descs_s[i] = d;
+    }
+    const u64 Ms = (u64)P * nts;
+    CK(ctx->smp_descs.ensure(nts * sizeof(ChunkDesc)));
+    CK(ctx->smp_mat.ensure((Ms + 4) * 4 + (size_t)P * 16));
+    CK(hipMemcpyAsync(ctx->smp_descs.p, ctx->h_descs_s.data(), nts * sizeof(ChunkDesc), hipMemcpyHostToDevice, ctx->stream));
+    ctx->h_sc[SC_NCH_S] = (u32)nts;
+    CK(hipMemcpyAsync(sc + SC_NCH_S, &ctx->h_sc[SC_NCH_S], 4, hipMemcpyHostToDevice, ctx->stream));
+    { const int e = hist(ctx->smp_descs.as<ChunkDesc>(), (const u32*)(sc + SC_NCH_S), nts, ctx->smp_mat.as<u32>()); if (e) return e; }
+    u64* mom = reinterpret_cast<u64*>(ctx->smp_mat.as<u32>() + ((Ms + 2) & ~(u64)1));
+    hipLaunchKernelGGL(k_bin_moments, dim3((P + 3) / 4), dim3(256), 0, ctx->stream, (const u32*)ctx->smp_mat.as<u32>(), (u32)nts, P, mom);
+    CKL("k_bin_moments");
+    ctx->h_mom.resize((size_t)P * 2);
+    void* lz = landing(ctx, (size_t)P * 16);
+    CK(hipMemcpyAsync(lz ? lz : (void*)ctx->h_mom.data(), mom, (size_t)P * 16, hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    if (lz) std::memcpy(ctx->h_mom.data(), lz, (size_t)P * 16);
+    u64 stot = 0;
+    for (u32 b = 0; b < P; ++b) stot += ctx->h_mom[2 * b];
+    *ntiles_out = ntiles; *nts_out = nts; *stot_out = stot;
+    return DSKGPU_OK;
+}
+
+// Stage 1, plan and region sizing.  One-word keys straight from the reads, one pass, two levels: both scatters run without a
+// histogram pass (block-owned slices at level 1, segment-owned regions at level 2); any overflow sends the whole attempt back
+// through the exact histogram + scan path.
+template <int W>
+int pass_plan(dskgpu_ctx* ctx, PassState<W>& ps, int extra_bits) {
+    typedef typename KeyT<W>::T Key;
+    Plan& pl = ps.pl;
+    // keys the plan is sized for: the exact number of valid windows of a single pass from the reads; of several passes its share
+    // + 2 % (cap holds 6 % head-room: sized for it, 7 passes of 200 M reads needed 1792 level-1 bins, more than the LDS of the
+    // histogram-free level 1 holds)
+    const u64 plan_n = (ps.src.from_reads && ctx->have_nvalid) ? std::min<u64>(ps.cap, ps.npass == 1 ? ps.nvalid + 1 : ps.nvalid / ps.npass + ps.nvalid / ps.npass / 50 + 4096) : ps.cap;
+    if (!make_plan(plan_n, extra_bits, W, (u32)ctx->num_cu, &pl))
+        return fail(ctx, DSKGPU_E_OVERFLOW, "cannot partition finer (table overflow persists)");
+    pl.d1.world = pl.d2.world = ctx->cfg.world_size; pl.d1.npass = pl.d2.npass = ps.npass; pl.d1.pass = pl.d2.pass = ps.pass;
+    { const int e = upload_descs1(ctx, ps); if (e) return e; }
+    if (pl.levels == 2 && ctx->sentinel_ok && !ctx->opt2_off && !ctx->tune.no_opt2 && ascatter_lds(W, pl.P2) <= 160 * 1024)
+        ps.opt_cap = opt_groups(W) * (8u / W);                                                 // 545 (two-word keys: 1091) groups of 64 B
+    if (ps.opt_cap && ctx->tune.opt_cap) ps.opt_cap = ctx->tune.opt_cap;                       // experiments / tests
+    if (W > 1 && (u64)pl.F * ps.opt_cap >= 0xFFFF0000ull) ps.opt_cap = 0;                      // k_count<W> keeps 32-bit offsets
+    const u32 opt_cap = ps.opt_cap;
+    // extension regions behind the home regions (region chains, kernels.h): an eighth of the home regions + 4096; their offsets
+    // inside the pool stay below 2^31.  Two-word keys (k_count_mw / k_count_chained_mw index keys with 32 bits): home regions
+    // and pool together below 2^32 keys.  Four-word keys: none (tiles of 4096 keys: the scan over the bins dominates anyway).
+    if (opt_cap && W <= 2) {
+        u64 want = std::min<u64>((u64)pl.F / 8 + 4096, 0x7FFFFFFFull / opt_cap - 1);
+        if (ctx->tune.max_ext >= 0) want = (u64)ctx->tune.max_ext;                                 // tests
+        if (W > 1) { const u64 room = 0xFFFF0000ull / opt_cap; want = room > (u64)pl.F + 1 ? std::min<u64>(want, room - pl.F - 1) : 0; }
+        ps.max_ext = (u32)want;
+    }
+    ps.nregions = (u64)pl.F + ps.max_ext;
+    if (!opt_cap) { CK(ctx->bufA.ensure((ps.cap + 1) * sizeof(Key))); CK(ctx->bufB.ensure((ps.cap + 1) * sizeof(Key))); }      // exact offsets: the keys of the pass, twice
+    if (opt_cap) {
+        // the rows of the solid k-mers land at the region offsets too: abundances (one-word keys: in bufA, the free
+        // ping-pong buffer) or keys + abundances (multi-word keys: bufA + abund2).  Size everything BEFORE level 1 writes bufA.
+        const u64 slots = (u64)pl.F * opt_cap + ATile<W>::KEYS + 16;
+        CK(ctx->bufA.ensure(std::max<u64>(W == 1 ? slots * 4 : slots * sizeof(Key), (ps.cap + 1) * sizeof(Key))));
+        if (W > 1) CK(ctx->abund2.ensure(slots * 4));
+    }
+    ps.opt1 = opt_cap && !ctx->opt1_off && !ctx->tune.no_opt1 && (ps.npass == 1 || ps.src.from_reads || W <= 2);   // several passes over records / a key array (the multi-GPU receive side): one- and two-word keys
+    if (ps.src.from_rec && (!ps.opt1 || W > 2 || ctx->tune.no_recsrc)) { const int e = records_to_keys(ctx, ps); if (e) return e; }
+    if (ps.opt1 && scatter_lds(W, pl.P1, false) > 160 * 1024) ps.opt1 = false;
+    return DSKGPU_OK;
+}
+
+// Stage 2, level-1 sample and slice layout (histogram-free level 1 only)
+template <int W>
+int pass_layout1(dskgpu_ctx* ctx, PassState<W>& ps) {
+    typedef typename KeyT<W>::T Key;
+    const KeySource<W>& src = ps.src;
+    const Plan& pl = ps.pl;
+    Opt1Spec& o1 = ps.o1;
+    o1 = Opt1Spec{nullptr, 0u, 0u, ps.sc + SC_OVF1, nullptr, ctx->sk_sp.R, ctx->gstats.as<u64>() + 2, nullptr, nullptr, 0u, nullptr, 0ull, {0ull, 0ull, 0ull, 0ull}, 0u};
+    // (the per-bin slice ends need 4 more bytes of LDS per bin: plans above 1634 level-1 bins keep UNIFORM slices, mean-sized, no sample)
+    const bool uniform1 = scatter_lds(W, pl.P1, true) > 160 * 1024;
+    if (ps.opt1) {
+        const u32 nch1 = ps.nch1;
+        const unsigned grid1 = ps.grid1 = scatter_grid(ctx, W, pl.P1, nch1, !uniform1);
+        // a block's share of the input: it walks chunks blockIdx, blockIdx + grid, .. (equal chunks, the busiest block has ceil(nch/grid))
+        const u64 cpb = (nch1 + grid1 - 1) / grid1;
+        double share = (double)cpb / (double)nch1;
+        if (src.from_rec && ctx->rec_slice_end.size() > 1) {      // a launch per slice: the busiest block's chunks of every slice add up
+            share = 0.0;
+            u64 rb = 0;
+            for (size_t sl = 0; sl < ctx->rec_slice_end.size(); ++sl) {
+                const u64 re = ctx->rec_slice_end[sl], nc = ctx->h_slice_chunk[sl + 1] - ctx->h_slice_chunk[sl];
+                if (nc) share += (double)((nc + grid1 - 1) / grid1) / (double)nc * (double)(re - rb) / (double)ctx->rec_n;
+                rb = re;
+            }
+        }
+        // ---- level-1 loads of this pass, per bin ("PartiInfo" before the spill): a positional sample -- the level-1 digit
+        // histogram of <= 1024 tiles spread over the source -- scaled to the pass.  Every bin's slices are sized from ITS load,
+        // so a bin that holds a repeat family (or poly-A) gets longer slices instead of overflowing the mean-sized ones.
+        // Records (multi-GPU receive side) have no histogram kernel: uniform loads.
+        const double pass_keys = (double)(ps.nvalid / ps.npass);
+        ps.load.assign(pl.P1, pass_keys / pl.P1);
+        ps.spread.assign(pl.P1, 0.0);
+        bool sampled = false;
+        // records (the multi-GPU receive side, the passes of a record-based multi-pass count): a positional sample of the records is
+        // expanded into a key array with pads (k_sk_sample_keys: SK_MAXN slots per candidate record) and sampled like any key array.
+        // Records that arrive in slices: the sample comes from the first slice (the slices are positional cuts of every sender's
+        // reads: alike), so only that slice has to have arrived.
+        const Key* d_keys_s = src.keys;              // the key array the sample kernels read
+        double smp_density = 1.0;                    // records: real keys per slot of the sample array (a level-1 tile is full, a sample tile is not)
+        bool rec_sample_ok = ctx->sentinel_ok;       // (the sample array is padded with the all-ones key, which the key-array kernels skip: only when it is no k-mer of this k)
+        u64 rec_units = 0;
+        if constexpr (W <= 2) {
+          if (src.from_rec && !ctx->tune.no_sample && !uniform1) {
+            const u64 nrec_s = ctx->rec_slice_end.size() > 1 ? ctx->rec_slice_end[0] : ctx->rec_n;
+            const u64 NR = RecTile<W>::NR;
+            const u64 nchk_all = (nrec_s + NR - 1) / NR;
+            const u64 nchk = std::min<u64>(nchk_all, 256);
+            if (nchk == 0) rec_sample_ok = false;
+            else {
+                { const int e = rec_gate_upto(ctx, 1); if (e) return e; }
+                std::vector<u64>& cbeg = ctx->h_cbeg;        // (the context's: it outlives the asynchronous copy below; the next use is behind this pass's next synchronisation)
+                cbeg.resize(nchk);
+                for (u64 i = 0; i < nchk; ++i) cbeg[i] = (i * nchk_all / nchk) * NR;
+                rec_units = nchk * NR * SK_MAXN;
+                CK(ctx->smp_keys.ensure(rec_units * sizeof(Key) + nchk * 8 + 64));
+                u64* d_cbeg = reinterpret_cast<u64*>(ctx->smp_keys.as<char>() + rec_units * sizeof(Key));
+                CK(hipMemcpyAsync(d_cbeg, cbeg.data(), nchk * 8, hipMemcpyHostToDevice, ctx->stream));
+                hipLaunchKernelGGL(k_sk_sample_keys<W>, dim3((unsigned)nchk), dim3(SKX_NT), 0, ctx->stream, ctx->rec_src, ctx->rec_n, ctx->sk_sp.R, (int)ctx->cfg.kmer_size,
+                                   (const u64*)d_cbeg, (u32)NR, ctx->smp_keys.as<Key>());
+                CKL("k_sk_sample_keys");
+                d_keys_s = ctx->smp_keys.as<Key>();
+            }
+          }
+        }
+        const bool smp_rec = src.from_rec && rec_units != 0;
+        if ((!src.from_rec || smp_rec) && rec_sample_ok && !ctx->tune.no_sample && !uniform1) {
+            const u64 units = src.from_reads ? src.nwords : smp_rec ? rec_units : src.nkeys, tile = src.from_reads ? Tile<W>::WORDS : Tile<W>::KEYS;
+            auto hist = [&](const ChunkDesc* dd, const u32* d_nch, u64 n, u32* mat) {
+                return src.from_reads ? launch_hist<W, 0>(ctx, nullptr, dd, d_nch, n, mat, pl.d1, pl.P1) : launch_hist<W, 1>(ctx, d_keys_s, dd, d_nch, n, mat, pl.d1, pl.P1);
+            };
+            u64 ntiles = 0, nts = 0, stot = 0;
+            { const int e = positional_sample(ctx, units, tile, pl.P1, hist, &ntiles, &nts, &stot); if (e) return e; }
+            if (stot >= (u64)pl.P1 * 64) {        // enough sampled keys to say something per bin
+                // one pass from the reads: scaled so that the loads add up to the exact number of valid k-mers; otherwise by position
+                const double scale = (src.from_reads && ps.npass > 1) ? (double)ntiles / (double)nts : pass_keys / (double)stot;
+                // tiles a block walks (the busiest one), and how far a bin's keys on those tiles may be from share * load:
+                //   the block's own spread: 5 sigma of the sum over its tiles of the per-tile count (variance measured on the sample),
+                //   the estimate's error  : 4 sigma of the sampled sum, scaled to the block's share
+                // (records: a level-1 tile is full, a tile of the sample array holds smp_density of its slots: the block walks
+                //  pass_keys * share / KEYS full tiles, each with 1 / density times the variance of a sample tile)
+                if (smp_rec) smp_density = std::max(0.05, (double)stot / ((double)nts * (double)Tile<W>::KEYS));
+                const double tiles_per_block = smp_rec ? pass_keys * share / (double)Tile<W>::KEYS : (double)ntiles * share;
+                for (u32 b = 0; b < pl.P1; ++b) {
+                    const double sum = (double)ctx->h_mom[2 * b], sq = (double)ctx->h_mom[2 * b + 1];
+                    const double mean = sum / (double)nts, var = std::max(mean, sq / (double)nts - mean * mean);      // (at least Poisson)
+                    ps.load[b] = sum * scale;
+                    ps.spread[b] = 5.0 * std::sqrt(tiles_per_block * var / smp_density) + 4.0 * std::sqrt((double)nts * var) * scale * share;
+                }
+                sampled = true;
+            }
+            // ---- a k-mer that alone is a large share of a level-1 bin (poly-A reads, a satellite: millions of occurrences):
+            // its bin stands far above the others.  Collect sampled keys of those bins, find the dominant k-mer(s) on the host
+            // and let the level-1 scatter count them apart (k_scatter<.., HEAVY>) -- everything lighter is what the region
+            // chains are for.
+            if constexpr (W <= 2) {
+                if (sampled && ps.opt_cap && !ctx->tune.no_heavy) { const int e = find_heavy<W>(ctx, src.from_reads, d_keys_s, (u32)nts, pl, ps.load, &ps.nheavy); if (e) return e; }
+            }
+            ctx->mark("sample1");
+        }
+        // slice of bin b = the busiest block's share of its load + the spread above + 1 % + 64 keys; without a sample: + 6 % + 160
+        // (what uniform reads need), in whole groups of 8 keys
+        ctx->h_boff.resize(pl.P1 + 1);
+        u64 area = 0;
+        if (uniform1) o1.uslice = 1u;          // (set below)
+        for (u32 b = 0; b < pl.P1; ++b) {
+            double sl = ps.load[b] * share;
+            // (records: the senders' zero-length pad records sit at the ends of their slices, so a level-1 chunk holds anything from
+            //  no pads to ~10 % -- a block that walks only a few chunks does not average that out: more room there)
+            const double few = (src.from_rec && share * (double)nch1 < 16.0) ? 0.08 : 0.0;
+            sl += sampled ? ps.spread[b] + sl * 0.01 + 64.0 : sl * (0.06 + few) + 160.0;
+            u64 slice = ((u64)sl + 8) & ~7ull;
+            if (uniform1) o1.uslice = (u32)slice;
+            if (ctx->tune.opt_slice) slice = ctx->tune.opt_slice;                                        // experiments / tests
+            ctx->h_boff[b] = (u32)std::min<u64>(area, 0xFFFFFFFFull); area += slice;
+        }
+        ctx->h_boff[pl.P1] = (u32)std::min<u64>(area, 0xFFFFFFFFull);
+        const u64 tail = 2 * Tile<W>::KEYS;                         // the dump zone behind the last slice (a tile's keys of a bin that outgrew its slice land there)
+        const u64 cells = (u64)pl.P1 * grid1;
+        if (ctx->tune.verbose) fprintf(stderr, "[dskgpu] pass %u/%u: P1 %u P2 %u, %u level-1 blocks, area %llu keys per block (%.2f GB of slices), sampled %d, keys %llu, %u chunks, share %.6f, %zu slices\n", ps.pass, ps.npass, pl.P1, pl.P2, grid1,
+                                       (unsigned long long)area, (double)area * grid1 * sizeof(Key) * 1e-9, (int)sampled, (unsigned long long)ps.nvalid, nch1, share, ctx->rec_slice_end.size());
+        if (area < 8 || area * grid1 + tail >= 0xFFFF0000ull) ps.opt1 = false;
+        else {
+            o1.area = (u32)area; o1.dump = (u32)(area * grid1);
+            CK(ctx->boff.ensure(((size_t)pl.P1 + 1) * 4));
+            CK(hipMemcpyAsync(ctx->boff.p, ctx->h_boff.data(), ((size_t)pl.P1 + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+            o1.boff = ctx->boff.as<u32>();
+            CK(ctx->mat1.ensure((cells + 1) * 4));                      // here: keys per (bin, block) slice
+            o1.fill = ctx->mat1.as<u32>();
+            if (grid1 + 1 > SLICED_MAX) ps.opt1 = false;                // the level-2 loader keeps the slice bounds in LDS
+            CK(ctx->bufA.ensure((area * grid1 + tail + 1) * sizeof(Key)));
+        }
+    }
+    if (src.from_rec && !ps.opt1) { const int e = records_to_keys(ctx, ps); if (e) return e; }
+    return DSKGPU_OK;
+}
+
+// The histogram-free level-1 scatter: one launch, on (source, one or several passes, k-mers counted apart or not).  Records and
+// heavy k-mers are one- and two-word keys only; so are several passes over a key array.
+template <int W, int SRC, int MODE, bool HEAVY>
+int scatter1_m(dskgpu_ctx* ctx, const PassState<W>& ps, const ChunkDesc* dd1, const u32* d_nch) {
+    return launch_scatter_m<W, SRC, MODE, true, HEAVY>(ctx, SRC == 1 ? ps.src.keys : nullptr, dd1, d_nch, ps.nch1, nullptr, ctx->bufA.template as<typename KeyT<W>::T>(),
+                                                       ps.pl.d1, ps.pl.P1, ps.o1);
+}
+template <int W>
+int launch_scatter1(dskgpu_ctx* ctx, const PassState<W>& ps, const ChunkDesc* dd1, const u32* d_nch) {
+    const bool mp = ps.npass > 1, heavy = ps.nheavy != 0, rec = ps.src.from_rec, reads = ps.src.from_reads;
+    if constexpr (W <= 2) {
+        if (rec && heavy) return mp ? scatter1_m<W, 2, 3, true>(ctx, ps, dd1, d_nch) : scatter1_m<W, 2, 1, true>(ctx, ps, dd1, d_nch);
+        if (rec) return mp ? scatter1_m<W, 2, 3, false>(ctx, ps, dd1, d_nch) : scatter1_m<W, 2, 1, false>(ctx, ps, dd1, d_nch);
+        if (heavy && reads) return mp ? scatter1_m<W, 0, 3, true>(ctx, ps, dd1, d_nch) : scatter1_m<W, 0, 1, true>(ctx, ps, dd1, d_nch);
+        if (heavy) return mp ? scatter1_m<W, 1, 3, true>(ctx, ps, dd1, d_nch) : scatter1_m<W, 1, 1, true>(ctx, ps, dd1, d_nch);
+        if (!reads && mp) return scatter1_m<W, 1, 3, false>(ctx, ps, dd1, d_nch);
+    } else if (rec || heavy || (!reads && mp)) return DSKGPU_E_STATE;
+    if (reads) return mp ? scatter1_m<W, 0, 3, false>(ctx, ps, dd1, d_nch) : scatter1_m<W, 0, 1, false>(ctx, ps, dd1, d_nch);
+    return scatter1_m<W, 1, 1, false>(ctx, ps, dd1, d_nch);
+}
+
+// Stage 3, level-1 scatter: the pass's scalars, then the histogram-free scatter or the exact histogram + scan + scatter
+// (which, for one of several passes, first checks that the pass fits its buffers: ps.too_big)
+template <int W>
+int pass_scatter1(dskgpu_ctx* ctx, PassState<W>& ps) {
+    typedef typename KeyT<W>::T Key;
+    const KeySource<W>& src = ps.src;
+    const Plan& pl = ps.pl;
+    const u32 nch1 = ps.nch1;
+    const u64 M1 = (u64)pl.P1 * nch1;
+    u32* h_sc = ctx->h_sc;
+    std::memset(h_sc, 0, sizeof(ctx->h_sc));
+    h_sc[SC_NCH1] = nch1; h_sc[SC_MLEN1] = (u32)M1; h_sc[SC_F] = pl.F;
+    if (ps.opt1) h_sc[SC_NCH2] = pl.P1;                    // level-2 chunks = the level-1 bin regions
+    h_sc[SC_WORK2] = (u32)std::min<u64>(pl.P1, (u64)ctx->num_cu);   // work counter of the segment-owned level-2 scatter: first segment not taken in the first round
+    // (with them: histogram / distinct counters of THIS pass attempt -- a table-overflow retry must not double count)
+    {
+        static_assert(sizeof(ctx->h_sc) == sizeof(ScalarSet), "scalar block");
+        ScalarSet hs; std::memcpy(hs.v, h_sc, sizeof hs.v);
+        const u32 nh = ctx->cfg.histo_max + 1;
+        u64 nzero = 0;
+        if (pl.levels == 2 && ps.opt_cap) { nzero = ps.nregions + 1; CK(ctx->mat2.ensure((size_t)nzero * 4)); }      // level 2's keys per region (home regions, then the extension pool)
+        const u64 work = std::max<u64>(nh, nzero);
+        hipLaunchKernelGGL(k_setup_pass, dim3((unsigned)std::min<u64>(1024, (work + 255) / 256)), dim3(256), 0, ctx->stream, ps.sc, hs, ctx->ghist.as<u64>(), nh, ctx->gstats.as<u64>(), 4u,
+                           nzero ? ctx->mat2.as<u32>() : (u32*)nullptr, nzero);
+        CKL("k_setup_pass");
+    }
+    ctx->mark("setup");
+    int rc;
+    const ChunkDesc* dd1 = ctx->descs1.as<ChunkDesc>();
+    if (ps.opt1) {
+        Opt1Spec& o1 = ps.o1;
+        if constexpr (W <= 2) { if (ps.nheavy) { o1.hv_keys = ctx->hv_buf.as<u64>() + HvLayout<W>::keys; o1.hv_cnt = reinterpret_cast<unsigned long long*>(ctx->hv_buf.as<u64>() + HvLayout<W>::counts); } }
+        if (src.from_rec && ctx->rec_slice_end.size() > 1) {
+            // the records arrive in slices: one launch per slice, each behind the arrival of its slice (rec_gate), the blocks'
+            // write cursors parked in between
+            const size_t S = ctx->rec_slice_end.size();
+            CK(ctx->cur_state.ensure((size_t)ps.grid1 * pl.P1 * 4));
+            o1.cur_state = ctx->cur_state.as<u32>();
+            rc = DSKGPU_OK;
+            for (size_t sl = 0; sl < S && rc == DSKGPU_OK; ++sl) {
+                if ((rc = rec_gate_upto(ctx, (u32)sl + 1))) break;
+                o1.g0 = ctx->h_slice_chunk[sl]; o1.gn = ctx->h_slice_chunk[sl + 1] - ctx->h_slice_chunk[sl];
+                o1.resume = sl > 0 ? 1u : 0u; o1.last = sl + 1 == S ? 1u : 0u;
+                rc = launch_scatter1<W>(ctx, ps, dd1, ps.sc + SC_NCH1);
+            }
+        }
+        else if (src.from_rec) { if (!(rc = rec_gate_all(ctx))) rc = launch_scatter1<W>(ctx, ps, dd1, ps.sc + SC_NCH1); }
+        else rc = launch_scatter1<W>(ctx, ps, dd1, ps.sc + SC_NCH1);
+        if (rc) return rc;
+        ctx->mark("scatter1");
+        return DSKGPU_OK;
+    }
+    CK(ctx->mat1.ensure((M1 + 1) * 4));
+    if (src.from_reads) rc = launch_hist<W, 0>(ctx, nullptr, dd1, ps.sc + SC_NCH1, nch1, ctx->mat1.as<u32>(), pl.d1, pl.P1);
+    else rc = launch_hist<W, 1>(ctx, src.keys, dd1, ps.sc + SC_NCH1, nch1, ctx->mat1.as<u32>(), pl.d1, pl.P1);
+    if (rc) return rc;
+    ctx->mark("hist1");
+    if ((rc = run_scan(ctx, ctx->mat1.as<u32>(), ps.sc + SC_MLEN1, M1))) return rc;
+    ctx->mark("scan1");
+    if (ps.npass > 1) {      // the pass must fit the buffers sized for it (skewed inputs can overfill one pass)
+        CK(hipMemcpyAsync(&ps.nkeys, ctx->mat1.as<u32>() + M1, 4, hipMemcpyDeviceToHost, ctx->stream));
+        CK(hipStreamSynchronize(ctx->stream));
+        if ((u64)ps.nkeys > ps.cap) { ps.too_big = true; return DSKGPU_OK; }
+    }
+    if (src.from_reads) rc = launch_scatter<W, 0>(ctx, nullptr, dd1, ps.sc + SC_NCH1, nch1, ctx->mat1.as<u32>(), ctx->bufA.as<Key>(), pl.d1, pl.P1);
+    else rc = launch_scatter<W, 1>(ctx, src.keys, dd1, ps.sc + SC_NCH1, nch1, ctx->mat1.as<u32>(), ctx->bufA.as<Key>(), pl.d1, pl.P1);
+    if (rc) return rc;
+    ctx->mark("scatter1");
+    return DSKGPU_OK;
+}
+
+// Stage 4, level 2 and the final offsets.  The fixed-capacity regions (k_scatter_al<.., OPT>): no histogram pass, every
+// sub-partition gets a region of opt_cap keys (+ chains of extension regions); a pool that runs out (heavy repeats) sends the
+// attempt back through the exact histogram + scan path, and the context remembers it for these reads.
+template <int W>
+int pass_scatter2(dskgpu_ctx* ctx, PassState<W>& ps) {
+    const Plan& pl = ps.pl;
+    int rc;
+    ps.fkeys = ctx->bufA.as<typename KeyT<W>::T>();
+    ps.scratch = &ctx->bufB;
+    CK(ctx->fstart.ensure(((size_t)pl.F + 2) * 4));
+    CK(ctx->nsolid.ensure(((size_t)pl.F + 2) * 4));
+    if (pl.levels == 2 && ps.opt_cap) {
+        CK(ctx->bufB.ensure((ps.nregions * ps.opt_cap + ATile<W>::KEYS + 16) * sizeof(typename KeyT<W>::T)));
+        CK(ctx->descs2.ensure(((size_t)pl.P1 * 2 + 1) * sizeof(ChunkDesc)));
+        CK(ctx->seg.ensure((size_t)pl.P1 * sizeof(SegInfo)));
+        CK(ctx->mat2.ensure(((size_t)ps.nregions + 1) * 4));                  // here: keys per region (home regions, then the extension pool)
+        CK(ctx->chain_next.ensure(((size_t)ps.nregions + 1 + ps.max_ext + 1) * 4));   // links (only read where subcnt has its chain bit set), then the list of chained sub-partitions
+        // (zeroed by k_setup_pass)
+        if (ps.opt1) {      // segments = the level-1 bin regions (slices + sentinel tails)
+            ctx->h_descs2.resize(pl.P1);
+            // heaviest segments first (the kernel hands them out by a work counter): a segment that holds a repeat family takes a
+            // block longer than the others, so it must not be the last thing a block starts
+            std::vector<u32> order(pl.P1);
+            for (u32 sgm = 0; sgm < pl.P1; ++sgm) order[sgm] = sgm;
+            // (in steps of 5 % of the mean, stable: the segments of uniform reads keep their natural order, neighbours in memory run together)
+            double mean_work = 0.0; for (double w : ps.load) mean_work += w; mean_work = std::max(1.0, mean_work / pl.P1);
+            auto wclass = [&](u32 a) { return (long long)(ps.load[a] / (0.05 * mean_work)); };
+            std::stable_sort(order.begin(), order.end(), [&](u32 a, u32 b) { return wclass(a) > wclass(b); });
+            for (u32 i = 0; i < pl.P1; ++i) {
+                const u32 sgm = order[i];
+                ChunkDesc d; d.begin = ctx->h_boff[sgm]; d.end = ctx->h_boff[sgm + 1]; d.flat_base = sgm * pl.P2; d.stride = 1;   // slice i of the segment: + i * area
+                ctx->h_descs2[i] = d;
+            }
+            CK(hipMemcpyAsync(ctx->descs2.p, ctx->h_descs2.data(), (size_t)pl.P1 * sizeof(ChunkDesc), hipMemcpyHostToDevice, ctx->stream));
+        } else {
+            hipLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, ctx->stream, ctx->mat1.as<u32>(), ps.nch1, pl.P1, 0x7FFFFFFFu, pl.P2,
+                               ctx->seg.as<SegInfo>(), ctx->descs2.as<ChunkDesc>(), ps.sc + SC_NCH2, ps.sc + SC_MLEN2, 1u);
+            CKL("k_plan");
+        }
+        ctx->mark("plan2");
+        OptSpec os{ps.opt_cap, ctx->mat2.as<u32>(), ps.sc + SC_OVF2, ps.opt1 ? ps.o1.fill : nullptr, 0u, ps.grid1, (u64)ps.o1.area,
+                   pl.F, ps.max_ext, ctx->chain_next.as<u32>(), ps.sc + SC_EXT, ctx->chain_next.as<u32>() + ps.nregions + 1, ps.sc + SC_NCHAINED,
+                   ps.sc + SC_WORK2, nullptr};
+        if (ctx->tune.verbose && ps.opt1) { CK(ctx->dbg.ensure((size_t)pl.P1 * 24)); os.dbg = ctx->dbg.as<unsigned long long>(); }
+        if (ps.opt1) rc = launch_scatter_al<W, 2, true, true>(ctx, ctx->bufA.as<typename KeyT<W>::T>(), ctx->descs2.as<ChunkDesc>(), ps.sc + SC_NCH2, (u64)pl.P1 * 2, nullptr,
+                                                              ctx->bufB.as<typename KeyT<W>::T>(), pl.d2, pl.P2, os);
+        else rc = launch_scatter_al<W, 2, true, false>(ctx, ctx->bufA.as<typename KeyT<W>::T>(), ctx->descs2.as<ChunkDesc>(), ps.sc + SC_NCH2, (u64)pl.P1 * 2, nullptr,
+                                                       ctx->bufB.as<typename KeyT<W>::T>(), pl.d2, pl.P2, os);
+        if (rc) return rc;
+        ctx->mark("scatter2");
+        if (ctx->tune.verbose && ps.opt1) {      // per-segment times of the level-2 scatter, in hand-out order
+            std::vector<unsigned long long> t((size_t)pl.P1 * 3);
+            CK(hipMemcpyAsync(t.data(), ctx->dbg.p, t.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+            CK(hipStreamSynchronize(ctx->stream));
+            unsigned long long t0 = ~0ull, t1 = 0; for (u32 i = 0; i < pl.P1; ++i) { t0 = std::min(t0, t[3 * i]); t1 = std::max(t1, t[3 * i + 1]); }
+            fprintf(stderr, "[dskgpu] level 2: %u segments, %.3f ms first start -> last end\n", pl.P1, (t1 - t0) * 1e-5);
+            for (u32 i = 0; i < pl.P1; ++i)
+                if (i < 6 || i + 3 >= pl.P1 || t[3 * i + 1] + 20000 > t1)
+                    fprintf(stderr, "[dskgpu]   desc %u (segment %u, load %.0f) block %llu: %.3f .. %.3f ms\n", i, (u32)(ctx->h_descs2[i].flat_base / pl.P2),
+                            ps.load[ctx->h_descs2[i].flat_base / pl.P2], t[3 * i + 2], (t[3 * i] - t0) * 1e-5, (t[3 * i + 1] - t0) * 1e-5);
+        }
+        ps.fkeys = ctx->bufB.as<typename KeyT<W>::T>();
+        ps.scratch = &ctx->bufA;
+    } else if (pl.levels == 2) {
+        const u64 max_chunks2 = ps.cap / CH2 + pl.P1 + 1;
+        const u64 M2 = max_chunks2 * pl.P2;
+        if (M2 >= 0xFFFFFFFFull) return fail(ctx, DSKGPU_E_ARG, "level-2 matrix too large");
+        CK(ctx->descs2.ensure(max_chunks2 * sizeof(ChunkDesc)));
+        CK(ctx->seg.ensure((size_t)pl.P1 * sizeof(SegInfo)));
+        CK(ctx->mat2.ensure((M2 + 1) * 4));
+        hipLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, ctx->stream, ctx->mat1.as<u32>(), ps.nch1, pl.P1, CH2, pl.P2,
+                           ctx->seg.as<SegInfo>(), ctx->descs2.as<ChunkDesc>(), ps.sc + SC_NCH2, ps.sc + SC_MLEN2, 0u);
+        CKL("k_plan");
+        ctx->mark("plan2");
+        const ChunkDesc* dd2 = ctx->descs2.as<ChunkDesc>();
+        if ((rc = launch_hist<W, 1>(ctx, ctx->bufA.as<typename KeyT<W>::T>(), dd2, ps.sc + SC_NCH2, max_chunks2, ctx->mat2.as<u32>(), pl.d2, pl.P2))) return rc;
+        ctx->mark("hist2");
+        if ((rc = run_scan(ctx, ctx->mat2.as<u32>(), ps.sc + SC_MLEN2, M2))) return rc;
+        ctx->mark("scan2");
+        if ((rc = launch_scatter<W, 1>(ctx, ctx->bufA.as<typename KeyT<W>::T>(), dd2, ps.sc + SC_NCH2, max_chunks2, ctx->mat2.as<u32>(), ctx->bufB.as<typename KeyT<W>::T>(), pl.d2, pl.P2))) return rc;
+        ctx->mark("scatter2");
+        ps.fkeys = ctx->bufB.as<typename KeyT<W>::T>();
+        ps.scratch = &ctx->bufA;
+        hipLaunchKernelGGL(k_final_offsets, dim3((pl.F + 256) / 256), dim3(256), 0, ctx->stream, ctx->mat2.as<u32>(),
+                           ctx->seg.as<SegInfo>(), pl.P2, 0u, ps.sc + SC_MLEN2, ctx->fstart.as<u32>(), pl.F);
+    } else {
+        hipLaunchKernelGGL(k_final_offsets, dim3((pl.F + 256) / 256), dim3(256), 0, ctx->stream, ctx->mat1.as<u32>(),
+                           (const SegInfo*)nullptr, pl.P1, ps.nch1, ps.sc + SC_MLEN1, ctx->fstart.as<u32>(), pl.F);
+    }
+    CKL("k_final_offsets");
+    ctx->mark("offsets");
+    return DSKGPU_OK;
+}
+
+// the count kernels (the sub-partitions, those that went on in extension regions, the k-mers counted apart), the scan of the
+// solid rows per sub-partition, the sizes back to the host (one sync)
+template <int W>
+int count_and_sizes(dskgpu_ctx* ctx, PassState<W>& ps, const CountParams& cp) {
+    typedef typename KeyT<W>::T Key;
+    const Plan& pl = ps.pl;
+    const unsigned cgrid = (unsigned)std::min<u64>(pl.F, (u64)ctx->num_cu * 2);
+    launch_count<W>(ctx, cgrid, ps.fkeys, ps.solid_keys, ps.solid_ab, ps.sc + SC_OVERFLOW, cp);
+    CKL("k_count");
+    if constexpr (W <= 2) {
+        if (ps.opt_cap && ps.max_ext) {      // the sub-partitions that went on in extension regions (none on repeat-free reads: the blocks leave at once)
+            auto kern = [] { if constexpr (W == 1) return k_count_chained; else return k_count_chained_mw<2>; }();
+            hipLaunchKernelGGL(kern, dim3((unsigned)std::min<u64>(ps.max_ext, (u64)ctx->num_cu * 2)), dim3(CNT_NT), 0, ctx->stream, ps.fkeys, ps.solid_keys, ps.solid_ab,
+                               ctx->nsolid.as<u32>(), ctx->ghist.as<u64>(), ctx->gstats.as<u64>(), ps.sc + SC_OVERFLOW, cp, (const u32*)cp.subcnt,
+                               (const u32*)ctx->chain_next.as<u32>(), (const u32*)(ctx->chain_next.as<u32>() + ps.nregions + 1), (const u32*)(ps.sc + SC_NCHAINED), ps.max_ext);
+            CKL(W == 1 ? "k_count_chained" : "k_count_chained_mw");
+        }
+        if (ps.nheavy) {      // the k-mers the level-1 scatter counted apart: histogram, distinct count, rows (appended behind the compacted ones: pass_rows)
+            const u32 slots = HV_KEYS;
+            u64* hvb = ctx->hv_buf.as<u64>();
+            hipLaunchKernelGGL(k_heavy_rows<W>, dim3((slots + 255) / 256), dim3(256), 0, ctx->stream, reinterpret_cast<const Key*>(hvb + HvLayout<W>::keys),
+                               (const unsigned long long*)(hvb + HvLayout<W>::counts), slots, cp.amin, cp.amax, cp.histo_max, ctx->ghist.as<u64>(), ctx->gstats.as<u64>(),
+                               hvb + HvLayout<W>::rows, reinterpret_cast<u32*>(hvb + HvLayout<W>::ab));
+            CKL("k_heavy_rows");
+        }
+    }
+    ctx->mark("count");
+    if (int e = run_scan(ctx, ctx->nsolid.as<u32>(), ps.sc + SC_F, pl.F)) return e;
+    ctx->mark("scan_solid");
+    // (k-mers of the pass: the last sub-partition offset, or -- fixed-capacity regions -- the level-1 total; with block-owned slices
+    //  the scatter's own count in gstats[2])
+    CK(ctx->back_dev.ensure(16 * 8));
+    if (!ctx->back_host) CK(hipHostMalloc(reinterpret_cast<void**>(&ctx->back_host), 16 * 8, hipHostMallocDefault));
+    const u32* nkp = ps.opt1 ? nullptr : (ps.opt_cap ? ctx->mat1.as<u32>() + (u64)pl.P1 * ps.nch1 : ctx->fstart.as<u32>() + pl.F);
+    hipLaunchKernelGGL(k_gather_back, dim3(1), dim3(64), 0, ctx->stream, (const u32*)ps.sc, (const u32*)(ctx->nsolid.as<u32>() + pl.F), nkp,
+                       (const u64*)ctx->gstats.as<u64>(), ctx->back_dev.as<u64>());
+    CKL("k_gather_back");
+    CK(hipMemcpyAsync(ctx->back_host, ctx->back_dev.p, 10 * 8, hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    const u64* bh = ctx->back_host;
+    ps.flags = (u32)bh[0]; ps.nsolid = (u32)bh[1]; if (!ps.opt1) ps.nkeys = (u32)bh[2];
+    ps.ovf2 = (u32)bh[3]; ps.ovf1 = (u32)bh[4]; ps.ext = (u32)bh[5];
+    for (int x = 0; x < 4; ++x) ps.stats[x] = bh[6 + x];
+    return DSKGPU_OK;
+}
+
+// Stage 5, count: one-word keys write solid rows in place (+ abundance into the free ping-pong buffer); two-word keys write rows
+// into the free buffer (+ abund2), and may count twice (below)
+template <int W>
+int pass_count(dskgpu_ctx* ctx, PassState<W>& ps) {
+    CountParams cp;
+    cp.F = ps.pl.F;
+    cp.maxload = W == 1 ? CNT_MAXLOAD : C2_MAXLOAD;
+    if (ctx->tune.table_maxload) cp.maxload = std::min<u32>(cp.maxload, ctx->tune.table_maxload);
+    cp.amin = ctx->cfg.abundance_min; cp.amax = ctx->cfg.abundance_max; cp.histo_max = ctx->cfg.histo_max;
+    cp.cap = ps.opt_cap; cp.subcnt = ps.opt_cap ? ctx->mat2.as<u32>() : nullptr;
+    ps.solid_keys = W == 1 ? ps.fkeys : ps.scratch->template as<typename KeyT<W>::T>();
+    ps.solid_ab = W == 1 ? ps.scratch->template as<u32>() : ctx->abund2.as<u32>();
+    if constexpr (W == 2) CK(hipMemcpyAsync(ctx->gstats.as<u64>() + 3, ctx->gstats.as<u64>() + 2, 8, hipMemcpyDeviceToDevice, ctx->stream));      // (the keys level 1 placed, before k_heavy_rows adds to them: see below)
+    if (int e = count_and_sizes<W>(ctx, ps, cp)) return e;
+    if constexpr (W == 2) {
+        // k_count2v3 keys its table by the mixed top word alone and checks every key's low word afterwards.  Two different k-mers of the pass with
+        // the same top word (birthday bound of a 64-bit hash: n^2 / 2^65 -- 0.5 % of the runs at 4 * 10^8 distinct k-mers), or one whose top word
+        // is the empty-slot value: the count runs again with the index-table kernel (the keys are untouched: two-word rows go to the other
+        // buffer), and the rest of the reads' passes use that kernel too.  Tests craft both cases.
+        if ((ps.flags & (CNT_OVF_VERIFY | CNT_OVF_SENTINEL)) && !((ps.opt_cap && ps.ovf2) || (ps.opt1 && ps.ovf1))) {
+            if (ctx->tune.verbose) fprintf(stderr, "[dskgpu] pass %u/%u: the top-word table met k-mers it cannot tell apart (flags %u): counting again with k_count_mw\n", ps.pass, ps.npass, ps.flags);
+            ctx->mw_v3_off = true;
+            ctx->stats.n_retries += 1;
+            CK(hipMemsetAsync(ctx->ghist.p, 0, ((size_t)ctx->cfg.histo_max + 1) * 8, ctx->stream));
+            CK(hipMemsetAsync(ctx->gstats.p, 0, 2 * 8, ctx->stream));
+            CK(hipMemcpyAsync(ctx->gstats.as<u64>() + 2, ctx->gstats.as<u64>() + 3, 8, hipMemcpyDeviceToDevice, ctx->stream));
+            CK(hipMemsetAsync(ps.sc + SC_OVERFLOW, 0, 4, ctx->stream));
+            if (int e = count_and_sizes<W>(ctx, ps, cp)) return e;
+        }
+    }
+    if (ps.opt1) ps.nkeys = (u32)ps.stats[2];
+    return DSKGPU_OK;
+}
+
+// the solid rows of a pass where the count kernels left them (regions / exact ranges), with the rows of the k-mers counted apart as
+// a dense tail (ro / rows_ab from row n_sparse on: already un-mixed)
+template <int W>
+void sparse_rows(dskgpu_ctx* ctx, const PassState<W>& ps, const RowsOut& ro, u32* rows_ab, u32 n_tail, dskgpu_ctx::SparseRows& spr, dskgpu_ctx::SparseRows2& spr2) {
+    const u64 n = ps.nsolid;
+    if constexpr (W == 1) {
+        spr.s = RsSparse{(const u64*)ps.solid_keys, (const u32*)ps.solid_ab, (const u32*)ctx->nsolid.as<u32>(), (const u32*)ctx->fstart.as<u32>(), ps.opt_cap, ps.pl.F, 0u};
+        spr.n_sparse = n; spr.n_tail = n_tail; spr.tail_k = n_tail ? ro.w[0] + n : nullptr; spr.tail_v = n_tail ? rows_ab + n : nullptr;
+    } else if constexpr (W == 2) {
+        spr2.s = Rs2Sparse{(const K2*)ps.solid_keys, (const u32*)ps.solid_ab, (const u32*)ctx->nsolid.as<u32>(), (const u32*)ctx->fstart.as<u32>(), ps.opt_cap, ps.pl.F, 0u};
+        spr2.n_sparse = n; spr2.n_tail = n_tail;
+        spr2.tail = n_tail ? Rows2C{ro.w[1] + n, ro.w[0] + n, rows_ab + n} : Rows2C{nullptr, nullptr, nullptr};
+    }
+}
+
+// Stage 6, the pass's rows: the heavy tail, then the hand-off to the row sort (sparse), the multi-pass partition order, or k_compact
+template <int W>
+int pass_rows(dskgpu_ctx* ctx, PassState<W>& ps) {
+    typedef typename KeyT<W>::T Key;
+    const Plan& pl = ps.pl;
+    const u32 h_nsolid = ps.nsolid;
+    const u64 nhs = ps.nheavy ? ps.stats[1] : 0;                    // solid rows of the k-mers counted apart
+    const u64 ns = ps.rows = h_nsolid + nhs;
+    // (a pass of a multi-pass job whose accumulators have room: the rows go there directly -- no copy of 0.7 GB per pass afterwards)
+    const bool to_sink = ctx->sink.active && ctx->sink.rows + ns + 1 <= ctx->sink.cap;
+    RowsOut ro{};
+    u32* rows_ab = nullptr;
+    if (to_sink) {
+        rows_ab = ctx->sink.ab + ctx->sink.rows;
+        for (int x = 0; x < W; ++x) ro.w[x] = ctx->sink.w[x] + ctx->sink.rows;
+        ctx->sink.took = true;
+    } else {
+        CK(ctx->out_ab.ensure((ns + 1) * 4));
+        rows_ab = ctx->out_ab.as<u32>();
+        for (int x = 0; x < W; ++x) { CK(ctx->out_w[x].ensure((ns + 1) * 8)); ro.w[x] = ctx->out_w[x].as<u64>(); }
+    }
+    if constexpr (W <= 2) {
+      if (nhs) {
+        for (int x = 0; x < W; ++x)
+            CK(hipMemcpyAsync(ro.w[x] + h_nsolid, ctx->hv_buf.as<u64>() + HvLayout<W>::rows + (size_t)x * HV_KEYS, nhs * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        CK(hipMemcpyAsync(rows_ab + h_nsolid, ctx->hv_buf.as<u64>() + HvLayout<W>::ab, nhs * 4, hipMemcpyDeviceToDevice, ctx->stream));
+      }
+    }
+    ctx->stats.n_heavy += ps.nheavy;
+    // Rows of a single pass that the hand-written MSD sort will order: its first step reads them where they lie (the regions /
+    // exact ranges of the count kernel + the few rows of the k-mers counted apart as a dense tail) -- no dense copy is made first
+    // (k_compact: 0.5 GB read + 0.5 GB written, 0.30 ms of a 14 ms step).  Several passes accumulate dense rows as before.
+    // (two-word rows: the same, through rowsort2.h's sparse step A -- sort_rows2_msd is what sort_rows picks under these conditions)
+    bool sparse_sort = false;
+    if constexpr (W <= 2) {
+        sparse_sort = ps.npass == 1 && ctx->job_passes == 1 && ns > 0 && ns <= rs_max_rows(ctx) && !(ctx->cfg.flags & DSKGPU_F_NO_SORT) &&
+                      !ctx->tune.rs_slab_rows && !ctx->bank_job.active && (W == 1 || 2u * ctx->cfg.kmer_size > 64u);
+        if (sparse_sort) {
+            sparse_rows<W>(ctx, ps, ro, rows_ab, (u32)nhs, ctx->sp_rows, ctx->sp_rows2);
+            ctx->sp_rows.valid = W == 1; ctx->sp_rows2.valid = W == 2;
+        }
+    }
+    bool mp_part = false;
+    if constexpr (W <= 2) {      // DSKGPU_F_PARTITION_ORDER in a multi-pass count: the pass's rows ordered partition by partition on their way into the dense arrays
+        mp_part = !sparse_sort && ctx->job_passes > 1 && ctx->mp_part_ok && ns > 0 && h_nsolid < 0xFFFF0000ull && (W == 1 || 2u * ctx->cfg.kmer_size > 64u);
+        if (!sparse_sort && ctx->job_passes > 1 && ns > 0 && !mp_part) ctx->mp_part_ok = false;      // (one pass outside the scheme: the job keeps the global order)
+        if (mp_part) {
+            dskgpu_ctx::SparseRows spr{}; dskgpu_ctx::SparseRows2 spr2{};
+            sparse_rows<W>(ctx, ps, ro, rows_ab, (u32)nhs, spr, spr2);
+            const u32 np_est = part_sort_nparts(W, pl.F, h_nsolid, (u32)nhs);
+            if (ctx->mp_part_off.ensure_keep(((size_t)ctx->mp_off_used + np_est + 2) * 4, (size_t)ctx->mp_off_used * 4, ctx->stream)) return fail(ctx, DSKGPU_E_NOMEM, "partition offsets");
+            u32 np = 0;
+            const int prc = launch_part_sort(ctx, W, spr, spr2, ro.w[0], rows_ab, Rows2{W == 2 ? ro.w[1] : nullptr, ro.w[0], rows_ab},
+                                             ctx->mp_part_off.as<u32>() + ctx->mp_off_used, ctx->mp_flag.as<u32>(), &np, nullptr);
+            if (prc) return prc;
+            ctx->mp_parts.push_back(dskgpu_ctx::MpPart{0ull, np, ctx->mp_off_used});      // (row_base: the caller knows where the pass's rows start in the job)
+            ctx->mp_off_used += np + 1;
+        }
+    }
+    if (!sparse_sort && !mp_part) {
+        hipLaunchKernelGGL(k_compact<W>, dim3((pl.F + 3) / 4), dim3(256), 0, ctx->stream, (const Key*)ps.solid_keys, (const u32*)ps.solid_ab,
+                           ctx->fstart.as<u32>(), ctx->nsolid.as<u32>(), pl.F, ro, rows_ab, ps.opt_cap);
+        CKL("k_compact");
+    }
+    ctx->mark("compact");
+    ctx->stats.n_ext_regions += std::min<u32>(ps.ext, ps.max_ext);
+    return DSKGPU_OK;
+}
+
+// What a pass leaves for run_pipeline.  too_big: the pass holds more keys (keys_seen) than `cap`; nothing else is set then.
+struct PassResult { u64 rows = 0, kmers = 0, distinct = 0, keys_seen = 0; Plan plan{}; bool too_big = false; };
+
+// One pass: partition + count the keys of pass `pass` (of `npass`) and leave its solid rows (unsorted) in out_w[0]/out_w[1]/out_ab,
+// the job's accumulators (ctx->sink) or where the count kernels put them (ctx->sp_rows / sp_rows2).
+// An overflow of a level-1 slice or the level-2 pool repeats the attempt on the exact path; a table overflow repeats it with a
+// finer partition, at most three times.
 template <int W>
 int run_one_pass(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_keys_in, u64 nkeys_in, u64 nwords,
-                 u32 pass, u32 npass, u64 cap, u64* ns_out, u64* nk_out, Plan* plan_out) {
-    typedef typename KeyT<W>::T Key;
-    u32* sc = ctx->scalars.as<u32>();
+                 u32 pass, u32 npass, u64 cap, PassResult* res) {
     ctx->sp_rows.valid = false; ctx->sp_rows2.valid = false;
-    int extra_bits = 0;
-    for (int attempt = 0;; ++attempt) {
-        Plan pl;
-        // keys the plan is sized for: the exact number of valid windows of a single pass from the reads; of several passes its share
-        // + 2 % (cap holds 6 % head-room: sized for it, 7 passes of 200 M reads needed 1792 level-1 bins, more than the LDS of the
-        // histogram-free level 1 holds)
-        const u64 plan_n = (from_reads && ctx->have_nvalid) ? std::min<u64>(cap, npass == 1 ? ctx->h_nvalid + 1 : ctx->h_nvalid / npass + ctx->h_nvalid / npass / 50 + 4096) : cap;
-        if (!make_plan(plan_n, extra_bits, W, (u32)ctx->num_cu, &pl))
-            return fail(ctx, DSKGPU_E_OVERFLOW, "cannot partition finer (table overflow persists)");
-        pl.d1.world = pl.d2.world = ctx->cfg.world_size; pl.d1.npass = pl.d2.npass = npass; pl.d1.pass = pl.d2.pass = pass;
-        // ---------------- level 1
-        u32 nch1 = 0;
-        const u64 max_chunks1 = (u64)ctx->num_cu * 8;
-        // key source: the encoded reads, a key array, or (multi-GPU receive side) super-k-mer records that the
-        // histogram-free level-1 scatter reads directly; any other path expands them to a key array first
-        bool from_rec = !from_reads && d_keys_in == nullptr;
-        auto upload_descs1 = [&]() -> int {
-            if (from_reads) build_descs1(ctx, nwords, Tile<W>::WORDS, max_chunks1, &nch1);
-            else if (from_rec && ctx->rec_slice_end.size() > 1) build_descs1_slices(ctx, RecTile<W>::NR, max_chunks1, &nch1);
-            else if (from_rec) build_descs1(ctx, ctx->rec_n, RecTile<W>::NR, max_chunks1, &nch1);
-            else build_descs1(ctx, nkeys_in, Tile<W>::KEYS, max_chunks1, &nch1);
-            CK(ctx->descs1.ensure(ctx->h_descs1.size() * sizeof(ChunkDesc)));
-            CK(hipMemcpyAsync(ctx->descs1.p, ctx->h_descs1.data(), ctx->h_descs1.size() * sizeof(ChunkDesc),
-                              hipMemcpyHostToDevice, ctx->stream));
-            return DSKGPU_OK;
-        };
-        auto records_to_keys = [&]() -> int {        // leave the records path: expand once, then it is a key array
-            int e = expand_records<W>(ctx, nkeys_in);
-            if (e) return e;
-            d_keys_in = ctx->sk_keys.as<Key>(); from_rec = false;
-            return upload_descs1();
-        };
-        { int e = upload_descs1(); if (e) return e; }
-        // One-word keys straight from the reads, one pass, two levels: both scatters run without a histogram
-        // pass (block-owned slices at level 1, segment-owned regions at level 2); any overflow sends the whole
-        // attempt back through the exact histogram + scan path.
-        u32 opt_cap = 0;                 // level 2: keys per sub-partition region (0 = exact offsets)
-        if (pl.levels == 2 && ctx->sentinel_ok && !ctx->opt2_off && !ctx->tune.no_opt2 && ascatter_lds(W, pl.P2) <= 160 * 1024)
-            opt_cap = opt_groups(W) * (8u / W);                                                 // 545 (two-word keys: 1091) groups of 64 B
-        if (opt_cap && ctx->tune.opt_cap) opt_cap = ctx->tune.opt_cap;                       // experiments / tests
-        if (W > 1 && (u64)pl.F * opt_cap >= 0xFFFF0000ull) opt_cap = 0;                       // k_count<W> keeps 32-bit offsets
-        // extension regions behind the home regions (region chains, kernels.h): an eighth of the home regions + 4096; their offsets
-        // inside the pool stay below 2^31.  Two-word keys (k_count_mw / k_count_chained_mw index keys with 32 bits): home regions
-        // and pool together below 2^32 keys.  Four-word keys: none (tiles of 4096 keys: the scan over the bins dominates anyway).
-        u32 max_ext = 0;
-        if (opt_cap && W <= 2) {
-            u64 want = std::min<u64>((u64)pl.F / 8 + 4096, 0x7FFFFFFFull / opt_cap - 1);
-            if (ctx->tune.max_ext >= 0) want = (u64)ctx->tune.max_ext;                                 // tests
-            if (W > 1) { const u64 room = 0xFFFF0000ull / opt_cap; want = room > (u64)pl.F + 1 ? std::min<u64>(want, room - pl.F - 1) : 0; }
-            max_ext = (u32)want;
-        }
-        const u64 nregions = (u64)pl.F + max_ext;
-        if (!opt_cap) { CK(ctx->bufA.ensure((cap + 1) * sizeof(Key))); CK(ctx->bufB.ensure((cap + 1) * sizeof(Key))); }      // exact offsets: the keys of the pass, twice
-        if (opt_cap) {
-            // the rows of the solid k-mers land at the region offsets too: abundances (one-word keys: in bufA, the free
-            // ping-pong buffer) or keys + abundances (multi-word keys: bufA + abund2).  Size everything BEFORE level 1 writes bufA.
-            const u64 slots = (u64)pl.F * opt_cap + ATile<W>::KEYS + 16;
-            CK(ctx->bufA.ensure(std::max<u64>(W == 1 ? slots * 4 : slots * sizeof(Key), (cap + 1) * sizeof(Key))));
-            if (W > 1) CK(ctx->abund2.ensure(slots * 4));
-        }
-        bool opt1 = opt_cap && !ctx->opt1_off && !ctx->tune.no_opt1 && (npass == 1 || from_reads || W <= 2);   // several passes over records / a key array (the multi-GPU receive side): one- and two-word keys
-        if (from_rec && (!opt1 || W > 2 || ctx->tune.no_recsrc)) { int e = records_to_keys(); if (e) return e; }
-        Opt1Spec o1{nullptr, 0u, 0u, sc + SC_OVF1, nullptr, ctx->sk_sp.R, ctx->gstats.as<u64>() + 2, nullptr, nullptr, 0u, nullptr, 0ull, {0ull, 0ull, 0ull, 0ull}, 0u};
-        unsigned grid1 = 0;
-        u32 nheavy = 0;                  // k-mers the level-2 scatter counts apart (find_heavy)
-        // (the per-bin slice ends need 4 more bytes of LDS per bin: plans above 1634 level-1 bins keep UNIFORM slices, mean-sized, no sample)
-        const bool uniform1 = scatter_lds(W, pl.P1, true) > 160 * 1024;
-        if (opt1 && scatter_lds(W, pl.P1, false) > 160 * 1024) opt1 = false;
-        if (opt1 && !from_reads) ctx->h_nvalid = nkeys_in;
-        if (opt1) {
-            grid1 = scatter_grid(ctx, W, pl.P1, nch1, !uniform1);
-            // a block's share of the input: it walks chunks blockIdx, blockIdx + grid, .. (equal chunks, the busiest block has ceil(nch/grid))
-            const u64 cpb = (nch1 + grid1 - 1) / grid1;
-            double share = (double)cpb / (double)nch1;
-            if (from_rec && ctx->rec_slice_end.size() > 1) {      // a launch per slice: the busiest block's chunks of every slice add up
-                share = 0.0;
-                u64 rb = 0;
-                for (size_t sl = 0; sl < ctx->rec_slice_end.size(); ++sl) {
-                    const u64 re = ctx->rec_slice_end[sl], nc = ctx->h_slice_chunk[sl + 1] - ctx->h_slice_chunk[sl];
-                    if (nc) share += (double)((nc + grid1 - 1) / grid1) / (double)nc * (double)(re - rb) / (double)ctx->rec_n;
-                    rb = re;
-                }
-            }
-            // ---- level-1 loads of this pass, per bin ("PartiInfo" before the spill): a positional sample -- the level-1 digit
-            // histogram of <= 1024 tiles spread over the source -- scaled to the pass.  Every bin's slices are sized from ITS load,
-            // so a bin that holds a repeat family (or poly-A) gets longer slices instead of overflowing the mean-sized ones.
-            // Records (multi-GPU receive side) have no histogram kernel: uniform loads.
-            const double pass_keys = (double)(ctx->h_nvalid / npass);
-            std::vector<double>& load = ctx->h_load;
-            load.assign(pl.P1, pass_keys / pl.P1);
-            ctx->h_seg_work = load;
-            std::vector<double>& spread = ctx->h_spread;
-            spread.assign(pl.P1, 0.0);
-            bool sampled = false;
-            // records (the multi-GPU receive side, the passes of a record-based multi-pass count): a positional sample of the records is
-            // expanded into a key array with pads (k_sk_sample_keys: SK_MAXN slots per candidate record) and sampled like any key array.
-            // Records that arrive in slices: the sample comes from the first slice (the slices are positional cuts of every sender's
-            // reads: alike), so only that slice has to have arrived.
-            const Key* d_keys_s = d_keys_in;             // the key array the sample kernels read
-            double smp_density = 1.0;                    // records: real keys per slot of the sample array (a level-1 tile is full, a sample tile is not)
-            bool rec_sample_ok = ctx->sentinel_ok;       // (the sample array is padded with the all-ones key, which the key-array kernels skip: only when it is no k-mer of this k)
-            u64 rec_units = 0;
-            if constexpr (W <= 2) {
-              if (from_rec && !ctx->tune.no_sample && !uniform1) {
-                const u64 nrec_s = ctx->rec_slice_end.size() > 1 ? ctx->rec_slice_end[0] : ctx->rec_n;
-                const u64 NR = RecTile<W>::NR;
-                const u64 nchk_all = (nrec_s + NR - 1) / NR;
-                const u64 nchk = std::min<u64>(nchk_all, 256);
-                if (nchk == 0) rec_sample_ok = false;
-                else {
-                    { const int e = rec_gate_upto(ctx, 1); if (e) return e; }
-                    std::vector<u64>& cbeg = ctx->h_cbeg;        // (the context's: it outlives the asynchronous copy below; the next use is behind this pass's next synchronisation)
-                    cbeg.resize(nchk);
-                    for (u64 i = 0; i < nchk; ++i) cbeg[i] = (i * nchk_all / nchk) * NR;
-                    rec_units = nchk * NR * SK_MAXN;
-                    CK(ctx->smp_keys.ensure(rec_units * sizeof(Key) + nchk * 8 + 64));
-                    u64* d_cbeg = reinterpret_cast<u64*>(ctx->smp_keys.as<char>() + rec_units * sizeof(Key));
-                    CK(hipMemcpyAsync(d_cbeg, cbeg.data(), nchk * 8, hipMemcpyHostToDevice, ctx->stream));
-                    hipLaunchKernelGGL(k_sk_sample_keys<W>, dim3((unsigned)nchk), dim3(SKX_NT), 0, ctx->stream, ctx->rec_src, ctx->rec_n, ctx->sk_sp.R, (int)ctx->cfg.kmer_size,
-                                       (const u64*)d_cbeg, (u32)NR, ctx->smp_keys.as<Key>());
-                    CKL("k_sk_sample_keys");
-                    d_keys_s = ctx->smp_keys.as<Key>();
-                }
-              }
-            }
-            const bool smp_rec = from_rec && rec_units != 0;
-            if ((!from_rec || smp_rec) && rec_sample_ok && !ctx->tune.no_sample && !uniform1) {
-                const u64 units = from_reads ? nwords : smp_rec ? rec_units : nkeys_in, tile = from_reads ? Tile<W>::WORDS : Tile<W>::KEYS;
-                const u64 ntiles = std::max<u64>(1, (units + tile - 1) / tile);
-                const u64 nts = std::min<u64>(ntiles, 1024);
-                ctx->h_descs_s.resize(nts);
-                for (u64 i = 0; i < nts; ++i) {
-                    const u64 t = i * ntiles / nts;
-                    ChunkDesc d; d.begin = t * tile; d.end = std::min<u64>(units, (t + 1) * tile); d.flat_base = (u32)i; d.stride = (u32)nts;
-                    ctx->h_descs_s[i] = d;
-                }
-                const u64 Ms = (u64)pl.P1 * nts;
-                CK(ctx->smp_descs.ensure(nts * sizeof(ChunkDesc)));
-                CK(ctx->smp_mat.ensure((Ms + 1) * 4 + (size_t)pl.P1 * 16));
-                CK(hipMemcpyAsync(ctx->smp_descs.p, ctx->h_descs_s.data(), nts * sizeof(ChunkDesc), hipMemcpyHostToDevice, ctx->stream));
-                ctx->h_sc[SC_NCH_S] = (u32)nts;
-                CK(hipMemcpyAsync(sc + SC_NCH_S, &ctx->h_sc[SC_NCH_S], 4, hipMemcpyHostToDevice, ctx->stream));
-                int e;
-                if (from_reads) e = launch_hist<W, 0>(ctx, nullptr, ctx->smp_descs.as<ChunkDesc>(), sc + SC_NCH_S, nts, ctx->smp_mat.as<u32>(), pl.d1, pl.P1);
-                else e = launch_hist<W, 1>(ctx, d_keys_s, ctx->smp_descs.as<ChunkDesc>(), sc + SC_NCH_S, nts, ctx->smp_mat.as<u32>(), pl.d1, pl.P1);
-                if (e) return e;
-                u64* mom = reinterpret_cast<u64*>(ctx->smp_mat.as<u32>() + ((Ms + 2) & ~(u64)1));
-                hipLaunchKernelGGL(k_bin_moments, dim3((pl.P1 + 3) / 4), dim3(256), 0, ctx->stream, (const u32*)ctx->smp_mat.as<u32>(), (u32)nts, pl.P1, mom);
-                CKL("k_bin_moments");
-                ctx->h_mom.resize((size_t)pl.P1 * 2);
-                {
-                    void* lz = landing(ctx, (size_t)pl.P1 * 16);
-                    CK(hipMemcpyAsync(lz ? lz : (void*)ctx->h_mom.data(), mom, (size_t)pl.P1 * 16, hipMemcpyDeviceToHost, ctx->stream));
-                    CK(hipStreamSynchronize(ctx->stream));
-                    if (lz) std::memcpy(ctx->h_mom.data(), lz, (size_t)pl.P1 * 16);
-                }
-                u64 stot = 0;
-                for (u32 b = 0; b < pl.P1; ++b) stot += ctx->h_mom[2 * b];
-                if (stot >= (u64)pl.P1 * 64) {        // enough sampled keys to say something per bin
-                    // one pass from the reads: scaled so that the loads add up to the exact number of valid k-mers; otherwise by position
-                    const double scale = (from_reads && npass > 1) ? (double)ntiles / (double)nts : pass_keys / (double)stot;
-                    // tiles a block walks (the busiest one), and how far a bin's keys on those tiles may be from share * load:
-                    //   the block's own spread: 5 sigma of the sum over its tiles of the per-tile count (variance measured on the sample),
-                    //   the estimate's error  : 4 sigma of the sampled sum, scaled to the block's share
-                    // (records: a level-1 tile is full, a tile of the sample array holds smp_density of its slots: the block walks
-                    //  pass_keys * share / KEYS full tiles, each with 1 / density times the variance of a sample tile)
-                    if (smp_rec) smp_density = std::max(0.05, (double)stot / ((double)nts * (double)Tile<W>::KEYS));
-                    const double tiles_per_block = smp_rec ? pass_keys * share / (double)Tile<W>::KEYS : (double)ntiles * share;
-                    for (u32 b = 0; b < pl.P1; ++b) {
-                        const double sum = (double)ctx->h_mom[2 * b], sq = (double)ctx->h_mom[2 * b + 1];
-                        const double mean = sum / (double)nts, var = std::max(mean, sq / (double)nts - mean * mean);      // (at least Poisson)
-                        load[b] = sum * scale;
-                        spread[b] = 5.0 * std::sqrt(tiles_per_block * var / smp_density) + 4.0 * std::sqrt((double)nts * var) * scale * share;
-                    }
-                    ctx->h_seg_work = load;
-                    sampled = true;
-                }
-                // ---- a k-mer that alone is a large share of a level-1 bin (poly-A reads, a satellite: millions of occurrences):
-                // its bin stands far above the others.  Collect sampled keys of those bins, find the dominant k-mer(s) on the host
-                // and let the level-1 scatter count them apart (k_scatter<.., HEAVY>) -- everything lighter is what the region
-                // chains are for.
-                if constexpr (W <= 2) {
-                    if (sampled && opt_cap && !ctx->tune.no_heavy) { const int e2 = find_heavy<W>(ctx, from_reads, d_keys_s, (u32)nts, pl, &nheavy); if (e2) return e2; }
-                }
-                ctx->mark("sample1");
-            }
-            // slice of bin b = the busiest block's share of its load + the spread above + 1 % + 64 keys; without a sample: + 6 % + 160
-            // (what uniform reads need), in whole groups of 8 keys
-            ctx->h_boff.resize(pl.P1 + 1);
-            u64 area = 0;
-            if (uniform1) o1.uslice = 1u;          // (set below)
-            for (u32 b = 0; b < pl.P1; ++b) {
-                double sl = load[b] * share;
-                // (records: the senders' zero-length pad records sit at the ends of their slices, so a level-1 chunk holds anything from
-                //  no pads to ~10 % -- a block that walks only a few chunks does not average that out: more room there)
-                const double few = (from_rec && share * (double)nch1 < 16.0) ? 0.08 : 0.0;
-                sl += sampled ? spread[b] + sl * 0.01 + 64.0 : sl * (0.06 + few) + 160.0;
-                u64 slice = ((u64)sl + 8) & ~7ull;
-                if (uniform1) o1.uslice = (u32)slice;
-                if (ctx->tune.opt_slice) slice = ctx->tune.opt_slice;                                        // experiments / tests
-                ctx->h_boff[b] = (u32)std::min<u64>(area, 0xFFFFFFFFull); area += slice;
-            }
-            ctx->h_boff[pl.P1] = (u32)std::min<u64>(area, 0xFFFFFFFFull);
-            const u64 tail = 2 * Tile<W>::KEYS;                         // the dump zone behind the last slice (a tile's keys of a bin that outgrew its slice land there)
-            const u64 cells = (u64)pl.P1 * grid1;
-            if (ctx->tune.verbose) fprintf(stderr, "[dskgpu] pass %u/%u: P1 %u P2 %u, %u level-1 blocks, area %llu keys per block (%.2f GB of slices), sampled %d, keys %llu, %u chunks, share %.6f, %zu slices\n", pass, npass, pl.P1, pl.P2, grid1,
-                                           (unsigned long long)area, (double)area * grid1 * sizeof(Key) * 1e-9, (int)sampled, (unsigned long long)ctx->h_nvalid, nch1, share, ctx->rec_slice_end.size());
-            if (area < 8 || area * grid1 + tail >= 0xFFFF0000ull) opt1 = false;
-            else {
-                o1.area = (u32)area; o1.dump = (u32)(area * grid1);
-                CK(ctx->boff.ensure(((size_t)pl.P1 + 1) * 4));
-                CK(hipMemcpyAsync(ctx->boff.p, ctx->h_boff.data(), ((size_t)pl.P1 + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-                o1.boff = ctx->boff.as<u32>();
-                CK(ctx->mat1.ensure((cells + 1) * 4));                      // here: keys per (bin, block) slice
-                o1.fill = ctx->mat1.as<u32>();
-                if (grid1 + 1 > SLICED_MAX) opt1 = false;                   // the level-2 loader keeps the slice bounds in LDS
-                CK(ctx->bufA.ensure((area * grid1 + tail + 1) * sizeof(Key)));
-            }
-        }
-        if (from_rec && !opt1) { int e = records_to_keys(); if (e) return e; }
-        const u64 M1 = (u64)pl.P1 * nch1;
-        u32* h_sc = ctx->h_sc;
-        std::memset(h_sc, 0, sizeof(ctx->h_sc));
-        h_sc[SC_NCH1] = nch1; h_sc[SC_MLEN1] = (u32)M1; h_sc[SC_F] = pl.F;
-        if (opt1) h_sc[SC_NCH2] = pl.P1;                       // level-2 chunks = the level-1 bin regions
-        h_sc[SC_WORK2] = (u32)std::min<u64>(pl.P1, (u64)ctx->num_cu);   // work counter of the segment-owned level-2 scatter: first segment not taken in the first round
-        // (with them: histogram / distinct counters of THIS pass attempt -- a table-overflow retry must not double count)
-        {
-            static_assert(sizeof(ctx->h_sc) == sizeof(ScalarSet), "scalar block");
-            ScalarSet hs; std::memcpy(hs.v, h_sc, sizeof hs.v);
-            const u32 nh = ctx->cfg.histo_max + 1;
-            u64 nzero = 0;
-            if (pl.levels == 2 && opt_cap) { nzero = nregions + 1; CK(ctx->mat2.ensure((size_t)nzero * 4)); }      // level 2's keys per region (home regions, then the extension pool)
-            const u64 work = std::max<u64>(nh, nzero);
-            hipLaunchKernelGGL(k_setup_pass, dim3((unsigned)std::min<u64>(1024, (work + 255) / 256)), dim3(256), 0, ctx->stream, sc, hs, ctx->ghist.as<u64>(), nh, ctx->gstats.as<u64>(), 4u,
-                               nzero ? ctx->mat2.as<u32>() : (u32*)nullptr, nzero);
-            CKL("k_setup_pass");
-        }
-        ctx->mark("setup");
-        int rc;
-        const ChunkDesc* dd1 = ctx->descs1.as<ChunkDesc>();
-        if (opt1) {
-            if constexpr (W <= 2) { if (nheavy) { o1.hv_keys = ctx->hv_buf.as<u64>() + HvLayout<W>::keys; o1.hv_cnt = reinterpret_cast<unsigned long long*>(ctx->hv_buf.as<u64>() + HvLayout<W>::counts); } }
-            if (from_rec && ctx->rec_slice_end.size() > 1) {
-                // the records arrive in slices: one launch per slice, each behind the arrival of its slice (rec_gate), the blocks'
-                // write cursors parked in between
-                const size_t S = ctx->rec_slice_end.size();
-                CK(ctx->cur_state.ensure((size_t)grid1 * pl.P1 * 4));
-                o1.cur_state = ctx->cur_state.as<u32>();
-                rc = DSKGPU_OK;
-                for (size_t sl = 0; sl < S && rc == DSKGPU_OK; ++sl) {
-                    if ((rc = rec_gate_upto(ctx, (u32)sl + 1))) break;
-                    o1.g0 = ctx->h_slice_chunk[sl]; o1.gn = ctx->h_slice_chunk[sl + 1] - ctx->h_slice_chunk[sl];
-                    o1.resume = sl > 0 ? 1u : 0u; o1.last = sl + 1 == S ? 1u : 0u;
-                    rc = launch_scatter_rec_h<W>(ctx, nheavy != 0, dd1, sc + SC_NCH1, nch1, ctx->bufA.as<Key>(), pl.d1, pl.P1, o1);
-                }
-            }
-            else if (from_rec) { if (!(rc = rec_gate_all(ctx))) rc = launch_scatter_rec_h<W>(ctx, nheavy != 0, dd1, sc + SC_NCH1, nch1, ctx->bufA.as<Key>(), pl.d1, pl.P1, o1); }
-            else if (nheavy && from_reads) {
-                if constexpr (W <= 2) rc = npass > 1 ? launch_scatter_m<W, 0, 3, true, true>(ctx, nullptr, dd1, sc + SC_NCH1, nch1, nullptr, ctx->bufA.as<Key>(), pl.d1, pl.P1, o1)
-                                                     : launch_scatter_m<W, 0, 1, true, true>(ctx, nullptr, dd1, sc + SC_NCH1, nch1, nullptr, ctx->bufA.as<Key>(), pl.d1, pl.P1, o1);
-                else rc = DSKGPU_E_STATE;
-            } else if (nheavy) {
-                if constexpr (W <= 2) rc = npass > 1 ? launch_scatter_m<W, 1, 3, true, true>(ctx, d_keys_in, dd1, sc + SC_NCH1, nch1, nullptr, ctx->bufA.as<Key>(), pl.d1, pl.P1, o1)
-                                                     : launch_scatter_m<W, 1, 1, true, true>(ctx, d_keys_in, dd1, sc + SC_NCH1, nch1, nullptr, ctx->bufA.as<Key>(), pl.d1, pl.P1, o1);
-                else rc = DSKGPU_E_STATE;
-            }
-            else if (from_reads && npass > 1) rc = launch_scatter_m<W, 0, 3, true>(ctx, nullptr, dd1, sc + SC_NCH1, nch1, nullptr, ctx->bufA.as<Key>(), pl.d1, pl.P1, o1);
-            else if (from_reads) rc = launch_scatter_m<W, 0, 1, true>(ctx, nullptr, dd1, sc + SC_NCH1, nch1, nullptr, ctx->bufA.as<Key>(), pl.d1, pl.P1, o1);
-            else if (npass > 1) {
-                if constexpr (W <= 2) rc = launch_scatter_m<W, 1, 3, true>(ctx, d_keys_in, dd1, sc + SC_NCH1, nch1, nullptr, ctx->bufA.as<Key>(), pl.d1, pl.P1, o1);
-                else rc = DSKGPU_E_STATE;
-            }
-            else rc = launch_scatter_m<W, 1, 1, true>(ctx, d_keys_in, dd1, sc + SC_NCH1, nch1, nullptr, ctx->bufA.as<Key>(), pl.d1, pl.P1, o1);
-            if (rc) return rc;
-            ctx->mark("scatter1");
-        } else {
-            CK(ctx->mat1.ensure((M1 + 1) * 4));
-            if (from_reads) rc = launch_hist<W, 0>(ctx, nullptr, dd1, sc + SC_NCH1, nch1, ctx->mat1.as<u32>(), pl.d1, pl.P1);
-            else rc = launch_hist<W, 1>(ctx, d_keys_in, dd1, sc + SC_NCH1, nch1, ctx->mat1.as<u32>(), pl.d1, pl.P1);
-            if (rc) return rc;
-            ctx->mark("hist1");
-            if ((rc = run_scan(ctx, ctx->mat1.as<u32>(), sc + SC_MLEN1, M1))) return rc;
-            ctx->mark("scan1");
-            if (npass > 1) {      // the pass must fit the buffers sized for it (skewed inputs can overfill one pass)
-                CK(hipMemcpyAsync(&ctx->h_back[2], ctx->mat1.as<u32>() + M1, 4, hipMemcpyDeviceToHost, ctx->stream));
-                CK(hipStreamSynchronize(ctx->stream));
-                if ((u64)ctx->h_back[2] > cap) { ctx->resolve_marks(); return PASS_TOO_BIG; }
-            }
-            if (from_reads) rc = launch_scatter<W, 0>(ctx, nullptr, dd1, sc + SC_NCH1, nch1, ctx->mat1.as<u32>(), ctx->bufA.as<Key>(), pl.d1, pl.P1);
-            else rc = launch_scatter<W, 1>(ctx, d_keys_in, dd1, sc + SC_NCH1, nch1, ctx->mat1.as<u32>(), ctx->bufA.as<Key>(), pl.d1, pl.P1);
-            if (rc) return rc;
-            ctx->mark("scatter1");
-        }
-        Key* fkeys = ctx->bufA.as<Key>();
-        DevBuf* scratch = &ctx->bufB;
-        CK(ctx->fstart.ensure(((size_t)pl.F + 2) * 4));
-        CK(ctx->nsolid.ensure(((size_t)pl.F + 2) * 4));
-        // ---------------- level 2
-        // One-word keys take the segment-owned scatter (k_scatter_al<.., OPT>): no histogram pass, every
-        // sub-partition gets a fixed region of OPT_CAP keys; a region that overflows (heavy repeats) sends the
-        // level back through the exact histogram + scan path, and the context remembers it for these reads.
-        if (pl.levels == 2 && opt_cap) {
-            CK(ctx->bufB.ensure((nregions * opt_cap + ATile<W>::KEYS + 16) * sizeof(Key)));
-            CK(ctx->descs2.ensure(((size_t)pl.P1 * 2 + 1) * sizeof(ChunkDesc)));
-            CK(ctx->seg.ensure((size_t)pl.P1 * sizeof(SegInfo)));
-            CK(ctx->mat2.ensure(((size_t)nregions + 1) * 4));                  // here: keys per region (home regions, then the extension pool)
-            CK(ctx->chain_next.ensure(((size_t)nregions + 1 + max_ext + 1) * 4));   // links (only read where subcnt has its chain bit set), then the list of chained sub-partitions
-            // (zeroed by k_setup_pass)
-            if (opt1) {      // segments = the level-1 bin regions (slices + sentinel tails)
-                ctx->h_descs2.resize(pl.P1);
-                // heaviest segments first (the kernel hands them out by a work counter): a segment that holds a repeat family takes a
-                // block longer than the others, so it must not be the last thing a block starts
-                std::vector<u32> order(pl.P1);
-                for (u32 sgm = 0; sgm < pl.P1; ++sgm) order[sgm] = sgm;
-                // (in steps of 5 % of the mean, stable: the segments of uniform reads keep their natural order, neighbours in memory run together)
-                double mean_work = 0.0; for (double w : ctx->h_seg_work) mean_work += w; mean_work = std::max(1.0, mean_work / pl.P1);
-                auto wclass = [&](u32 a) { return (long long)(ctx->h_seg_work[a] / (0.05 * mean_work)); };
-                std::stable_sort(order.begin(), order.end(), [&](u32 a, u32 b) { return wclass(a) > wclass(b); });
-                for (u32 i = 0; i < pl.P1; ++i) {
-                    const u32 sgm = order[i];
-                    ChunkDesc d; d.begin = ctx->h_boff[sgm]; d.end = ctx->h_boff[sgm + 1]; d.flat_base = sgm * pl.P2; d.stride = 1;   // slice i of the segment: + i * area
-                    ctx->h_descs2[i] = d;
-                }
-                CK(hipMemcpyAsync(ctx->descs2.p, ctx->h_descs2.data(), (size_t)pl.P1 * sizeof(ChunkDesc), hipMemcpyHostToDevice, ctx->stream));
-            } else {
-                hipLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, ctx->stream, ctx->mat1.as<u32>(), nch1, pl.P1, 0x7FFFFFFFu, pl.P2,
-                                   ctx->seg.as<SegInfo>(), ctx->descs2.as<ChunkDesc>(), sc + SC_NCH2, sc + SC_MLEN2, 1u);
-                CKL("k_plan");
-            }
-            ctx->mark("plan2");
-            OptSpec os{opt_cap, ctx->mat2.as<u32>(), sc + SC_OVF2, opt1 ? o1.fill : nullptr, 0u, grid1, (u64)o1.area,
-                       pl.F, max_ext, ctx->chain_next.as<u32>(), sc + SC_EXT, ctx->chain_next.as<u32>() + nregions + 1, sc + SC_NCHAINED,
-                       sc + SC_WORK2, nullptr};
-            if (ctx->tune.verbose && opt1) { CK(ctx->dbg.ensure((size_t)pl.P1 * 24)); os.dbg = ctx->dbg.as<unsigned long long>(); }
-            if (opt1) rc = launch_scatter_al<W, 2, true, true>(ctx, ctx->bufA.as<Key>(), ctx->descs2.as<ChunkDesc>(), sc + SC_NCH2, (u64)pl.P1 * 2, nullptr,
-                                                               ctx->bufB.as<Key>(), pl.d2, pl.P2, os);
-            else rc = launch_scatter_al<W, 2, true, false>(ctx, ctx->bufA.as<Key>(), ctx->descs2.as<ChunkDesc>(), sc + SC_NCH2, (u64)pl.P1 * 2, nullptr,
-                                                           ctx->bufB.as<Key>(), pl.d2, pl.P2, os);
-            if (rc) return rc;
-            ctx->mark("scatter2");
-            if (ctx->tune.verbose && opt1) {      // per-segment times of the level-2 scatter, in hand-out order
-                std::vector<unsigned long long> t((size_t)pl.P1 * 3);
-                CK(hipMemcpyAsync(t.data(), ctx->dbg.p, t.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-                CK(hipStreamSynchronize(ctx->stream));
-                unsigned long long t0 = ~0ull, t1 = 0; for (u32 i = 0; i < pl.P1; ++i) { t0 = std::min(t0, t[3 * i]); t1 = std::max(t1, t[3 * i + 1]); }
-                fprintf(stderr, "[dskgpu] level 2: %u segments, %.3f ms first start -> last end\n", pl.P1, (t1 - t0) * 1e-5);
-                for (u32 i = 0; i < pl.P1; ++i)
-                    if (i < 6 || i + 3 >= pl.P1 || t[3 * i + 1] + 20000 > t1)
-                        fprintf(stderr, "[dskgpu]   desc %u (segment %u, load %.0f) block %llu: %.3f .. %.3f ms\n", i, (u32)(ctx->h_descs2[i].flat_base / pl.P2),
-                                ctx->h_load[ctx->h_descs2[i].flat_base / pl.P2], t[3 * i + 2], (t[3 * i] - t0) * 1e-5, (t[3 * i + 1] - t0) * 1e-5);
-            }
-            fkeys = ctx->bufB.as<Key>();
-            scratch = &ctx->bufA;
-        } else if (pl.levels == 2) {
-            const u64 max_chunks2 = cap / CH2 + pl.P1 + 1;
-            const u64 M2 = max_chunks2 * pl.P2;
-            if (M2 >= 0xFFFFFFFFull) return fail(ctx, DSKGPU_E_ARG, "level-2 matrix too large");
-            CK(ctx->descs2.ensure(max_chunks2 * sizeof(ChunkDesc)));
-            CK(ctx->seg.ensure((size_t)pl.P1 * sizeof(SegInfo)));
-            CK(ctx->mat2.ensure((M2 + 1) * 4));
-            hipLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, ctx->stream, ctx->mat1.as<u32>(), nch1, pl.P1, CH2, pl.P2,
-                               ctx->seg.as<SegInfo>(), ctx->descs2.as<ChunkDesc>(), sc + SC_NCH2, sc + SC_MLEN2, 0u);
-            CKL("k_plan");
-            ctx->mark("plan2");
-            const ChunkDesc* dd2 = ctx->descs2.as<ChunkDesc>();
-            if ((rc = launch_hist<W, 1>(ctx, ctx->bufA.as<Key>(), dd2, sc + SC_NCH2, max_chunks2, ctx->mat2.as<u32>(), pl.d2, pl.P2))) return rc;
-            ctx->mark("hist2");
-            if ((rc = run_scan(ctx, ctx->mat2.as<u32>(), sc + SC_MLEN2, M2))) return rc;
-            ctx->mark("scan2");
-            if ((rc = launch_scatter<W, 1>(ctx, ctx->bufA.as<Key>(), dd2, sc + SC_NCH2, max_chunks2, ctx->mat2.as<u32>(), ctx->bufB.as<Key>(), pl.d2, pl.P2))) return rc;
-            ctx->mark("scatter2");
-            fkeys = ctx->bufB.as<Key>();
-            scratch = &ctx->bufA;
-            hipLaunchKernelGGL(k_final_offsets, dim3((pl.F + 256) / 256), dim3(256), 0, ctx->stream, ctx->mat2.as<u32>(),
-                               ctx->seg.as<SegInfo>(), pl.P2, 0u, sc + SC_MLEN2, ctx->fstart.as<u32>(), pl.F);
-        } else {
-            hipLaunchKernelGGL(k_final_offsets, dim3((pl.F + 256) / 256), dim3(256), 0, ctx->stream, ctx->mat1.as<u32>(),
-                               (const SegInfo*)nullptr, pl.P1, nch1, sc + SC_MLEN1, ctx->fstart.as<u32>(), pl.F);
-        }
-        CKL("k_final_offsets");
-        ctx->mark("offsets");
-        // ---------------- count: one-word keys write solid rows in place (+ abundance into the
-        // free ping-pong buffer); two-word keys write rows into the free buffer (+ abund2)
-        CountParams cp;
-        cp.F = pl.F;
-        cp.maxload = W == 1 ? CNT_MAXLOAD : C2_MAXLOAD;
-        if (ctx->tune.table_maxload) cp.maxload = std::min<u32>(cp.maxload, ctx->tune.table_maxload);
-        cp.amin = ctx->cfg.abundance_min; cp.amax = ctx->cfg.abundance_max; cp.histo_max = ctx->cfg.histo_max;
-        cp.cap = opt_cap; cp.subcnt = opt_cap ? ctx->mat2.as<u32>() : nullptr;
-        const unsigned cgrid = (unsigned)std::min<u64>(pl.F, (u64)ctx->num_cu * 2);
-        Key* solid_keys = W == 1 ? fkeys : scratch->as<Key>();
-        u32* solid_ab = W == 1 ? scratch->as<u32>() : ctx->abund2.as<u32>();
-        // the count stage as one unit: two-word keys may run it twice (k_count2v3, then -- when its verification bit went up -- k_count_mw:
-        // the keys are still there, two-word rows go to the free buffer)
-        auto count_stage = [&]() -> int {
-            launch_count<W>(ctx, cgrid, fkeys, solid_keys, solid_ab, sc + SC_OVERFLOW, cp);
-            CKL("k_count");
-            if constexpr (W == 2) {
-                if (opt_cap && max_ext) {
-                    hipLaunchKernelGGL(k_count_chained_mw<2>, dim3((unsigned)std::min<u64>(max_ext, (u64)ctx->num_cu * 2)), dim3(CNT_NT), 0, ctx->stream, (const Key*)fkeys, solid_keys, solid_ab,
-                                       ctx->nsolid.as<u32>(), ctx->ghist.as<u64>(), ctx->gstats.as<u64>(), sc + SC_OVERFLOW, cp, (const u32*)cp.subcnt,
-                                       (const u32*)ctx->chain_next.as<u32>(), (const u32*)(ctx->chain_next.as<u32>() + nregions + 1), (const u32*)(sc + SC_NCHAINED), max_ext);
-                    CKL("k_count_chained_mw");
-                }
-            }
-            if constexpr (W == 1) {
-                if (opt_cap && max_ext) {      // the sub-partitions that went on in extension regions (none on repeat-free reads: the blocks leave at once)
-                    hipLaunchKernelGGL(k_count_chained, dim3((unsigned)std::min<u64>(max_ext, (u64)ctx->num_cu * 2)), dim3(CNT_NT), 0, ctx->stream, fkeys, solid_keys, solid_ab,
-                                       ctx->nsolid.as<u32>(), ctx->ghist.as<u64>(), ctx->gstats.as<u64>(), sc + SC_OVERFLOW, cp, (const u32*)cp.subcnt,
-                                       (const u32*)ctx->chain_next.as<u32>(), (const u32*)(ctx->chain_next.as<u32>() + nregions + 1), (const u32*)(sc + SC_NCHAINED), max_ext);
-                    CKL("k_count_chained");
-                }
-            }
-            if constexpr (W <= 2) {
-              if (nheavy) {      // the k-mers the level-1 scatter counted apart: histogram, distinct count, rows (appended behind the compacted ones below)
-                const u32 slots = HV_KEYS;
-                u64* hvb = ctx->hv_buf.as<u64>();
-                hipLaunchKernelGGL(k_heavy_rows<W>, dim3((slots + 255) / 256), dim3(256), 0, ctx->stream, reinterpret_cast<const Key*>(hvb + HvLayout<W>::keys),
-                                   (const unsigned long long*)(hvb + HvLayout<W>::counts), slots, cp.amin, cp.amax, cp.histo_max, ctx->ghist.as<u64>(), ctx->gstats.as<u64>(),
-                                   hvb + HvLayout<W>::rows, reinterpret_cast<u32*>(hvb + HvLayout<W>::ab));
-                CKL("k_heavy_rows");
-              }
-            }
-            return DSKGPU_OK;
-        };
-        // count, scan of the solid rows per sub-partition, sizes back to the host (one sync)
-        auto count_and_sizes = [&]() -> int {
-            if (int e = count_stage()) return e;
-            ctx->mark("count");
-            if (int e = run_scan(ctx, ctx->nsolid.as<u32>(), sc + SC_F, pl.F)) return e;
-            ctx->mark("scan_solid");
-            // (k-mers of the pass: the last sub-partition offset, or -- fixed-capacity regions -- the level-1 total; with block-owned slices
-            //  the scatter's own count in gstats[2])
-            CK(ctx->back_dev.ensure(16 * 8));
-            if (!ctx->back_host) CK(hipHostMalloc(reinterpret_cast<void**>(&ctx->back_host), 16 * 8, hipHostMallocDefault));
-            const u32* nkp = opt1 ? nullptr : (opt_cap ? ctx->mat1.as<u32>() + M1 : ctx->fstart.as<u32>() + pl.F);
-            hipLaunchKernelGGL(k_gather_back, dim3(1), dim3(64), 0, ctx->stream, (const u32*)sc, (const u32*)(ctx->nsolid.as<u32>() + pl.F), nkp,
-                               (const u64*)ctx->gstats.as<u64>(), ctx->back_dev.as<u64>());
-            CKL("k_gather_back");
-            CK(hipMemcpyAsync(ctx->back_host, ctx->back_dev.p, 10 * 8, hipMemcpyDeviceToHost, ctx->stream));
-            CK(hipStreamSynchronize(ctx->stream));
-            const u64* bh = ctx->back_host;
-            ctx->h_back[0] = (u32)bh[0]; ctx->h_back[1] = (u32)bh[1]; if (!opt1) ctx->h_back[2] = (u32)bh[2];
-            ctx->h_ovf2 = (u32)bh[3]; ctx->h_ovf1 = (u32)bh[4]; ctx->h_ext = (u32)bh[5];
-            for (int x = 0; x < 4; ++x) ctx->h_stats[x] = bh[6 + x];
-            return DSKGPU_OK;
-        };
-        if constexpr (W == 2) CK(hipMemcpyAsync(ctx->gstats.as<u64>() + 3, ctx->gstats.as<u64>() + 2, 8, hipMemcpyDeviceToDevice, ctx->stream));      // (the keys level 1 placed, before k_heavy_rows adds to them: see below)
-        if ((rc = count_and_sizes())) return rc;
-        if constexpr (W == 2) {
-            // k_count2v3 keys its table by the mixed top word alone and checks every key's low word afterwards.  Two different k-mers of the pass with
-            // the same top word (birthday bound of a 64-bit hash: n^2 / 2^65 -- 0.5 % of the runs at 4 * 10^8 distinct k-mers), or one whose top word
-            // is the empty-slot value: the COUNT STAGE runs again with the index-table kernel (the keys are untouched: two-word rows go to the other
-            // buffer), and the rest of the reads' passes use that kernel too.  Tests craft both cases.
-            if ((ctx->h_back[0] & (CNT_OVF_VERIFY | CNT_OVF_SENTINEL)) && !((opt_cap && ctx->h_ovf2) || (opt1 && ctx->h_ovf1))) {
-                if (ctx->tune.verbose) fprintf(stderr, "[dskgpu] pass %u/%u: the top-word table met k-mers it cannot tell apart (flags %u): counting again with k_count_mw\n", pass, npass, ctx->h_back[0]);
-                ctx->mw_v3_off = true;
-                ctx->stats.n_retries += 1;
-                CK(hipMemsetAsync(ctx->ghist.p, 0, ((size_t)ctx->cfg.histo_max + 1) * 8, ctx->stream));
-                CK(hipMemsetAsync(ctx->gstats.p, 0, 2 * 8, ctx->stream));
-                CK(hipMemcpyAsync(ctx->gstats.as<u64>() + 2, ctx->gstats.as<u64>() + 3, 8, hipMemcpyDeviceToDevice, ctx->stream));
-                CK(hipMemsetAsync(sc + SC_OVERFLOW, 0, 4, ctx->stream));
-                if ((rc = count_and_sizes())) return rc;
-            }
-        }
-        const u32 h_ovf = ctx->h_back[0], h_nsolid = ctx->h_back[1], h_nk = opt1 ? (u32)ctx->h_stats[2] : ctx->h_back[2];
-        if ((opt_cap && ctx->h_ovf2) || (opt1 && ctx->h_ovf1)) {       // a slice / region overflowed: repeat this attempt with exact offsets
+    KeySource<W> src{from_reads, !from_reads && d_keys_in == nullptr, d_keys_in, nkeys_in, nwords};
+    const u64 nvalid = from_reads ? ctx->h_nvalid : nkeys_in;
+    int extra_bits = 0, table_retries = 0;
+    for (;;) {
+        PassState<W> ps{src, pass, npass, cap, nvalid, ctx->scalars.as<u32>()};
+        int e;
+        if ((e = pass_plan<W>(ctx, ps, extra_bits)) || (e = pass_layout1<W>(ctx, ps)) || (e = pass_scatter1<W>(ctx, ps))) return e;
+        if (ps.too_big) { ctx->resolve_marks(); res->too_big = true; res->keys_seen = ps.nkeys; return DSKGPU_OK; }
+        if ((e = pass_scatter2<W>(ctx, ps)) || (e = pass_count<W>(ctx, ps))) return e;
+        const bool ovf1 = ps.opt1 && ps.ovf1, ovf2 = ps.opt_cap && ps.ovf2;
+        if (ovf1 || ovf2) {      // a slice / region overflowed: the attempt again with exact offsets (no table retry)
             ctx->resolve_marks();
-            if (ctx->tune.verbose) fprintf(stderr, "[dskgpu] pass %u/%u: %s overflowed: the exact path takes over\n", pass, npass, (opt1 && ctx->h_ovf1) ? "a level-1 slice" : "the level-2 extension pool");
-            if (opt1 && ctx->h_ovf1) ctx->opt1_off = true;
+            if (ctx->tune.verbose) fprintf(stderr, "[dskgpu] pass %u/%u: %s overflowed: the exact path takes over\n", pass, npass, ovf1 ? "a level-1 slice" : "the level-2 extension pool");
+            if (ovf1) ctx->opt1_off = true;
             else { ctx->opt2_off = true; ctx->opt1_off = true; }     // the exact level 2 cannot read sentinel-padded slices
             ctx->stats.n_retries += 1;
             ctx->mark("start");
-            --attempt;
             continue;
         }
-        if (h_ovf & 1u) {
+        if (ps.flags & 1u) {     // a count table overflowed: a finer partition
             ctx->resolve_marks();
-            if (attempt >= 3) return fail(ctx, DSKGPU_E_OVERFLOW, "hash table overflow after 3 retries");
-            extra_bits += 1;
+            if (table_retries >= 3) return fail(ctx, DSKGPU_E_OVERFLOW, "hash table overflow after 3 retries");
+            ++table_retries; extra_bits += 1;
             ctx->stats.n_retries += 1;
             ctx->mark("start");
             continue;
         }
-        // ---------------- dense rows of this pass
-        const u64 nhs = nheavy ? ctx->h_stats[1] : 0;                    // solid rows of the k-mers counted apart
-        const u64 ns = h_nsolid + nhs;
-        // (a pass of a multi-pass job whose accumulators have room: the rows go there directly -- no copy of 0.7 GB per pass afterwards)
-        const bool to_sink = ctx->sink.active && ctx->sink.rows + ns + 1 <= ctx->sink.cap;
-        RowsOut ro{};
-        u32* rows_ab = nullptr;
-        if (to_sink) {
-            rows_ab = ctx->sink.ab + ctx->sink.rows;
-            for (int x = 0; x < W; ++x) ro.w[x] = ctx->sink.w[x] + ctx->sink.rows;
-            ctx->sink.took = true;
-        } else {
-            CK(ctx->out_ab.ensure((ns + 1) * 4));
-            rows_ab = ctx->out_ab.as<u32>();
-            for (int x = 0; x < W; ++x) { CK(ctx->out_w[x].ensure((ns + 1) * 8)); ro.w[x] = ctx->out_w[x].as<u64>(); }
-        }
-        if constexpr (W <= 2) {
-          if (nhs) {
-            for (int x = 0; x < W; ++x)
-                CK(hipMemcpyAsync(ro.w[x] + h_nsolid, ctx->hv_buf.as<u64>() + HvLayout<W>::rows + (size_t)x * HV_KEYS, nhs * 8, hipMemcpyDeviceToDevice, ctx->stream));
-            CK(hipMemcpyAsync(rows_ab + h_nsolid, ctx->hv_buf.as<u64>() + HvLayout<W>::ab, nhs * 4, hipMemcpyDeviceToDevice, ctx->stream));
-          }
-        }
-        ctx->stats.n_heavy += nheavy;
-        // One-word rows of a single pass that the hand-written MSD sort will order: its first step reads them where they lie (the regions /
-        // exact ranges of the count kernel + the few rows of the k-mers counted apart as a dense tail) -- no dense copy is made first
-        // (k_compact: 0.5 GB read + 0.5 GB written, 0.30 ms of a 14 ms step).  Several passes accumulate dense rows as before.
-        bool sparse_sort = false;
-        if constexpr (W == 1) {
-            const u64 rs_max = rs_max_rows(ctx);
-            sparse_sort = npass == 1 && ctx->job_passes == 1 && ns > 0 && ns <= rs_max && !(ctx->cfg.flags & DSKGPU_F_NO_SORT) &&
-                          !ctx->tune.rs_slab_rows && !ctx->bank_job.active;
-            if (sparse_sort) {
-                ctx->sp_rows.valid = true;
-                ctx->sp_rows.s = RsSparse{(const u64*)solid_keys, (const u32*)solid_ab, (const u32*)ctx->nsolid.as<u32>(), (const u32*)ctx->fstart.as<u32>(), opt_cap, pl.F, 0u};
-                ctx->sp_rows.n_sparse = h_nsolid;
-                ctx->sp_rows.n_tail = (u32)nhs;
-                ctx->sp_rows.tail_k = nhs ? ro.w[0] + h_nsolid : nullptr;        // (copied there above: dense, already un-mixed)
-                ctx->sp_rows.tail_v = nhs ? rows_ab + h_nsolid : nullptr;
-            }
-        }
-        if constexpr (W == 2) {      // (two-word rows: the same, through rowsort2.h's sparse step A -- sort_rows2_msd is what sort_rows picks under these conditions)
-            const u64 rs_max = rs_max_rows(ctx);
-            sparse_sort = npass == 1 && ctx->job_passes == 1 && ns > 0 && ns <= rs_max && !(ctx->cfg.flags & DSKGPU_F_NO_SORT) &&
-                          !ctx->tune.rs_slab_rows && !ctx->bank_job.active && 2u * ctx->cfg.kmer_size > 64u;
-            if (sparse_sort) {
-                ctx->sp_rows2.valid = true;
-                ctx->sp_rows2.s = Rs2Sparse{(const K2*)solid_keys, (const u32*)solid_ab, (const u32*)ctx->nsolid.as<u32>(), (const u32*)ctx->fstart.as<u32>(), opt_cap, pl.F, 0u};
-                ctx->sp_rows2.n_sparse = h_nsolid;
-                ctx->sp_rows2.n_tail = (u32)nhs;
-                ctx->sp_rows2.tail = nhs ? Rows2C{ro.w[1] + h_nsolid, ro.w[0] + h_nsolid, rows_ab + h_nsolid} : Rows2C{nullptr, nullptr, nullptr};
-            }
-        }
-        bool mp_part = false;
-        if constexpr (W <= 2) {      // DSKGPU_F_PARTITION_ORDER in a multi-pass count: the pass's rows ordered partition by partition on their way into the dense arrays
-            mp_part = !sparse_sort && ctx->job_passes > 1 && ctx->mp_part_ok && ns > 0 && h_nsolid < 0xFFFF0000ull && (W == 1 || 2u * ctx->cfg.kmer_size > 64u);
-            if (!sparse_sort && ctx->job_passes > 1 && ns > 0 && !mp_part) ctx->mp_part_ok = false;      // (one pass outside the scheme: the job keeps the global order)
-            if (mp_part) {
-                dskgpu_ctx::SparseRows spr{}; dskgpu_ctx::SparseRows2 spr2{};
-                if constexpr (W == 1) {
-                    spr.s = RsSparse{(const u64*)solid_keys, (const u32*)solid_ab, (const u32*)ctx->nsolid.as<u32>(), (const u32*)ctx->fstart.as<u32>(), opt_cap, pl.F, 0u};
-                    spr.n_sparse = h_nsolid; spr.n_tail = (u32)nhs; spr.tail_k = nhs ? ro.w[0] + h_nsolid : nullptr; spr.tail_v = nhs ? rows_ab + h_nsolid : nullptr;
-                } else {
-                    spr2.s = Rs2Sparse{(const K2*)solid_keys, (const u32*)solid_ab, (const u32*)ctx->nsolid.as<u32>(), (const u32*)ctx->fstart.as<u32>(), opt_cap, pl.F, 0u};
-                    spr2.n_sparse = h_nsolid; spr2.n_tail = (u32)nhs;
-                    spr2.tail = nhs ? Rows2C{ro.w[1] + h_nsolid, ro.w[0] + h_nsolid, rows_ab + h_nsolid} : Rows2C{nullptr, nullptr, nullptr};
-                }
-                const u32 np_est = part_sort_nparts(W, pl.F, h_nsolid, (u32)nhs);
-                if (ctx->mp_part_off.ensure_keep(((size_t)ctx->mp_off_used + np_est + 2) * 4, (size_t)ctx->mp_off_used * 4, ctx->stream)) return fail(ctx, DSKGPU_E_NOMEM, "partition offsets");
-                u32 np = 0;
-                const int prc = launch_part_sort(ctx, W, spr, spr2, ro.w[0], rows_ab, Rows2{W == 2 ? ro.w[1] : nullptr, ro.w[0], rows_ab},
-                                                 ctx->mp_part_off.as<u32>() + ctx->mp_off_used, ctx->mp_flag.as<u32>(), &np, nullptr);
-                if (prc) return prc;
-                ctx->mp_parts.push_back(dskgpu_ctx::MpPart{0ull, np, ctx->mp_off_used});      // (row_base: the caller knows where the pass's rows start in the job)
-                ctx->mp_off_used += np + 1;
-            }
-        }
-        if (!sparse_sort && !mp_part) {
-            hipLaunchKernelGGL(k_compact<W>, dim3((pl.F + 3) / 4), dim3(256), 0, ctx->stream, (const Key*)solid_keys, (const u32*)solid_ab,
-                               ctx->fstart.as<u32>(), ctx->nsolid.as<u32>(), pl.F, ro, rows_ab, opt_cap);
-            CKL("k_compact");
-        }
-        ctx->mark("compact");
-        ctx->stats.n_ext_regions += std::min<u32>(ctx->h_ext, max_ext);
-        *ns_out = ns; *nk_out = h_nk; *plan_out = pl;
+        if ((e = pass_rows<W>(ctx, ps))) return e;
+        res->rows = ps.rows; res->kmers = res->keys_seen = ps.nkeys; res->distinct = ps.stats[0]; res->plan = ps.pl;
         return DSKGPU_OK;
     }
 }
@@ -1199,29 +1246,9 @@ int level0_materialise(dskgpu_ctx* ctx, u64 nwords, u32 lo, u32 npass, u64 reser
     // ---- the passes' loads in this sweep, sampled
     std::vector<u64> slice(G, uslice);
     if (!ctx->tune.no_sample) {
-        const u64 ntiles = std::max<u64>(1, (nwords + Tile<1>::WORDS - 1) / Tile<1>::WORDS);
-        const u64 nts = std::min<u64>(ntiles, 1024);
-        ctx->h_descs_s.resize(nts);
-        for (u64 i = 0; i < nts; ++i) {
-            const u64 t = i * ntiles / nts;
-            ChunkDesc d; d.begin = t * Tile<1>::WORDS; d.end = std::min<u64>(nwords, (t + 1) * Tile<1>::WORDS); d.flat_base = (u32)i; d.stride = (u32)nts;
-            ctx->h_descs_s[i] = d;
-        }
-        const u64 Ms = (u64)G * nts;
-        CK(ctx->smp_descs.ensure(nts * sizeof(ChunkDesc)));
-        CK(ctx->smp_mat.ensure((Ms + 4) * 4 + (size_t)G * 16));
-        CK(hipMemcpyAsync(ctx->smp_descs.p, ctx->h_descs_s.data(), nts * sizeof(ChunkDesc), hipMemcpyHostToDevice, ctx->stream));
-        ctx->h_sc[SC_NCH_S] = (u32)nts;
-        CK(hipMemcpyAsync(sc + SC_NCH_S, &ctx->h_sc[SC_NCH_S], 4, hipMemcpyHostToDevice, ctx->stream));
-        { const int e = launch_hist_m<1, 0, 4>(ctx, nullptr, ctx->smp_descs.as<ChunkDesc>(), sc + SC_NCH_S, nts, ctx->smp_mat.as<u32>(), ds, G); if (e) return e; }
-        u64* mom = reinterpret_cast<u64*>(ctx->smp_mat.as<u32>() + ((Ms + 2) & ~(u64)1));
-        hipLaunchKernelGGL(k_bin_moments, dim3((G + 3) / 4), dim3(256), 0, ctx->stream, (const u32*)ctx->smp_mat.as<u32>(), (u32)nts, G, mom);
-        CKL("k_bin_moments");
-        ctx->h_mom.resize((size_t)G * 2);
-        CK(hipMemcpyAsync(ctx->h_mom.data(), mom, (size_t)G * 16, hipMemcpyDeviceToHost, ctx->stream));
-        CK(hipStreamSynchronize(ctx->stream));
-        u64 stot = 0;
-        for (u32 b = 0; b < G; ++b) stot += ctx->h_mom[2 * b];
+        auto hist = [&](const ChunkDesc* dd, const u32* d_nch, u64 n, u32* mat) { return launch_hist_m<1, 0, 4>(ctx, nullptr, dd, d_nch, n, mat, ds, G); };
+        u64 ntiles = 0, nts = 0, stot = 0;
+        { const int e = positional_sample(ctx, nwords, Tile<1>::WORDS, G, hist, &ntiles, &nts, &stot); if (e) return e; }
         if (stot >= (u64)G * 4096) {
             const double scale = (double)ntiles / (double)nts, tiles_per_block = (double)ntiles * share;
             for (u32 b = 0; b < G; ++b) {
@@ -1466,7 +1493,7 @@ int run_pipeline(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_
         std::vector<u64> pass_hist(ctx->hist.size());
         u64 tot_rows = 0, tot_kmers = 0, tot_distinct = 0;
         Plan pl{};
-        bool too_big = false;
+        bool too_big = false; u64 seen = 0;      // a pass that held more keys than its buffers: how many
         u32 l0_lo = 0, l0_n = 0; u64 l0_keys[L0_MAX_PASSES] = {0}; u64 l0_base[L0_MAX_PASSES] = {0};       // passes materialised by the last level-0 sweep
         bool l0_try = W == 1 && from_reads && npass > 1 && ctx->have_nvalid && !ctx->tune.no_level0 && !rec_l0;
         u32 r_hi = 0; u64 r_base[SK_MAX_OWNERS] = {0};     // record-based level 0: owners materialised by the last sweep, first word of each one's region
@@ -1478,7 +1505,8 @@ int run_pipeline(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_
         ctx->mp_part_ok = npass > 1 && W <= 2 && (ctx->cfg.flags & DSKGPU_F_PARTITION_ORDER) && !(ctx->cfg.flags & DSKGPU_F_NO_SORT) && !ctx->bank_job.active;
         if (ctx->mp_part_ok) { CK(ctx->mp_flag.ensure(256)); CK(hipMemsetAsync(ctx->mp_flag.p, 0, 4, ctx->stream)); }
         for (u32 p = 0; p < npass; ++p) {
-            u64 ns = 0, nk = 0;
+            PassResult r{};
+            r.plan = pl;                   // (a pass without keys leaves the plan of the one before)
             int rc;
             const size_t mp_before = ctx->mp_parts.size();
             ctx->sink = dskgpu_ctx::RowSink{};
@@ -1511,14 +1539,12 @@ int run_pipeline(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_
                     if (rc) return rc;
                     r_hi = hi; ++sweeps;
                 }
-                const u64 nvalid = ctx->h_nvalid;
                 const u64 nk_in = ctx->h_sk_sent[p];
                 ctx->rec_src = ctx->l0buf.as<u64>() + r_base[p]; ctx->rec_n = rl.region[p]; ctx->rec_expanded = false; ctx->rec_sized = false;
                 ctx->rec_hint = 0; ctx->rec_hint_est = false; ctx->rec_slice_end.clear(); ctx->rec_gate = nullptr;
-                if (nk_in == 0) { ns = 0; nk = 0; ctx->h_stats[0] = 0; rc = DSKGPU_OK; CK(hipMemsetAsync(ctx->ghist.p, 0, ((size_t)ctx->cfg.histo_max + 1) * 8, ctx->stream)); }
-                else rc = run_one_pass<W>(ctx, false, nullptr, nk_in, 0, 0u, 1u, nk_in, &ns, &nk, &pl);
+                if (nk_in == 0) { rc = DSKGPU_OK; CK(hipMemsetAsync(ctx->ghist.p, 0, ((size_t)ctx->cfg.histo_max + 1) * 8, ctx->stream)); }
+                else rc = run_one_pass<W>(ctx, false, nullptr, nk_in, 0, 0u, 1u, nk_in, &r);
                 ctx->rec_src = nullptr;
-                ctx->h_nvalid = nvalid;
             } else
             if (l0_try && p >= l0_lo + l0_n) {       // the next group of passes: one sweep over the reads writes their keys
                 // (until the first pass has told how many rows a pass leaves, room is kept for one solid row per sixteen k-mers -- what
@@ -1531,14 +1557,14 @@ int run_pipeline(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_
             }
             if (rec_l0) { /* done above */ }
             else if (l0_try && p < l0_lo + l0_n) {
-                const u64 nvalid = ctx->h_nvalid;    // (a pass from a key array sizes itself from its own key count)
                 const u64 nk_in = l0_keys[p - l0_lo];
-                rc = run_one_pass<W>(ctx, false, reinterpret_cast<const Key*>(ctx->l0buf.as<u64>() + l0_base[p - l0_lo]), nk_in, 0, 0u, 1u, nk_in, &ns, &nk, &pl);
-                ctx->h_nvalid = nvalid;
-            } else { rc = run_one_pass<W>(ctx, from_reads, d_keys_in, nkeys_in, nwords, p, npass, cap, &ns, &nk, &pl); if (from_reads) ++sweeps; }
-            if (rc == PASS_TOO_BIG) { too_big = true; break; }
+                rc = run_one_pass<W>(ctx, false, reinterpret_cast<const Key*>(ctx->l0buf.as<u64>() + l0_base[p - l0_lo]), nk_in, 0, 0u, 1u, nk_in, &r);
+            } else { rc = run_one_pass<W>(ctx, from_reads, d_keys_in, nkeys_in, nwords, p, npass, cap, &r); if (from_reads) ++sweeps; }
             if (rc) return rc;
-            tot_kmers += nk; tot_distinct += ctx->h_stats[0];
+            if (r.too_big) { too_big = true; seen = r.keys_seen; break; }
+            pl = r.plan;
+            const u64 ns = r.rows;
+            tot_kmers += r.kmers; tot_distinct += r.distinct;
             if (ctx->mp_parts.size() > mp_before) ctx->mp_parts.back().row_base = tot_rows;
             if (npass > 1) {      // append this pass's rows and histogram to the job's
                 CK(hipMemcpyAsync(pass_hist.data(), ctx->ghist.p, pass_hist.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1580,7 +1606,6 @@ int run_pipeline(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_
         if (too_big) {
             // the pass holds more keys than its buffers: give the passes that capacity (more passes would not make THAT pass
             // smaller); only when it exceeds what 32-bit offsets address, more passes
-            const u64 seen = (u64)ctx->h_back[2];
             if (seen + (1u << 20) < 0xFFFF0000ull && seen > cap_floor) cap_floor = seen + (1u << 20); else { npass *= 2; cap_floor = 0; }
             continue;
         }

@@ -137,7 +137,7 @@ struct dskgpu_ctx {
     DevBuf smp_mat, smp_descs, boff;   // sampled level-1 loads: chunk x bin matrix of the sample tiles, their descriptors; per-bin slice offsets
     DevBuf dbg, l0buf; DevBuf hv_lut, hv_collect, hv_buf; // heavy k-mers: bin -> collect slot, collected sample keys; [keys | counts | rows] of the k-mers counted apart
     std::vector<unsigned char> h_hv_lut; std::vector<u32> h_hv_cnt, h_hv_step; std::vector<u64> h_hv_coll, h_hv_keys;
-    std::vector<ChunkDesc> h_descs_s; std::vector<u64> h_cbeg; std::vector<u32> h_boff; std::vector<u64> h_mom; std::vector<double> h_load, h_spread, h_seg_work;
+    std::vector<ChunkDesc> h_descs_s, h_descs1, h_descs2; std::vector<u64> h_cbeg; std::vector<u32> h_boff; std::vector<u64> h_mom;
     DevBuf out_w[4], srt_w[4], acc_w[4];   // rows as struct-of-arrays: word i of every row in [i]
     DevBuf out_ab, srt_ab, srt_tmp, srt_idx, srt_idx2, srt_k, srt_k2, abund2, acc_ab;   // srt_k2: one record per row for the multi-word gather
     u64 max_keys_per_pass = 0;     // 0 = as many as 32-bit offsets allow
@@ -178,12 +178,11 @@ struct dskgpu_ctx {
     const u64* rec_src = nullptr; u64 rec_n = 0; u64 rec_nch = 0, rec_rpc = 0; bool rec_expanded = false;
     u64* land = nullptr;                             // 64 KB of pinned host memory: where the small per-step read-backs land (landing())
     DevBuf back_dev; u64* back_host = nullptr;      // the count stage's read-back record (k_gather_back) and its pinned landing zone
-    u32 h_back[3] = {0}; u64 h_stats[4] = {0}; u32 h_ovf2 = 0, h_ovf1 = 0, h_ext = 0; u64 h_nvalid = 0; bool have_nvalid = false;
+    u32 h_back[3] = {0}; u64 h_stats[4] = {0}; u32 h_ovf1 = 0; u64 h_nvalid = 0; bool have_nvalid = false;      // read-back landings; the valid k-mer windows of the reads
     bool sentinel_ok = true;       // the all-ones key is not the mixed form of a canonical k-mer of this k (checked at create)
     bool opt1_off = false;         // same for the histogram-free level-1 scatter (block-owned slices)
     bool mw_v3_off = false;        // the top-word table of k_count2v3 met two k-mers it cannot tell apart on these reads: k_count_mw from now on
     bool opt2_off = false;         // the fixed-capacity level-2 scatter overflowed on these reads: use the exact path   // host landing zone of the async size read-back
-    std::vector<ChunkDesc> h_descs1, h_descs2;
     std::vector<const void*> big_lds_fns;   // kernels whose dynamic-LDS limit this context has raised (allow_big_lds)
     u32 h_sc[SC_COUNT] = {0};      // host mirror of the device scalars (kept alive across async copies)
 
