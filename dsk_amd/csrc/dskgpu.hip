@@ -1080,7 +1080,7 @@ int pass_count(dskgpu_ctx* ctx, PassState<W>& ps) {
 // the solid rows of a pass where the count kernels left them (regions / exact ranges), with the rows of the k-mers counted apart as
 // a dense tail (ro / rows_ab from row n_sparse on: already un-mixed)
 template <int W>
-void sparse_rows(dskgpu_ctx* ctx, const PassState<W>& ps, const RowsOut& ro, u32* rows_ab, u32 n_tail, dskgpu_ctx::SparseRows& spr, dskgpu_ctx::SparseRows2& spr2) {
+void sparse_rows(dskgpu_ctx* ctx, const PassState<W>& ps, const RowsOut& ro, u32* rows_ab, u32 n_tail, dskgpu_ctx::SparseRows& spr, dskgpu_ctx::SparseRows2& spr2, dskgpu_ctx::SparseRows4& spr4) {
     const u64 n = ps.nsolid;
     if constexpr (W == 1) {
         spr.s = RsSparse{(const u64*)ps.solid_keys, (const u32*)ps.solid_ab, (const u32*)ctx->nsolid.as<u32>(), (const u32*)ctx->fstart.as<u32>(), ps.opt_cap, ps.pl.F, 0u};
@@ -1089,6 +1089,9 @@ void sparse_rows(dskgpu_ctx* ctx, const PassState<W>& ps, const RowsOut& ro, u32
         spr2.s = Rs2Sparse{(const K2*)ps.solid_keys, (const u32*)ps.solid_ab, (const u32*)ctx->nsolid.as<u32>(), (const u32*)ctx->fstart.as<u32>(), ps.opt_cap, ps.pl.F, 0u};
         spr2.n_sparse = n; spr2.n_tail = n_tail;
         spr2.tail = n_tail ? Rows2C{ro.w[1] + n, ro.w[0] + n, rows_ab + n} : Rows2C{nullptr, nullptr, nullptr};
+    } else {      // (four-word keys: no k-mers counted apart, no tail)
+        spr4.s = Rs4Sparse{(const KN<4>*)ps.solid_keys, (const u32*)ps.solid_ab, (const u32*)ctx->nsolid.as<u32>(), (const u32*)ctx->fstart.as<u32>(), ps.opt_cap, ps.pl.F, 0u};
+        spr4.n_sparse = n;
     }
 }
 
@@ -1130,21 +1133,30 @@ int pass_rows(dskgpu_ctx* ctx, PassState<W>& ps) {
         sparse_sort = ps.npass == 1 && ctx->job_passes == 1 && ns > 0 && ns <= rs_max_rows(ctx) && !(ctx->cfg.flags & DSKGPU_F_NO_SORT) &&
                       !ctx->tune.rs_slab_rows && !ctx->bank_job.active && (W == 1 || 2u * ctx->cfg.kmer_size > 64u);
         if (sparse_sort) {
-            sparse_rows<W>(ctx, ps, ro, rows_ab, (u32)nhs, ctx->sp_rows, ctx->sp_rows2);
+            sparse_rows<W>(ctx, ps, ro, rows_ab, (u32)nhs, ctx->sp_rows, ctx->sp_rows2, ctx->sp_rows4);
             ctx->sp_rows.valid = W == 1; ctx->sp_rows2.valid = W == 2;
+        }
+    } else {
+        // four-word rows: sparse only for DSKGPU_F_PARTITION_ORDER (k_part_sort4 reads them there and writes them dense into ro / rows_ab, which is
+        // where the global sort of four-word rows, sort_rows4, wants them should a block give up); without the flag k_compact as before
+        sparse_sort = (ctx->cfg.flags & DSKGPU_F_PARTITION_ORDER) && ps.npass == 1 && ctx->job_passes == 1 && ns > 0 && ns < 0xFFFF0000ull &&
+                      !(ctx->cfg.flags & DSKGPU_F_NO_SORT) && !ctx->tune.rs_slab_rows && !ctx->bank_job.active;
+        if (sparse_sort) {
+            sparse_rows<W>(ctx, ps, ro, rows_ab, 0u, ctx->sp_rows, ctx->sp_rows2, ctx->sp_rows4);
+            ctx->sp_rows4.valid = true;
         }
     }
     bool mp_part = false;
-    if constexpr (W <= 2) {      // DSKGPU_F_PARTITION_ORDER in a multi-pass count: the pass's rows ordered partition by partition on their way into the dense arrays
+    {      // DSKGPU_F_PARTITION_ORDER in a multi-pass count: the pass's rows ordered partition by partition on their way into the dense arrays
         mp_part = !sparse_sort && ctx->job_passes > 1 && ctx->mp_part_ok && ns > 0 && h_nsolid < 0xFFFF0000ull && (W == 1 || 2u * ctx->cfg.kmer_size > 64u);
         if (!sparse_sort && ctx->job_passes > 1 && ns > 0 && !mp_part) ctx->mp_part_ok = false;      // (one pass outside the scheme: the job keeps the global order)
         if (mp_part) {
-            dskgpu_ctx::SparseRows spr{}; dskgpu_ctx::SparseRows2 spr2{};
-            sparse_rows<W>(ctx, ps, ro, rows_ab, (u32)nhs, spr, spr2);
+            dskgpu_ctx::SparseRows spr{}; dskgpu_ctx::SparseRows2 spr2{}; dskgpu_ctx::SparseRows4 spr4{};
+            sparse_rows<W>(ctx, ps, ro, rows_ab, (u32)nhs, spr, spr2, spr4);
             const u32 np_est = part_sort_nparts(W, pl.F, h_nsolid, (u32)nhs);
             if (ctx->mp_part_off.ensure_keep(((size_t)ctx->mp_off_used + np_est + 2) * 4, (size_t)ctx->mp_off_used * 4, ctx->stream)) return fail(ctx, DSKGPU_E_NOMEM, "partition offsets");
             u32 np = 0;
-            const int prc = launch_part_sort(ctx, W, spr, spr2, ro.w[0], rows_ab, Rows2{W == 2 ? ro.w[1] : nullptr, ro.w[0], rows_ab},
+            const int prc = launch_part_sort(ctx, W, spr, spr2, spr4, ro.w[0], rows_ab, Rows2{W == 2 ? ro.w[1] : nullptr, ro.w[0], rows_ab}, ro,
                                              ctx->mp_part_off.as<u32>() + ctx->mp_off_used, ctx->mp_flag.as<u32>(), &np, nullptr);
             if (prc) return prc;
             ctx->mp_parts.push_back(dskgpu_ctx::MpPart{0ull, np, ctx->mp_off_used});      // (row_base: the caller knows where the pass's rows start in the job)
@@ -1171,7 +1183,7 @@ struct PassResult { u64 rows = 0, kmers = 0, distinct = 0, keys_seen = 0; Plan p
 template <int W>
 int run_one_pass(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_keys_in, u64 nkeys_in, u64 nwords,
                  u32 pass, u32 npass, u64 cap, PassResult* res) {
-    ctx->sp_rows.valid = false; ctx->sp_rows2.valid = false;
+    ctx->sp_rows.valid = false; ctx->sp_rows2.valid = false; ctx->sp_rows4.valid = false;
     KeySource<W> src{from_reads, !from_reads && d_keys_in == nullptr, d_keys_in, nkeys_in, nwords};
     const u64 nvalid = from_reads ? ctx->h_nvalid : nkeys_in;
     int extra_bits = 0, table_retries = 0;
@@ -1502,7 +1514,7 @@ int run_pipeline(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_
         bool rows_sized = false; // the row accumulators are sized for all passes (known after the first one)
         ctx->job_passes = npass;
         ctx->mp_parts.clear(); ctx->mp_off_used = 0;
-        ctx->mp_part_ok = npass > 1 && W <= 2 && (ctx->cfg.flags & DSKGPU_F_PARTITION_ORDER) && !(ctx->cfg.flags & DSKGPU_F_NO_SORT) && !ctx->bank_job.active;
+        ctx->mp_part_ok = npass > 1 && (ctx->cfg.flags & DSKGPU_F_PARTITION_ORDER) && !(ctx->cfg.flags & DSKGPU_F_NO_SORT) && !ctx->bank_job.active;
         if (ctx->mp_part_ok) { CK(ctx->mp_flag.ensure(256)); CK(hipMemsetAsync(ctx->mp_flag.p, 0, 4, ctx->stream)); }
         for (u32 p = 0; p < npass; ++p) {
             PassResult r{};

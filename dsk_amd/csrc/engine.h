@@ -194,6 +194,8 @@ struct dskgpu_ctx {
     // once they are sized; run_one_pass sets `took` when it did: the pass's rows are then already appended)
     struct RowSink { bool active = false, took = false; u32* ab = nullptr; u64* w[4] = {nullptr, nullptr, nullptr, nullptr}; u64 rows = 0, cap = 0; } sink;
     struct SparseRows2 { bool valid = false; Rs2Sparse s{}; u64 n_sparse = 0; Rows2C tail{nullptr, nullptr, nullptr}; u32 n_tail = 0; } sp_rows2;      // (two-word rows)
+    // (four-word rows: handed over sparse under DSKGPU_F_PARTITION_ORDER only -- k_part_sort4 is their one sparse reader; no k-mers counted apart, so no tail)
+    struct SparseRows4 { bool valid = false; Rs4Sparse s{}; u64 n_sparse = 0; } sp_rows4;
     // results
     bool have_result = false;
     // DSKGPU_F_PARTITION_ORDER for the passes of a multi-pass count: every pass orders its rows partition by partition straight into the job's row arrays
@@ -260,7 +262,7 @@ int order_rows(dskgpu_ctx* ctx, u64 n, u32 npass);
 u64 rs_max_rows(const dskgpu_ctx* ctx);
 int sort_index_multiword(dskgpu_ctx* ctx, const u64* const* rows, u64 n, int W);
 u32 part_sort_nparts(int W, u64 F, u64 n_sparse, u32 n_tail);
-int launch_part_sort(dskgpu_ctx* ctx, int W, const dskgpu_ctx::SparseRows& spr, const dskgpu_ctx::SparseRows2& spr2, u64* ov, u32* oab, Rows2 o2,
-                     u32* d_part_off, u32* d_flag, u32* nparts_out, u32* qpp_out);
+int launch_part_sort(dskgpu_ctx* ctx, int W, const dskgpu_ctx::SparseRows& spr, const dskgpu_ctx::SparseRows2& spr2, const dskgpu_ctx::SparseRows4& spr4,
+                     u64* ov, u32* oab, Rows2 o2, RowsOut o4, u32* d_part_off, u32* d_flag, u32* nparts_out, u32* qpp_out);
 u32 rows_partitions(const dskgpu_ctx* ctx);
 void rows_partition_range(const dskgpu_ctx* ctx, u32 p, u64* b, u64* e);

@@ -101,6 +101,8 @@ struct Rows2C { const u64* hi; const u64* lo; const u32* ab; };
 // scan of the per-sub-partition solid counts): the row sort's first step reads them there (one- / two-word keys, still mixed)
 struct RsSparse { const u64* keys; const u32* ab; const u32* soff; const u32* fstart; u32 cap, F, qpc; };
 struct Rs2Sparse { const K2* keys; const u32* ab; const u32* soff; const u32* fstart; u32 cap, F, qpc; };
+// four-word keys (k > 64): read there by the partition-order pass only (partsort.h: k_part_sort4) -- the global sort of four-word rows takes dense rows
+struct Rs4Sparse { const KN<4>* keys; const u32* ab; const u32* soff; const u32* fstart; u32 cap, F, qpc; };
 
 template <class T>
 __global__ void k_gather(T* __restrict__ dst, const T* __restrict__ src, const u32* __restrict__ idx, u64 n) {

@@ -1,13 +1,14 @@
 // partsort.h -- the solid rows in the REFERENCE's order: ascending inside an output partition, partitions = classes of the hash
-// (gfx950, wave64; one-word and two-word rows of a single pass).
+// (gfx950, wave64; one-, two- and four-word rows -- every k up to 128 --, one launch per pass).
 //
 // What the reference's readers see is `Partition<Count> "solid"`: dsk2ascii walks the partitions one after the other
 // (utils/dsk2ascii.cpp:61,77) and prints the rows of each as they come (:85-104); gatb-core's partitions are classes of the
 // minimizer hash, and only inside a partition are the rows ascending.  The global order rowsort.h produces is more than that
 // contract asks for and costs three passes over the rows (4.3 x their bytes, 1.3 ms of a 13.7 ms step: VERDICT r05).  With
 // DSKGPU_F_PARTITION_ORDER an output partition is a run of `qpp` consecutive hash sub-partitions of the count kernel -- at most
-// PS_CAP rows --, and ONE block orders it in LDS: the rows are read once where the count kernel left them (RsSparse: the regions,
-// keys still mixed) and written once, dense, partition after partition.
+// PS_CAP rows (PS2_CAP for two-word rows, PS4_CAP for four-word rows) --, and ONE block orders it in LDS: the rows are read once
+// where the count kernel left them (RsSparse / Rs2Sparse / Rs4Sparse: the regions, keys still mixed) and written once, dense,
+// partition after partition.
 //
 //   load   every thread takes PS_RPT (4) rows of the partition into registers (the sub-partition of a row by bisection over the LDS
 //          slice of the scanned counts, as rowsort.h's RsSparseSrc), un-mixes the key
@@ -260,4 +261,122 @@ __global__ __launch_bounds__(PS_NT) void k_part_sort2(Rs2Sparse s, Rows2C tail, 
     }
     __syncthreads();
     for (u32 i = tid; i < n; i += PS_NT) { o.hi[(u64)r0 + i] = lh[i]; o.lo[(u64)r0 + i] = ll[i]; o.ab[(u64)r0 + i] = la[i]; }
+}
+
+// ---- the same for four-word rows (65 <= k <= 128, device key KN<4>): four word arrays + the abundances, PS4_CAP rows per block
+// One row per thread: 1024 rows are 36 KB of LDS (word by word: lw[x][i], so neither the placement nor the store strides by 36 bytes)
+// + 16 KB of bins + the slice of the scanned counts = 54 KB, static, two blocks of 16 waves per CU.  It is also the count side's
+// unit: a sub-partition of four-word keys is sized for 640 keys with 1024 staged, so one sub-partition fits one block whatever the
+// abundance threshold.  What differs from the narrower kernels:
+//   bin    the 2k value bits end in word 2 or 3 (k = 65: two bits of word 2; k = 128: all of word 3): the shift 2k - 12 = 118 .. 244
+//          crosses words (ps4_bin)
+//   tail   none: no k-mers are counted apart for four-word keys, so there is no tail block -- every block reads the sparse rows and
+//          writes other memory than it reads (the output pointers carry no __restrict__ all the same: nothing here needs it)
+#define PS4_CAP PS_NT                     // 1024 rows
+__device__ __forceinline__ u64 rs4_sp_base(const Rs4Sparse& s, u32 q) { return s.cap ? (u64)q * s.cap : (u64)s.fstart[q]; }
+__device__ __forceinline__ u32 ps4_bin(u64 w0, u64 w1, u64 w2, u64 w3, int sh) {      // the top 12 of the 2k value bits: (w3 : w2 : w1 : w0) >> sh
+    const int wi = sh >> 6, b = sh & 63;                                               // (kernel arguments: uniform selects, no indexed registers)
+    const u64 lo = wi == 0 ? w0 : wi == 1 ? w1 : wi == 2 ? w2 : w3;
+    const u64 hi = wi == 0 ? w1 : wi == 1 ? w2 : wi == 2 ? w3 : 0ull;
+    const u64 v = b ? (lo >> b) | (hi << (64 - b)) : lo;
+    return v < PS_BINS ? (u32)v : PS_BINS - 1;
+}
+__global__ __launch_bounds__(PS_NT) void k_part_sort4(Rs4Sparse s, PsParams pp, RowsOut o, u32* oab, u32* part_off, u32* flag) {
+    __shared__ u64 lw[4][PS4_CAP];
+    __shared__ u32 la[PS4_CAP];
+    __shared__ u32 cnt[PS_BINS];
+    __shared__ u32 lsoff[PS_MAXQ + 1];
+    __shared__ u32 wsum[PS_NT / 64 + 1];
+    const u32 tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const u32 p = blockIdx.x;
+    const u32 q0 = p * pp.qpp < s.F ? p * pp.qpp : s.F, q1 = q0 + pp.qpp < s.F ? q0 + pp.qpp : s.F, nq = q1 - q0;
+    for (u32 x = tid; x <= nq; x += PS_NT) lsoff[x] = s.soff[q0 + x];
+    for (u32 b = tid; b < PS_BINS; b += PS_NT) cnt[b] = 0;
+    __syncthreads();
+    const u32 r0 = lsoff[0];
+    const u32 n = lsoff[nq] - r0;
+    if (tid == 0) {
+        part_off[p] = r0;
+        if (p + 1 == gridDim.x) part_off[p + 1] = r0 + n;
+    }
+    if (n > PS4_CAP) {                                              // (block-uniform) more rows than a block orders: hand them on as they are, dense, and say so
+        if (tid == 0) *flag = 1u;
+        for (u32 i = tid; i < n; i += PS_NT) {
+            const u32 r = r0 + i;
+            u32 lo = 0, hi = nq;
+            while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if (lsoff[mid] <= r) lo = mid; else hi = mid; }
+            const u64 src = rs4_sp_base(s, q0 + lo) + (u64)(r - lsoff[lo]);
+            KN<4> kx;
+#pragma unroll
+            for (int x = 0; x < 4; ++x) kx.w[x] = s.keys[src].w[x];
+            kunmixN(kx);
+#pragma unroll
+            for (int x = 0; x < 4; ++x) o.w[x][(u64)r] = kx.w[x];
+            oab[(u64)r] = s.ab[src];
+        }
+        return;
+    }
+    if (n == 0) return;
+    const bool have = tid < n;
+    u64 k0, k1, k2, k3; u32 a;
+    {
+        const u32 r = r0 + (have ? tid : n - 1);                    // (clamped: unconditional loads)
+        u32 lo = 0, hi = nq;                                        // largest x with lsoff[x] <= r
+        while (hi - lo > 1) { const u32 mid = (lo + hi) >> 1; if (lsoff[mid] <= r) lo = mid; else hi = mid; }
+        const u64 src = rs4_sp_base(s, q0 + lo) + (u64)(r - lsoff[lo]);
+        KN<4> kx;                                                   // (word by word: a struct copy of a four-word key goes through scratch, see table_insert2)
+#pragma unroll
+        for (int x = 0; x < 4; ++x) kx.w[x] = s.keys[src].w[x];
+        kunmixN(kx);
+        k0 = kx.w[0]; k1 = kx.w[1]; k2 = kx.w[2]; k3 = kx.w[3]; a = s.ab[src];
+    }
+    u32 rb = 0xFFFFFFFFu;                                           // bin << 16 | rank inside the bin
+    if (have) { const u32 bin = ps4_bin(k0, k1, k2, k3, pp.sh); rb = (bin << 16) | atomicAdd(&cnt[bin], 1u); }
+    __syncthreads();
+    {   // exclusive scan over the PS_BINS counts, PS_BINS / PS_NT per thread
+        constexpr int CPT = PS_BINS / PS_NT;
+        u32 c[CPT], sum = 0;
+#pragma unroll
+        for (int x = 0; x < CPT; ++x) { c[x] = cnt[tid * CPT + x]; sum += c[x]; }
+        const u32 inc = wave_incl_scan(sum);
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        u32 run = inc - sum;
+#pragma unroll
+        for (int x = 0; x < PS_NT / 64; ++x) { const u32 v = wsum[x]; if ((u32)x < wave) run += v; }
+        bool heavy = false;
+#pragma unroll
+        for (int x = 0; x < CPT; ++x) { cnt[tid * CPT + x] = (run << 16) | c[x]; run += c[x]; heavy = heavy || c[x] > pp.maxc; }
+        if (heavy) *flag = 1u;                                       // (the rows are still all written, and ordered: the flag only sends the host to the global sort)
+    }
+    __syncthreads();
+    u32 pos = 0, cb = 0;
+    if (have) {
+        cb = cnt[rb >> 16];
+        pos = (cb >> 16) + (rb & 0xFFFFu);
+        lw[0][pos] = k0; lw[1][pos] = k1; lw[2][pos] = k2; lw[3][pos] = k3; la[pos] = a;
+    }
+    __syncthreads();
+    // rows that share their bin: final slot = first slot of the bin + number of smaller rows in it, compared over all four words, most
+    // significant first (distinct k-mers: no ties)
+    const u32 c = cb & 0xFFFFu;
+    const bool moved = have && c > 1u;
+    if (moved) {
+        const u32 ob = cb >> 16;
+        u32 less = 0;
+        for (u32 x = 0; x < c; ++x) {
+            const u64 h3 = lw[3][ob + x], h2 = lw[2][ob + x], h1 = lw[1][ob + x], h0 = lw[0][ob + x];
+            const bool lt = h3 < k3 || (h3 == k3 && (h2 < k2 || (h2 == k2 && (h1 < k1 || (h1 == k1 && h0 < k0)))));
+            less += lt ? 1u : 0u;
+        }
+        pos = ob + less;
+    }
+    __syncthreads();
+    if (moved) { lw[0][pos] = k0; lw[1][pos] = k1; lw[2][pos] = k2; lw[3][pos] = k3; la[pos] = a; }
+    __syncthreads();
+    if (have) {
+#pragma unroll
+        for (int x = 0; x < 4; ++x) o.w[x][(u64)r0 + tid] = lw[x][tid];
+        oab[(u64)r0 + tid] = la[tid];
+    }
 }

@@ -688,23 +688,29 @@ int sort_rows_huge(dskgpu_ctx* ctx, u64 n) {
 
 }  // namespace
 
-// ---- DSKGPU_F_PARTITION_ORDER: one-word rows of a single pass, ordered inside output partitions of <= PS_CAP rows by one LDS pass
-// (partsort.h).  In: the sparse rows (ctx->sp_rows).  Out: srt_w[0] / srt_ab dense, partition after partition; part_off on the device
-// and (after the caller's synchronisation) in h_part_off; SC_SORTFLAG raised when a block could not order its partition.
-// one launch: the sparse rows `spr` / `spr2` (W = 1 / 2) -> dense rows at ov / o2, partition offsets (relative to the first row) at d_part_off
-// [0 .. *nparts], *d_flag raised when a block could not order its partition (the rows are complete either way)
-int launch_part_sort(dskgpu_ctx* ctx, int W, const dskgpu_ctx::SparseRows& spr, const dskgpu_ctx::SparseRows2& spr2, u64* ov, u32* oab, Rows2 o2,
-                     u32* d_part_off, u32* d_flag, u32* nparts_out, u32* qpp_out) {
-    const u64 F = W == 1 ? spr.s.F : spr2.s.F, n_sparse = W == 1 ? spr.n_sparse : spr2.n_sparse;
-    const u32 n_tail = W == 1 ? spr.n_tail : spr2.n_tail;
-    const u64 cap_rows = W == 1 ? PS_CAP : PS2_CAP;
+// ---- DSKGPU_F_PARTITION_ORDER: the rows of a single pass, ordered inside output partitions of <= PS_CAP / PS2_CAP / PS4_CAP rows (one- / two- /
+// four-word rows) by one LDS pass (partsort.h).  In: the sparse rows (ctx->sp_rows / sp_rows2 / sp_rows4).  Out: dense, partition after
+// partition -- srt_w[] / srt_ab, four-word rows in out_w[] / out_ab (where sort_rows4 expects its input, should a block give up);
+// part_off on the device and (after the caller's synchronisation) in h_part_off; SC_SORTFLAG raised when a block could not order its partition.
+// rows a block orders, and the sub-partitions per output partition / the partitions for F sub-partitions holding n_sparse rows (+ a tail)
+static u64 part_sort_cap(int W) { return W == 1 ? PS_CAP : W == 2 ? PS2_CAP : PS4_CAP; }
+static u32 part_sort_qpp(int W, u64 F, u64 n_sparse) {
     const u64 mean = std::max<u64>(1, (n_sparse + F - 1) / std::max<u64>(F, 1));
-    const u32 qpp = (u32)std::min<u64>(std::max<u64>(1, (cap_rows * 3 / 4) / mean), PS_MAXQ);
+    return (u32)std::min<u64>(std::max<u64>(1, (part_sort_cap(W) * 3 / 4) / mean), PS_MAXQ);
+}
+// one launch: the sparse rows `spr` / `spr2` / `spr4` (W = 1 / 2 / 4) -> dense rows at ov / o2 / o4, partition offsets (relative to the first row) at
+// d_part_off[0 .. *nparts], *d_flag raised when a block could not order its partition (the rows are complete either way)
+int launch_part_sort(dskgpu_ctx* ctx, int W, const dskgpu_ctx::SparseRows& spr, const dskgpu_ctx::SparseRows2& spr2, const dskgpu_ctx::SparseRows4& spr4,
+                     u64* ov, u32* oab, Rows2 o2, RowsOut o4, u32* d_part_off, u32* d_flag, u32* nparts_out, u32* qpp_out) {
+    const u64 F = W == 1 ? spr.s.F : W == 2 ? spr2.s.F : spr4.s.F, n_sparse = W == 1 ? spr.n_sparse : W == 2 ? spr2.n_sparse : spr4.n_sparse;
+    const u32 n_tail = W == 1 ? spr.n_tail : W == 2 ? spr2.n_tail : 0u;
+    const u32 qpp = part_sort_qpp(W, F, n_sparse);
     const u32 nps = (u32)((F + qpp - 1) / qpp), nparts = nps + (n_tail ? 1u : 0u);
     const int sh = std::max(0, 2 * (int)ctx->cfg.kmer_size - 12);
     const PsParams pp{qpp, nps, W == 1 ? std::min(sh, 52) : sh, n_tail, ctx->tune.ps_maxc ? std::min<u32>(ctx->tune.ps_maxc, PS_MAXC) : PS_MAXC};
     if (W == 1) hipLaunchKernelGGL(k_part_sort, dim3(nparts), dim3(PS_NT), 0, ctx->stream, spr.s, spr.tail_k, spr.tail_v, pp, ov, oab, d_part_off, d_flag);
-    else hipLaunchKernelGGL(k_part_sort2, dim3(nparts), dim3(PS_NT), 0, ctx->stream, spr2.s, spr2.tail, pp, o2, d_part_off, d_flag);
+    else if (W == 2) hipLaunchKernelGGL(k_part_sort2, dim3(nparts), dim3(PS_NT), 0, ctx->stream, spr2.s, spr2.tail, pp, o2, d_part_off, d_flag);
+    else hipLaunchKernelGGL(k_part_sort4, dim3(nparts), dim3(PS_NT), 0, ctx->stream, spr4.s, pp, o4, oab, d_part_off, d_flag);
     CKL("k_part_sort");
     *nparts_out = nparts; if (qpp_out) *qpp_out = qpp;
     return DSKGPU_OK;
@@ -712,9 +718,7 @@ int launch_part_sort(dskgpu_ctx* ctx, int W, const dskgpu_ctx::SparseRows& spr, 
 
 // partitions a launch will make for F sub-partitions holding n_sparse rows (+ a tail)
 u32 part_sort_nparts(int W, u64 F, u64 n_sparse, u32 n_tail) {
-    const u64 cap_rows = W == 1 ? PS_CAP : PS2_CAP;
-    const u64 mean = std::max<u64>(1, (n_sparse + F - 1) / std::max<u64>(F, 1));
-    const u32 qpp = (u32)std::min<u64>(std::max<u64>(1, (cap_rows * 3 / 4) / mean), PS_MAXQ);
+    const u32 qpp = part_sort_qpp(W, F, n_sparse);
     return (u32)((F + qpp - 1) / qpp) + (n_tail ? 1u : 0u);
 }
 
@@ -724,22 +728,30 @@ int sort_rows_partition_order(dskgpu_ctx* ctx, u64 n, Round* r) {
     const int W = ctx->W;
     const dskgpu_ctx::SparseRows spr = ctx->sp_rows;
     const dskgpu_ctx::SparseRows2 spr2 = ctx->sp_rows2;
-    ctx->sp_rows.valid = false; ctx->sp_rows2.valid = false;
-    const u32 nparts = part_sort_nparts(W, W == 1 ? spr.s.F : spr2.s.F, W == 1 ? spr.n_sparse : spr2.n_sparse, W == 1 ? spr.n_tail : spr2.n_tail);
-    for (int x = 0; x < W; ++x) CK(ctx->srt_w[x].ensure(n * 8));
-    CK(ctx->srt_ab.ensure(n * 4));
+    const dskgpu_ctx::SparseRows4 spr4 = ctx->sp_rows4;
+    ctx->sp_rows.valid = false; ctx->sp_rows2.valid = false; ctx->sp_rows4.valid = false;
+    const u32 nparts = part_sort_nparts(W, W == 1 ? spr.s.F : W == 2 ? spr2.s.F : spr4.s.F, W == 1 ? spr.n_sparse : W == 2 ? spr2.n_sparse : spr4.n_sparse,
+                                        W == 1 ? spr.n_tail : W == 2 ? spr2.n_tail : 0u);
+    // four-word rows go to out_* (pass_rows sized them for the pass's rows; nothing else is in them while the rows are sparse): the
+    // retry in global order, sort_rows4, finds a complete dense copy of the rows where it reads its input
+    DevBuf* dst_w = W == 4 ? ctx->out_w : ctx->srt_w;
+    DevBuf& dst_ab = W == 4 ? ctx->out_ab : ctx->srt_ab;
+    for (int x = 0; x < W; ++x) CK(dst_w[x].ensure(n * 8));
+    CK(dst_ab.ensure(n * 4));
     CK(ctx->rs.part_off.ensure(((size_t)nparts + 2) * 4));
     { const int rc = grow_pinned(ctx, ctx->rs.h_part_off, ctx->rs.h_part_cap, (size_t)nparts + 2, ((size_t)nparts + 2) * 2); if (rc) return rc; }
     u32* sc = ctx->scalars.as<u32>();
     hipLaunchKernelGGL(k_set_rs_scalars, dim3(1), dim3(64), 0, ctx->stream, sc + SC_RSLEN, 0u, 1u, sc + SC_SORTFLAG, (u32*)nullptr);
     u32 np = 0;
-    { const int rc = launch_part_sort(ctx, W, spr, spr2, ctx->srt_w[0].as<u64>(), ctx->srt_ab.as<u32>(), Rows2{ctx->srt_w[1].as<u64>(), ctx->srt_w[0].as<u64>(), ctx->srt_ab.as<u32>()},
+    RowsOut o4{};
+    if (W == 4) for (int x = 0; x < 4; ++x) o4.w[x] = dst_w[x].as<u64>();
+    { const int rc = launch_part_sort(ctx, W, spr, spr2, spr4, dst_w[0].as<u64>(), dst_ab.as<u32>(), Rows2{W == 2 ? dst_w[1].as<u64>() : nullptr, dst_w[0].as<u64>(), dst_ab.as<u32>()}, o4,
                                       ctx->rs.part_off.as<u32>(), sc + SC_SORTFLAG, &np, nullptr); if (rc) return rc; }
     CK(hipMemcpyAsync(ctx->rs.h_part_off, ctx->rs.part_off.p, ((size_t)nparts + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
     ctx->rs.part_mode = true; ctx->rs.n_parts = nparts; ctx->rs.h_part_off64.clear();
     r->back = 2;            // (the flag travels with the histogram)
-    for (int x = 0; x < W; ++x) ctx->res_w[x] = ctx->srt_w[x].as<u64>();
-    ctx->res_ab = ctx->srt_ab.as<u32>();
+    for (int x = 0; x < W; ++x) ctx->res_w[x] = dst_w[x].as<u64>();
+    ctx->res_ab = dst_ab.as<u32>();
     return DSKGPU_OK;
 }
 
@@ -815,10 +827,13 @@ int sort_rows(dskgpu_ctx* ctx, u64 n, bool global, Round* r) {
     ctx->res_ab = ctx->out_ab.as<u32>();
     ctx->rs.part_mode = false;
     ctx->rs.listed = 0;
-    if ((ctx->sp_rows.valid && (n == 0 || (ctx->cfg.flags & DSKGPU_F_NO_SORT) || W != 1)) || (ctx->sp_rows2.valid && (n == 0 || (ctx->cfg.flags & DSKGPU_F_NO_SORT) || W != 2)))
+    // (four-word rows have one sparse reader, the partition-order pass: sparse rows that it will not take are an error, not a quiet detour)
+    const bool part = (ctx->cfg.flags & DSKGPU_F_PARTITION_ORDER) && !global && n < 0xFFFF0000ull;
+    if ((ctx->sp_rows.valid && (n == 0 || (ctx->cfg.flags & DSKGPU_F_NO_SORT) || W != 1)) || (ctx->sp_rows2.valid && (n == 0 || (ctx->cfg.flags & DSKGPU_F_NO_SORT) || W != 2)) ||
+        (ctx->sp_rows4.valid && (n == 0 || (ctx->cfg.flags & DSKGPU_F_NO_SORT) || W != 4 || !part)))
         return fail(ctx, DSKGPU_E_STATE, "row sort: sparse rows on a path that cannot read them");
     if (n == 0 || (ctx->cfg.flags & DSKGPU_F_NO_SORT)) return DSKGPU_OK;
-    if ((ctx->sp_rows.valid || ctx->sp_rows2.valid) && (ctx->cfg.flags & DSKGPU_F_PARTITION_ORDER) && !global && n < 0xFFFF0000ull) return sort_rows_partition_order(ctx, n, r);
+    if ((ctx->sp_rows.valid || ctx->sp_rows2.valid || ctx->sp_rows4.valid) && part) return sort_rows_partition_order(ctx, n, r);
     if (ctx->sp_rows.valid) return sort_rows_msd(ctx, n, r);      // the rows of a single one-word pass, still in the count kernel's regions (run_one_pass made sure this sort takes them)
     if (ctx->sp_rows2.valid) return sort_rows2_msd(ctx, n, r);    // (the two-word twin)
     const u64 rs_max = rs_max_rows(ctx);
@@ -857,7 +872,7 @@ int order_rows(dskgpu_ctx* ctx, u64 n, u32 npass) {
             rs.part_mode = true; rs.n_parts = (u32)(rs.h_part_off64.size() - 1);
             for (int x = 0; x < 4; ++x) ctx->res_w[x] = x < W ? ctx->out_w[x].as<u64>() : nullptr;
             ctx->res_ab = ctx->out_ab.as<u32>();
-            ctx->sp_rows.valid = false; ctx->sp_rows2.valid = false;
+            ctx->sp_rows.valid = false; ctx->sp_rows2.valid = false; ctx->sp_rows4.valid = false;
             rs.flag = 0; rs.listed = 0;
             return DSKGPU_OK;
         }
@@ -890,7 +905,7 @@ int order_rows(dskgpu_ctx* ctx, u64 n, u32 npass) {
         if (rs.part_mode && rs.flag) {      // a partition (or a value bin of one) above what a block orders in LDS: the global sort, on the same sparse rows
             if (ctx->tune.verbose) fprintf(stderr, "[dskgpu] row sort: a partition exceeds what one block orders -- global order instead of partition order\n");
             rs.part_mode = false; rs.flag = 0;
-            ctx->sp_rows = sp_rows; ctx->sp_rows2 = sp_rows2;
+            ctx->sp_rows = sp_rows; ctx->sp_rows2 = sp_rows2;      // (four-word rows: the partition pass left them dense in out_*, sort_rows4's input)
             global = true;
             continue;
         }

@@ -235,7 +235,8 @@ class KmerCounter:
                  minimizer_size: int = 0, max_pass_mkeys: int = 0, solidity_kind: str = "sum", solidity_custom: int = 0,
                  histo2d: bool = False, mg_explicit: bool = False, place: bool = False, partition_order: bool = False):
         """partition_order: DSKGPU_F_PARTITION_ORDER -- rows ascending inside every output partition only (the reference's Partition<Count>
-        contract; thousands of small partitions), one pass over the rows instead of the three of the global order.
+        contract; thousands of small partitions), one pass over the rows instead of the three of the global order.  Honoured at every
+        k up to 128: partitions of at most 4096 rows for k <= 32, 2048 for k <= 64, 1024 (PS4_CAP) for 65 <= k <= 128.
         place: DSKGPU_F_PLACE -- every big device buffer becomes the best-placed of 8 candidate allocations (one-off cost of a
         few seconds at the first count, steps ~6 % faster and no longer box- and process-dependent): for contexts that count often."""
         self._lib = load_library()

@@ -74,9 +74,12 @@ typedef struct dskgpu_config {
                                    * hash sub-partitions of at most 4096 rows (dskgpu_num_partitions of them: thousands) -- what Partition<Count> "solid"
                                    * guarantees its readers (utils/dsk2ascii.cpp:61,77,85-104: partition after partition, the rows of each as they
                                    * come; gatb-core's partitions are classes of the minimizer hash).  One pass over the rows instead of three
-                                   * (csrc/partsort.h).  Honoured by a single-pass count of one- and two-word k-mers (k <= 64; 2048 rows per partition above k = 32); every other path -- and an
-                                   * input on which a partition would exceed what one block orders -- keeps the global order, which satisfies the
-                                   * same contract with nb_partitions value ranges. */
+                                   * (csrc/partsort.h).  Honoured at every k (1 <= k <= 128), by a single pass and by every pass of a multi-pass count;
+                                   * rows per partition: at most 4096 (PS_CAP) for k <= 32, 2048 (PS2_CAP) for 33 <= k <= 64, 1024 (PS4_CAP) for
+                                   * 65 <= k <= 128 (four-word device keys: one 36-byte row per thread of the block that orders the partition).  The
+                                   * per-bank modes (a solidity kind other than sum, DSKGPU_F_HISTO2D) -- and an input on which a partition would
+                                   * exceed what one block orders -- keep the global order, which satisfies the same contract with nb_partitions
+                                   * value ranges. */
 #define DSKGPU_F_PLACE 16u        /* pick the place of every big device buffer: where a buffer lies in HBM changes the rate of
                                    * scattered stores into it by up to 40 % (tools/micro/write_place.hip; the "two speeds" of the
                                    * partition kernels).  Each allocation >= 256 MB becomes the best of up to 8 candidates, timed
