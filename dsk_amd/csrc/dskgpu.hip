@@ -1080,19 +1080,12 @@ int pass_count(dskgpu_ctx* ctx, PassState<W>& ps) {
 // the solid rows of a pass where the count kernels left them (regions / exact ranges), with the rows of the k-mers counted apart as
 // a dense tail (ro / rows_ab from row n_sparse on: already un-mixed)
 template <int W>
-void sparse_rows(dskgpu_ctx* ctx, const PassState<W>& ps, const RowsOut& ro, u32* rows_ab, u32 n_tail, dskgpu_ctx::SparseRows& spr, dskgpu_ctx::SparseRows2& spr2, dskgpu_ctx::SparseRows4& spr4) {
-    const u64 n = ps.nsolid;
-    if constexpr (W == 1) {
-        spr.s = RsSparse{(const u64*)ps.solid_keys, (const u32*)ps.solid_ab, (const u32*)ctx->nsolid.as<u32>(), (const u32*)ctx->fstart.as<u32>(), ps.opt_cap, ps.pl.F, 0u};
-        spr.n_sparse = n; spr.n_tail = n_tail; spr.tail_k = n_tail ? ro.w[0] + n : nullptr; spr.tail_v = n_tail ? rows_ab + n : nullptr;
-    } else if constexpr (W == 2) {
-        spr2.s = Rs2Sparse{(const K2*)ps.solid_keys, (const u32*)ps.solid_ab, (const u32*)ctx->nsolid.as<u32>(), (const u32*)ctx->fstart.as<u32>(), ps.opt_cap, ps.pl.F, 0u};
-        spr2.n_sparse = n; spr2.n_tail = n_tail;
-        spr2.tail = n_tail ? Rows2C{ro.w[1] + n, ro.w[0] + n, rows_ab + n} : Rows2C{nullptr, nullptr, nullptr};
-    } else {      // (four-word keys: no k-mers counted apart, no tail)
-        spr4.s = Rs4Sparse{(const KN<4>*)ps.solid_keys, (const u32*)ps.solid_ab, (const u32*)ctx->nsolid.as<u32>(), (const u32*)ctx->fstart.as<u32>(), ps.opt_cap, ps.pl.F, 0u};
-        spr4.n_sparse = n;
-    }
+SparseRows sparse_rows(dskgpu_ctx* ctx, const PassState<W>& ps, const RowsOut& ro, const u32* rows_ab, u32 n_tail) {
+    SparseRows r;
+    r.W = W; r.keys = ps.solid_keys; r.ab = (const u32*)ps.solid_ab; r.soff = ctx->nsolid.as<u32>(); r.fstart = ctx->fstart.as<u32>(); r.cap = ps.opt_cap; r.F = ps.pl.F;
+    r.n_sparse = ps.nsolid; r.n_tail = W <= 2 ? n_tail : 0u;      // (four-word keys: no k-mers counted apart, no tail)
+    if (r.n_tail) { for (int x = 0; x < W; ++x) r.tail_w.w[x] = ro.w[x] + r.n_sparse; r.tail_ab = rows_ab + r.n_sparse; }
+    return r;
 }
 
 // Stage 6, the pass's rows: the heavy tail, then the hand-off to the row sort (sparse), the multi-pass partition order, or k_compact
@@ -1132,35 +1125,25 @@ int pass_rows(dskgpu_ctx* ctx, PassState<W>& ps) {
     if constexpr (W <= 2) {
         sparse_sort = ps.npass == 1 && ctx->job_passes == 1 && ns > 0 && ns <= rs_max_rows(ctx) && !(ctx->cfg.flags & DSKGPU_F_NO_SORT) &&
                       !ctx->tune.rs_slab_rows && !ctx->bank_job.active && (W == 1 || 2u * ctx->cfg.kmer_size > 64u);
-        if (sparse_sort) {
-            sparse_rows<W>(ctx, ps, ro, rows_ab, (u32)nhs, ctx->sp_rows, ctx->sp_rows2, ctx->sp_rows4);
-            ctx->sp_rows.valid = W == 1; ctx->sp_rows2.valid = W == 2;
-        }
     } else {
         // four-word rows: sparse only for DSKGPU_F_PARTITION_ORDER (k_part_sort4 reads them there and writes them dense into ro / rows_ab, which is
         // where the global sort of four-word rows, sort_rows4, wants them should a block give up); without the flag k_compact as before
         sparse_sort = (ctx->cfg.flags & DSKGPU_F_PARTITION_ORDER) && ps.npass == 1 && ctx->job_passes == 1 && ns > 0 && ns < 0xFFFF0000ull &&
                       !(ctx->cfg.flags & DSKGPU_F_NO_SORT) && !ctx->tune.rs_slab_rows && !ctx->bank_job.active;
-        if (sparse_sort) {
-            sparse_rows<W>(ctx, ps, ro, rows_ab, 0u, ctx->sp_rows, ctx->sp_rows2, ctx->sp_rows4);
-            ctx->sp_rows4.valid = true;
-        }
     }
+    if (sparse_sort) ctx->sp_rows = sparse_rows<W>(ctx, ps, ro, rows_ab, (u32)nhs);
+    PartPasses& mp = ctx->rs.mp;
     bool mp_part = false;
     {      // DSKGPU_F_PARTITION_ORDER in a multi-pass count: the pass's rows ordered partition by partition on their way into the dense arrays
-        mp_part = !sparse_sort && ctx->job_passes > 1 && ctx->mp_part_ok && ns > 0 && h_nsolid < 0xFFFF0000ull && (W == 1 || 2u * ctx->cfg.kmer_size > 64u);
-        if (!sparse_sort && ctx->job_passes > 1 && ns > 0 && !mp_part) ctx->mp_part_ok = false;      // (one pass outside the scheme: the job keeps the global order)
+        mp_part = !sparse_sort && ctx->job_passes > 1 && mp.ok && ns > 0 && h_nsolid < 0xFFFF0000ull && (W == 1 || 2u * ctx->cfg.kmer_size > 64u);
+        if (!sparse_sort && ctx->job_passes > 1 && ns > 0 && !mp_part) mp.ok = false;      // (one pass outside the scheme: the job keeps the global order)
         if (mp_part) {
-            dskgpu_ctx::SparseRows spr{}; dskgpu_ctx::SparseRows2 spr2{}; dskgpu_ctx::SparseRows4 spr4{};
-            sparse_rows<W>(ctx, ps, ro, rows_ab, (u32)nhs, spr, spr2, spr4);
-            const u32 np_est = part_sort_nparts(W, pl.F, h_nsolid, (u32)nhs);
-            if (ctx->mp_part_off.ensure_keep(((size_t)ctx->mp_off_used + np_est + 2) * 4, (size_t)ctx->mp_off_used * 4, ctx->stream)) return fail(ctx, DSKGPU_E_NOMEM, "partition offsets");
+            const SparseRows rows = sparse_rows<W>(ctx, ps, ro, rows_ab, (u32)nhs);
+            if (mp.part_off.ensure_keep(((size_t)mp.off_used + part_sort_nparts(rows) + 2) * 4, (size_t)mp.off_used * 4, ctx->stream)) return fail(ctx, DSKGPU_E_NOMEM, "partition offsets");
             u32 np = 0;
-            const int prc = launch_part_sort(ctx, W, spr, spr2, spr4, ro.w[0], rows_ab, Rows2{W == 2 ? ro.w[1] : nullptr, ro.w[0], rows_ab}, ro,
-                                             ctx->mp_part_off.as<u32>() + ctx->mp_off_used, ctx->mp_flag.as<u32>(), &np, nullptr);
-            if (prc) return prc;
-            ctx->mp_parts.push_back(dskgpu_ctx::MpPart{0ull, np, ctx->mp_off_used});      // (row_base: the caller knows where the pass's rows start in the job)
-            ctx->mp_off_used += np + 1;
+            if (const int prc = launch_part_sort(ctx, rows, ro, rows_ab, mp.part_off.as<u32>() + mp.off_used, mp.flag.as<u32>(), &np)) return prc;
+            mp.passes.push_back(PartPasses::Pass{mp.row_base, np, mp.off_used});
+            mp.off_used += np + 1;
         }
     }
     if (!sparse_sort && !mp_part) {
@@ -1177,13 +1160,13 @@ int pass_rows(dskgpu_ctx* ctx, PassState<W>& ps) {
 struct PassResult { u64 rows = 0, kmers = 0, distinct = 0, keys_seen = 0; Plan plan{}; bool too_big = false; };
 
 // One pass: partition + count the keys of pass `pass` (of `npass`) and leave its solid rows (unsorted) in out_w[0]/out_w[1]/out_ab,
-// the job's accumulators (ctx->sink) or where the count kernels put them (ctx->sp_rows / sp_rows2).
+// the job's accumulators (ctx->sink) or where the count kernels put them (ctx->sp_rows).
 // An overflow of a level-1 slice or the level-2 pool repeats the attempt on the exact path; a table overflow repeats it with a
 // finer partition, at most three times.
 template <int W>
 int run_one_pass(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_keys_in, u64 nkeys_in, u64 nwords,
                  u32 pass, u32 npass, u64 cap, PassResult* res) {
-    ctx->sp_rows.valid = false; ctx->sp_rows2.valid = false; ctx->sp_rows4.valid = false;
+    ctx->take_sparse_rows();
     KeySource<W> src{from_reads, !from_reads && d_keys_in == nullptr, d_keys_in, nkeys_in, nwords};
     const u64 nvalid = from_reads ? ctx->h_nvalid : nkeys_in;
     int extra_bits = 0, table_retries = 0;
@@ -1513,14 +1496,15 @@ int run_pipeline(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_
         u64 sweeps = 0;          // times the encoded reads were walked to generate k-mers (DSK's notion of a pass: README.md:126-130)
         bool rows_sized = false; // the row accumulators are sized for all passes (known after the first one)
         ctx->job_passes = npass;
-        ctx->mp_parts.clear(); ctx->mp_off_used = 0;
-        ctx->mp_part_ok = npass > 1 && (ctx->cfg.flags & DSKGPU_F_PARTITION_ORDER) && !(ctx->cfg.flags & DSKGPU_F_NO_SORT) && !ctx->bank_job.active;
-        if (ctx->mp_part_ok) { CK(ctx->mp_flag.ensure(256)); CK(hipMemsetAsync(ctx->mp_flag.p, 0, 4, ctx->stream)); }
+        PartPasses& mp = ctx->rs.mp;
+        mp.passes.clear(); mp.off_used = 0;
+        mp.ok = npass > 1 && (ctx->cfg.flags & DSKGPU_F_PARTITION_ORDER) && !(ctx->cfg.flags & DSKGPU_F_NO_SORT) && !ctx->bank_job.active;
+        if (mp.ok) { CK(mp.flag.ensure(256)); CK(hipMemsetAsync(mp.flag.p, 0, 4, ctx->stream)); }
         for (u32 p = 0; p < npass; ++p) {
             PassResult r{};
             r.plan = pl;                   // (a pass without keys leaves the plan of the one before)
             int rc;
-            const size_t mp_before = ctx->mp_parts.size();
+            mp.row_base = tot_rows;      // (where this pass's rows start in the job)
             ctx->sink = dskgpu_ctx::RowSink{};
             if (npass > 1 && rows_sized) {      // the pass compacts its rows straight behind the job's (when they fit: run_one_pass)
                 ctx->sink.active = true; ctx->sink.rows = tot_rows; ctx->sink.ab = ctx->acc_ab.as<u32>();
@@ -1577,7 +1561,6 @@ int run_pipeline(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_
             pl = r.plan;
             const u64 ns = r.rows;
             tot_kmers += r.kmers; tot_distinct += r.distinct;
-            if (ctx->mp_parts.size() > mp_before) ctx->mp_parts.back().row_base = tot_rows;
             if (npass > 1) {      // append this pass's rows and histogram to the job's
                 CK(hipMemcpyAsync(pass_hist.data(), ctx->ghist.p, pass_hist.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
                 // grow once: the passes hold similar numbers of rows (hash-uniform), so size for all of them after the first

@@ -86,6 +86,28 @@ struct Tuning {
     }
 };
 
+// The solid rows of a pass where the count kernels left them (regions of `cap` rows, or exact ranges from fstart; soff = the scan of the
+// per-sub-partition solid counts; keys still mixed) + the rows of the k-mers counted apart as a dense, un-mixed tail (W <= 2 only).  The
+// row sort's first step and the partition-order pass read them there instead of a dense copy made by k_compact.  as<>(): the descriptor
+// a kernel of that width takes (layouts.h), built at its launch.
+struct SparseRows {
+    int W = 0;                     // 0 = none; else 1, 2 or 4: the words of a key
+    const void* keys = nullptr; const u32 *ab = nullptr, *soff = nullptr, *fstart = nullptr; u32 cap = 0, F = 0;
+    u64 n_sparse = 0; u32 n_tail = 0; RowsIn tail_w{}; const u32* tail_ab = nullptr;
+    template <class S> S as(u32 qpc = 0) const { return S{static_cast<decltype(S::keys)>(keys), ab, soff, fstart, cap, F, qpc}; }
+    Rows2C tail2() const { return Rows2C{tail_w.w[1], tail_w.w[0], tail_ab}; }
+};
+
+// DSKGPU_F_PARTITION_ORDER for the passes of a multi-pass count: every pass orders its rows partition by partition straight into the job's
+// row arrays (one k_part_sort launch instead of k_compact), the offsets of its partitions -- relative to the pass's first row, row_base of
+// the job (run_pipeline sets `row_base` before the pass runs) -- go to part_off[off_index ..], one flag serves the whole job; at the end
+// the offsets become 64-bit row numbers (RowSort::h_part_off64).  ok: every pass so far took part
+struct PartPasses {
+    struct Pass { u64 row_base; u32 nparts, off_index; };
+    std::vector<Pass> passes; DevBuf part_off, flag; u32 off_used = 0; bool ok = false; u64 row_base = 0;
+    std::vector<u32> h_off;
+};
+
 // The row sort's state between calls (order_rows below owns it; the partition accessors read its layout)
 struct RowSort {
     DevBuf fix_list;               // multi-word row sort: [count | (first row, rows) x FIX_LIST_CAP] of the prefix runs above FIX_CAP rows
@@ -99,8 +121,9 @@ struct RowSort {
     // out that way, h_part_off[p] = first row of partition p (n_parts + 1 entries, pinned; several passes: h_part_off64)
     bool part_mode = false; u32 n_parts = 0; u32* h_part_off = nullptr; size_t h_part_cap = 0; DevBuf part_off;
     std::vector<u64> h_part_off64;
+    PartPasses mp;
     void release() {
-        for (DevBuf* b : {&fix_list, &g[0], &g[1], &g[2], &g[3], &del, &lens, &ovs, &part_off}) b->release();
+        for (DevBuf* b : {&fix_list, &g[0], &g[1], &g[2], &g[3], &del, &lens, &ovs, &part_off, &mp.part_off, &mp.flag}) b->release();
         if (hist_pin) (void)hipHostFree(hist_pin);
         if (h_part_off) (void)hipHostFree(h_part_off);
         hist_pin = nullptr; h_part_off = nullptr;
@@ -186,24 +209,16 @@ struct dskgpu_ctx {
     std::vector<const void*> big_lds_fns;   // kernels whose dynamic-LDS limit this context has raised (allow_big_lds)
     u32 h_sc[SC_COUNT] = {0};      // host mirror of the device scalars (kept alive across async copies)
 
-    // the solid rows of a single one-word pass where the count kernel left them (run_one_pass): the row sort's first step reads them there
-    // instead of a dense copy made by k_compact (rowsort.h: RsSparse)
     u32 job_passes = 1;            // passes of the running count as run_pipeline sees them (a pass of a record-based multi-pass count runs as "pass 0 of 1" inside run_one_pass)
-    struct SparseRows { bool valid = false; RsSparse s{}; u64 n_sparse = 0; const u64* tail_k = nullptr; const u32* tail_v = nullptr; u32 n_tail = 0; } sp_rows;
+    // the solid rows of a single pass handed to the row sort where the count kernel left them (pass_rows; W = 0: the rows are dense).  Four-word
+    // rows: under DSKGPU_F_PARTITION_ORDER only -- k_part_sort4 is their one sparse reader; no k-mers counted apart, so no tail
+    SparseRows sp_rows;
+    SparseRows take_sparse_rows() { const SparseRows r = sp_rows; sp_rows = SparseRows{}; return r; }
     // multi-pass jobs: where a pass may put its dense rows straight away -- the job's accumulators, from row `rows` on (run_pipeline sets it
     // once they are sized; run_one_pass sets `took` when it did: the pass's rows are then already appended)
     struct RowSink { bool active = false, took = false; u32* ab = nullptr; u64* w[4] = {nullptr, nullptr, nullptr, nullptr}; u64 rows = 0, cap = 0; } sink;
-    struct SparseRows2 { bool valid = false; Rs2Sparse s{}; u64 n_sparse = 0; Rows2C tail{nullptr, nullptr, nullptr}; u32 n_tail = 0; } sp_rows2;      // (two-word rows)
-    // (four-word rows: handed over sparse under DSKGPU_F_PARTITION_ORDER only -- k_part_sort4 is their one sparse reader; no k-mers counted apart, so no tail)
-    struct SparseRows4 { bool valid = false; Rs4Sparse s{}; u64 n_sparse = 0; } sp_rows4;
     // results
     bool have_result = false;
-    // DSKGPU_F_PARTITION_ORDER for the passes of a multi-pass count: every pass orders its rows partition by partition straight into the job's row arrays
-    // (one k_part_sort launch instead of k_compact), the offsets of its partitions -- relative to the pass's first row -- go to
-    // mp_part_off[off_index ..], one flag (mp_flag) serves the whole job; at the end the offsets become 64-bit row numbers (h_part_off64)
-    struct MpPart { u64 row_base; u32 nparts, off_index; };
-    std::vector<MpPart> mp_parts; DevBuf mp_part_off, mp_flag; u32 mp_off_used = 0; bool mp_part_ok = false;
-    std::vector<u32> h_mp_off;
     u64 n_rows = 0;
     const u64* res_w[4] = {nullptr, nullptr, nullptr, nullptr}; const u32* res_ab = nullptr;
     dskgpu_stats stats{};
@@ -261,8 +276,7 @@ int allow_big_lds(dskgpu_ctx* ctx, const void* fn, int bytes = 160 * 1024);     
 int order_rows(dskgpu_ctx* ctx, u64 n, u32 npass);
 u64 rs_max_rows(const dskgpu_ctx* ctx);
 int sort_index_multiword(dskgpu_ctx* ctx, const u64* const* rows, u64 n, int W);
-u32 part_sort_nparts(int W, u64 F, u64 n_sparse, u32 n_tail);
-int launch_part_sort(dskgpu_ctx* ctx, int W, const dskgpu_ctx::SparseRows& spr, const dskgpu_ctx::SparseRows2& spr2, const dskgpu_ctx::SparseRows4& spr4,
-                     u64* ov, u32* oab, Rows2 o2, RowsOut o4, u32* d_part_off, u32* d_flag, u32* nparts_out, u32* qpp_out);
+u32 part_sort_nparts(const SparseRows& rows);
+int launch_part_sort(dskgpu_ctx* ctx, const SparseRows& rows, RowsOut out, u32* out_ab, u32* d_part_off, u32* d_flag, u32* nparts_out);
 u32 rows_partitions(const dskgpu_ctx* ctx);
 void rows_partition_range(const dskgpu_ctx* ctx, u32 p, u64* b, u64* e);

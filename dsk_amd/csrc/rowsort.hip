@@ -115,6 +115,18 @@ u64 step_a_chunks(u64 n, u64 ncu, u64 tile, u64* chunk) {
     return (n + *chunk - 1) / *chunk;
 }
 
+// the same over a sparse source (the rows still lie in the count kernel's F sub-partitions): chunks = groups of *qpc consecutive sub-partitions
+// (about 64 K rows, at most RS_SP_MAXQ sub-partitions), *nch_sp of them, + one chunk of *chunk rows for the dense tail (the rows of the
+// k-mers counted apart) -> the number of chunks
+u64 step_a_chunks_sparse(u64 F, u64 n_sparse, u32 n_tail, u64 ncu, u32* qpc, u64* nch_sp, u64* chunk) {
+    u64 want = std::max<u64>(1, (n_sparse + 65535) / 65536);
+    want = (want + ncu - 1) / ncu * ncu;
+    *qpc = (u32)std::min<u64>(std::max<u64>(1, (F + want - 1) / want), RS_SP_MAXQ);
+    *nch_sp = (F + *qpc - 1) / *qpc;
+    *chunk = n_tail;
+    return *nch_sp + (n_tail ? 1 : 0);
+}
+
 // the fewest top bits of the first digit (bA bits; bucket b = [start[b], start[b + 1])) whose groups of buckets hold <= rs_max rows
 // each; -1 when one bucket alone holds more
 template <class T>
@@ -141,7 +153,7 @@ struct Round {
 // (tk / tv: scratch of the same size).  One-word rows: (k-mer value, abundance); multi-word rows: (top 63 bits of the value,
 // row index).  Whatever the kernels do not order themselves raises SC_SORTFLAG (zeroed here): the caller falls back to a
 // full-width library sort (k / v and tk / tv each hold a complete permutation of the pairs either way).
-int msd_sort_pairs(dskgpu_ctx* ctx, u64* k, u32* v, u64* tk, u32* tv, u64 n, int total, bool reset_flags = true, u32 base = 0, const dskgpu_ctx::SparseRows* spr = nullptr) {
+int msd_sort_pairs(dskgpu_ctx* ctx, u64* k, u32* v, u64* tk, u32* tv, u64 n, int total, bool reset_flags = true, u32 base = 0, const SparseRows* spr = nullptr) {
     // second digit: 8 bits up to 96 M rows, 9 up to 192 M, 10 beyond (sub-buckets stay near 200 rows: one wave each in step C)
     int wantB = n <= (96ull << 20) ? 8 : n <= (192ull << 20) ? 9 : 10;
     if (ctx->tune.rs_bbits >= 8 && ctx->tune.rs_bbits <= 10) wantB = (int)ctx->tune.rs_bbits;      // tests
@@ -150,21 +162,8 @@ int msd_sort_pairs(dskgpu_ctx* ctx, u64* k, u32* v, u64* tk, u32* tv, u64 n, int
     RsSpec sp{r1, r2, r3, (1u << bA) - 1u, (1u << bB) - 1u, (1u << bC) - 1u};
     const u64 ncu = (u64)ctx->num_cu;
     u64 chunk, nch = step_a_chunks(n, ncu, RS_TILE, &chunk);
-    // sparse source (spr: the rows still lie in the count kernel's regions): chunks = groups of qpc consecutive sub-partitions (about 64 K
-    // rows, at most RS_SP_MAXQ sub-partitions), + one chunk for the dense tail (the rows of the k-mers counted apart)
     RsSparse sps{}; u64 nch_sp = 0;
-    if (spr) {
-        sps = spr->s;
-        const u64 F = sps.F;
-        u64 want = std::max<u64>(1, (spr->n_sparse + 65535) / 65536);
-        want = (want + ncu - 1) / ncu * ncu;
-        u64 qpc = std::max<u64>(1, (F + want - 1) / want);
-        if (qpc > RS_SP_MAXQ) qpc = RS_SP_MAXQ;
-        nch_sp = (F + qpc - 1) / qpc;
-        sps.qpc = (u32)qpc;
-        nch = nch_sp + (spr->n_tail ? 1 : 0);
-        chunk = spr->n_tail;                                              // (the tail is one chunk)
-    }
+    if (spr) { u32 qpc; nch = step_a_chunks_sparse(spr->F, spr->n_sparse, spr->n_tail, ncu, &qpc, &nch_sp, &chunk); sps = spr->as<RsSparse>(qpc); }
     const u64 M = (u64)RS_ABINS * nch;
     if (M >= 0xFFFFFFF0ull) return fail(ctx, DSKGPU_E_ARG, "row sort: chunk matrix too large");
     const u64 nsubw = (u64)RS_ABINS * (BB + 1);                           // sub-bucket starts; behind them the list of large sub-buckets
@@ -183,11 +182,11 @@ int msd_sort_pairs(dskgpu_ctx* ctx, u64* k, u32* v, u64* tk, u32* tv, u64 n, int
         const size_t ldsS = ldsA + ((size_t)RS_SP_MAXQ + 1) * 4;
         { const int e = allow_big_lds(ctx, reinterpret_cast<const void*>(&k_rs_scatter_sp)); if (e) return e; }
         hipLaunchKernelGGL(k_rs_hist_sp, dim3((unsigned)nch_sp), dim3(RS_NT), 0, ctx->stream, sps, (u32)nch, matrix, sp);
-        if (spr->n_tail) hipLaunchKernelGGL(k_rs_hist, dim3(1), dim3(RS_NT), 0, ctx->stream, spr->tail_k, (u64)spr->n_tail, (u32)chunk, (u32)nch, matrix, sp, (u32)nch_sp);
+        if (spr->n_tail) hipLaunchKernelGGL(k_rs_hist, dim3(1), dim3(RS_NT), 0, ctx->stream, spr->tail_w.w[0], (u64)spr->n_tail, (u32)chunk, (u32)nch, matrix, sp, (u32)nch_sp);
         CKL("k_rs_hist_sp");
         { const int e = run_scan(ctx, matrix, sc + SC_RSLEN, M); if (e) return e; }
         hipLaunchKernelGGL(k_rs_scatter_sp, dim3((unsigned)nch_sp), dim3(RS_NT), ldsS, ctx->stream, sps, (u32)nch, (const u32*)matrix, tk, tv, sp);
-        if (spr->n_tail) hipLaunchKernelGGL(k_rs_scatter<false>, dim3(1), dim3(RS_NT), ldsA, ctx->stream, spr->tail_k, spr->tail_v, (u64)spr->n_tail, (u32)chunk, (u32)nch, (const u32*)matrix, tk, tv, sp, (const u64*)nullptr, (u32)nch_sp);
+        if (spr->n_tail) hipLaunchKernelGGL(k_rs_scatter<false>, dim3(1), dim3(RS_NT), ldsA, ctx->stream, spr->tail_w.w[0], spr->tail_ab, (u64)spr->n_tail, (u32)chunk, (u32)nch, (const u32*)matrix, tk, tv, sp, (const u64*)nullptr, (u32)nch_sp);
         CKL("k_rs_scatter_sp");
     } else {
         hipLaunchKernelGGL(k_rs_hist, dim3((unsigned)nch), dim3(RS_NT), 0, ctx->stream, k, n, (u32)chunk, (u32)nch, matrix, sp, 0u);
@@ -223,7 +222,7 @@ int msd_sort_pairs(dskgpu_ctx* ctx, u64* k, u32* v, u64* tk, u32* tv, u64 n, int
 // ctx->rs.ovs for the caller's next round; a heavy first-digit bucket or a full list raises SC_SORTFLAG.  k holds a complete
 // permutation of the rows either way.
 // spr: step A reads the rows in the count kernel's regions (+ a dense tail: the rows of the k-mers counted apart), as in msd_sort_pairs
-int msd_sort_rows2(dskgpu_ctx* ctx, Rows2 k, Rows2 t, u64 n, int total, bool reset_flags, u32 base, const dskgpu_ctx::SparseRows2* spr = nullptr) {
+int msd_sort_rows2(dskgpu_ctx* ctx, Rows2 k, Rows2 t, u64 n, int total, bool reset_flags, u32 base, const SparseRows* spr = nullptr) {
     int wantB = n <= (96ull << 20) ? 8 : n <= (192ull << 20) ? 9 : 10;
     if (ctx->tune.rs_bbits >= 8 && ctx->tune.rs_bbits <= 10) wantB = (int)ctx->tune.rs_bbits;      // tests
     const int bA = std::min(RS2_ABITS, total), r1 = total - bA, bB = std::min(wantB, r1), r2 = r1 - bB, bC = std::min(8, r2), r3 = r2 - bC;
@@ -232,18 +231,7 @@ int msd_sort_rows2(dskgpu_ctx* ctx, Rows2 k, Rows2 t, u64 n, int total, bool res
     const u64 ncu = (u64)ctx->num_cu;
     u64 chunk, nch = step_a_chunks(n, ncu, RS2_TILE, &chunk);
     Rs2Sparse sps{}; u64 nch_sp = 0;
-    if (spr) {      // chunks = groups of qpc consecutive sub-partitions (about 64 K rows, at most RS_SP_MAXQ of them) + one chunk for the dense tail
-        sps = spr->s;
-        const u64 F = sps.F;
-        u64 want = std::max<u64>(1, (spr->n_sparse + 65535) / 65536);
-        want = (want + ncu - 1) / ncu * ncu;
-        u64 qpc = std::max<u64>(1, (F + want - 1) / want);
-        if (qpc > RS_SP_MAXQ) qpc = RS_SP_MAXQ;
-        nch_sp = (F + qpc - 1) / qpc;
-        sps.qpc = (u32)qpc;
-        nch = nch_sp + (spr->n_tail ? 1 : 0);
-        chunk = spr->n_tail;
-    }
+    if (spr) { u32 qpc; nch = step_a_chunks_sparse(spr->F, spr->n_sparse, spr->n_tail, ncu, &qpc, &nch_sp, &chunk); sps = spr->as<Rs2Sparse>(qpc); }
     const u64 M = (u64)RS2_ABINS * nch;
     const u64 nsubw = (u64)RS2_ABINS * (BB + 1);
     CK(ctx->srt_tmp.ensure((M + 2 + 2 * nsubw + 16) * 4));
@@ -264,11 +252,11 @@ int msd_sort_rows2(dskgpu_ctx* ctx, Rows2 k, Rows2 t, u64 n, int total, bool res
         const size_t ldsS = ldsA + ((size_t)RS_SP_MAXQ + 1) * 4;
         { const int e = allow_big_lds(ctx, reinterpret_cast<const void*>(&k2_scatter_sp)); if (e) return e; }
         hipLaunchKernelGGL(k2_hist_sp, dim3((unsigned)nch_sp), dim3(RS_NT), 0, ctx->stream, sps, (u32)nch, matrix, sp);
-        if (spr->n_tail) hipLaunchKernelGGL(k2_hist, dim3(1), dim3(RS_NT), 0, ctx->stream, spr->tail, (u64)spr->n_tail, (u32)chunk, (u32)nch, matrix, sp, (u32)nch_sp);
+        if (spr->n_tail) hipLaunchKernelGGL(k2_hist, dim3(1), dim3(RS_NT), 0, ctx->stream, spr->tail2(), (u64)spr->n_tail, (u32)chunk, (u32)nch, matrix, sp, (u32)nch_sp);
         CKL("k2_hist_sp");
         { const int e = run_scan(ctx, matrix, sc + SC_RSLEN, M); if (e) return e; }
         hipLaunchKernelGGL(k2_scatter_sp, dim3((unsigned)nch_sp), dim3(RS_NT), ldsS, ctx->stream, sps, (u32)nch, (const u32*)matrix, t, sp);
-        if (spr->n_tail) hipLaunchKernelGGL(k2_scatter<false>, dim3(1), dim3(RS_NT), ldsA, ctx->stream, spr->tail, (u64)spr->n_tail, (u32)chunk, (u32)nch, matrix, t, sp, (const u64*)nullptr, (u32)nch_sp);
+        if (spr->n_tail) hipLaunchKernelGGL(k2_scatter<false>, dim3(1), dim3(RS_NT), ldsA, ctx->stream, spr->tail2(), (u64)spr->n_tail, (u32)chunk, (u32)nch, matrix, t, sp, (const u64*)nullptr, (u32)nch_sp);
         CKL("k2_scatter_sp");
     } else {
         hipLaunchKernelGGL(k2_hist, dim3((unsigned)nch), dim3(RS_NT), 0, ctx->stream, kc, n, (u32)chunk, (u32)nch, matrix, sp, 0u);
@@ -323,13 +311,13 @@ int rows2_rounds(dskgpu_ctx* ctx, Rows2 R, Rows2 S) {
 
 // two-word rows, <= RS_MAX_ROWS: out_* ordered in place; the sub-buckets the sort lists go round again on their remaining bits,
 // range by range (a handful on real reads; each round consumes 26-28 bits: at most ceil(128 / 18) rounds).  Leaves the flag
-// read-back to order_rows like the other sorts (the full-width fallback reads out_*)
-int sort_rows2_msd(dskgpu_ctx* ctx, u64 n, Round* r) {
+// read-back to order_rows like the other sorts (the full-width fallback reads out_*).  spr: the rows are still sparse (step A reads them there)
+int sort_rows2_msd(dskgpu_ctx* ctx, u64 n, Round* r, const SparseRows* spr = nullptr) {
     for (int x = 0; x < 2; ++x) CK(ctx->srt_w[x].ensure(n * 8));
     CK(ctx->srt_ab.ensure(n * 4));
     const Rows2 K{ctx->out_w[1].as<u64>(), ctx->out_w[0].as<u64>(), ctx->out_ab.as<u32>()};
     const Rows2 T{ctx->srt_w[1].as<u64>(), ctx->srt_w[0].as<u64>(), ctx->srt_ab.as<u32>()};
-    { const int e = msd_sort_rows2(ctx, K, T, n, 2 * (int)ctx->cfg.kmer_size, true, 0u, ctx->sp_rows2.valid ? &ctx->sp_rows2 : nullptr); ctx->sp_rows2.valid = false; if (e) return e; }
+    { const int e = msd_sort_rows2(ctx, K, T, n, 2 * (int)ctx->cfg.kmer_size, true, 0u, spr); if (e) return e; }
     { const int e = rows2_rounds(ctx, K, T); if (e) return e; }
     r->back = 2; r->partial = true;
     return DSKGPU_OK;
@@ -396,12 +384,11 @@ int sort_rows2_big(dskgpu_ctx* ctx, u64 n, Round* r) {
     return DSKGPU_OK;
 }
 
-// one-word rows: out_* ordered in place (srt_* = scratch and, for the fallback, a complete permutation of the rows)
-int sort_rows_msd(dskgpu_ctx* ctx, u64 n, Round* r) {
+// one-word rows: out_* ordered in place (srt_* = scratch and, for the fallback, a complete permutation of the rows).  spr: as above
+int sort_rows_msd(dskgpu_ctx* ctx, u64 n, Round* r, const SparseRows* spr = nullptr) {
     CK(ctx->srt_w[0].ensure(n * 8)); CK(ctx->srt_ab.ensure(n * 4));
     const int e = msd_sort_pairs(ctx, ctx->out_w[0].as<u64>(), ctx->out_ab.as<u32>(), ctx->srt_w[0].as<u64>(), ctx->srt_ab.as<u32>(), n,
-                                 (int)std::min(64u, 2u * ctx->cfg.kmer_size), true, 0u, ctx->sp_rows.valid ? &ctx->sp_rows : nullptr);
-    ctx->sp_rows.valid = false; ctx->sp_rows2.valid = false;
+                                 (int)std::min(64u, 2u * ctx->cfg.kmer_size), true, 0u, spr);
     if (e) return e;
     r->back = 1; r->partial = true;      // (flag and sub-bucket count travel with the histogram)
     r->k = ctx->out_w[0].as<u64>(); r->v = ctx->out_ab.as<u32>();
@@ -689,7 +676,7 @@ int sort_rows_huge(dskgpu_ctx* ctx, u64 n) {
 }  // namespace
 
 // ---- DSKGPU_F_PARTITION_ORDER: the rows of a single pass, ordered inside output partitions of <= PS_CAP / PS2_CAP / PS4_CAP rows (one- / two- /
-// four-word rows) by one LDS pass (partsort.h).  In: the sparse rows (ctx->sp_rows / sp_rows2 / sp_rows4).  Out: dense, partition after
+// four-word rows) by one LDS pass (partsort.h).  In: the sparse rows of the pass (SparseRows).  Out: dense, partition after
 // partition -- srt_w[] / srt_ab, four-word rows in out_w[] / out_ab (where sort_rows4 expects its input, should a block give up);
 // part_off on the device and (after the caller's synchronisation) in h_part_off; SC_SORTFLAG raised when a block could not order its partition.
 // rows a block orders, and the sub-partitions per output partition / the partitions for F sub-partitions holding n_sparse rows (+ a tail)
@@ -698,40 +685,31 @@ static u32 part_sort_qpp(int W, u64 F, u64 n_sparse) {
     const u64 mean = std::max<u64>(1, (n_sparse + F - 1) / std::max<u64>(F, 1));
     return (u32)std::min<u64>(std::max<u64>(1, (part_sort_cap(W) * 3 / 4) / mean), PS_MAXQ);
 }
-// one launch: the sparse rows `spr` / `spr2` / `spr4` (W = 1 / 2 / 4) -> dense rows at ov / o2 / o4, partition offsets (relative to the first row) at
-// d_part_off[0 .. *nparts], *d_flag raised when a block could not order its partition (the rows are complete either way)
-int launch_part_sort(dskgpu_ctx* ctx, int W, const dskgpu_ctx::SparseRows& spr, const dskgpu_ctx::SparseRows2& spr2, const dskgpu_ctx::SparseRows4& spr4,
-                     u64* ov, u32* oab, Rows2 o2, RowsOut o4, u32* d_part_off, u32* d_flag, u32* nparts_out, u32* qpp_out) {
-    const u64 F = W == 1 ? spr.s.F : W == 2 ? spr2.s.F : spr4.s.F, n_sparse = W == 1 ? spr.n_sparse : W == 2 ? spr2.n_sparse : spr4.n_sparse;
-    const u32 n_tail = W == 1 ? spr.n_tail : W == 2 ? spr2.n_tail : 0u;
-    const u32 qpp = part_sort_qpp(W, F, n_sparse);
-    const u32 nps = (u32)((F + qpp - 1) / qpp), nparts = nps + (n_tail ? 1u : 0u);
-    const int sh = std::max(0, 2 * (int)ctx->cfg.kmer_size - 12);
-    const PsParams pp{qpp, nps, W == 1 ? std::min(sh, 52) : sh, n_tail, ctx->tune.ps_maxc ? std::min<u32>(ctx->tune.ps_maxc, PS_MAXC) : PS_MAXC};
-    if (W == 1) hipLaunchKernelGGL(k_part_sort, dim3(nparts), dim3(PS_NT), 0, ctx->stream, spr.s, spr.tail_k, spr.tail_v, pp, ov, oab, d_part_off, d_flag);
-    else if (W == 2) hipLaunchKernelGGL(k_part_sort2, dim3(nparts), dim3(PS_NT), 0, ctx->stream, spr2.s, spr2.tail, pp, o2, d_part_off, d_flag);
-    else hipLaunchKernelGGL(k_part_sort4, dim3(nparts), dim3(PS_NT), 0, ctx->stream, spr4.s, pp, o4, oab, d_part_off, d_flag);
-    CKL("k_part_sort");
-    *nparts_out = nparts; if (qpp_out) *qpp_out = qpp;
-    return DSKGPU_OK;
+// partitions a launch will make of `rows`
+u32 part_sort_nparts(const SparseRows& rows) {
+    const u32 qpp = part_sort_qpp(rows.W, rows.F, rows.n_sparse);
+    return (u32)((rows.F + qpp - 1) / qpp) + (rows.n_tail ? 1u : 0u);
 }
-
-// partitions a launch will make for F sub-partitions holding n_sparse rows (+ a tail)
-u32 part_sort_nparts(int W, u64 F, u64 n_sparse, u32 n_tail) {
-    const u32 qpp = part_sort_qpp(W, F, n_sparse);
-    return (u32)((F + qpp - 1) / qpp) + (n_tail ? 1u : 0u);
+// one launch: the sparse rows -> dense rows at out / out_ab, partition offsets (relative to the first row) at d_part_off[0 .. *nparts],
+// *d_flag raised when a block could not order its partition (the rows are complete either way)
+int launch_part_sort(dskgpu_ctx* ctx, const SparseRows& rows, RowsOut out, u32* out_ab, u32* d_part_off, u32* d_flag, u32* nparts_out) {
+    const int W = rows.W;
+    const u32 qpp = part_sort_qpp(W, rows.F, rows.n_sparse), nparts = part_sort_nparts(rows), nps = nparts - (rows.n_tail ? 1u : 0u);
+    const int sh = std::max(0, 2 * (int)ctx->cfg.kmer_size - 12);
+    const PsParams pp{qpp, nps, W == 1 ? std::min(sh, 52) : sh, rows.n_tail, ctx->tune.ps_maxc ? std::min<u32>(ctx->tune.ps_maxc, PS_MAXC) : PS_MAXC};
+    if (W == 1) hipLaunchKernelGGL(k_part_sort, dim3(nparts), dim3(PS_NT), 0, ctx->stream, rows.as<RsSparse>(), rows.tail_w.w[0], rows.tail_ab, pp, out.w[0], out_ab, d_part_off, d_flag);
+    else if (W == 2) hipLaunchKernelGGL(k_part_sort2, dim3(nparts), dim3(PS_NT), 0, ctx->stream, rows.as<Rs2Sparse>(), rows.tail2(), pp, Rows2{out.w[1], out.w[0], out_ab}, d_part_off, d_flag);
+    else hipLaunchKernelGGL(k_part_sort4, dim3(nparts), dim3(PS_NT), 0, ctx->stream, rows.as<Rs4Sparse>(), pp, out, out_ab, d_part_off, d_flag);
+    CKL("k_part_sort");
+    *nparts_out = nparts;
+    return DSKGPU_OK;
 }
 
 namespace {
 
-int sort_rows_partition_order(dskgpu_ctx* ctx, u64 n, Round* r) {
-    const int W = ctx->W;
-    const dskgpu_ctx::SparseRows spr = ctx->sp_rows;
-    const dskgpu_ctx::SparseRows2 spr2 = ctx->sp_rows2;
-    const dskgpu_ctx::SparseRows4 spr4 = ctx->sp_rows4;
-    ctx->sp_rows.valid = false; ctx->sp_rows2.valid = false; ctx->sp_rows4.valid = false;
-    const u32 nparts = part_sort_nparts(W, W == 1 ? spr.s.F : W == 2 ? spr2.s.F : spr4.s.F, W == 1 ? spr.n_sparse : W == 2 ? spr2.n_sparse : spr4.n_sparse,
-                                        W == 1 ? spr.n_tail : W == 2 ? spr2.n_tail : 0u);
+int sort_rows_partition_order(dskgpu_ctx* ctx, const SparseRows& rows, u64 n, Round* r) {
+    const int W = rows.W;
+    const u32 nparts = part_sort_nparts(rows);
     // four-word rows go to out_* (pass_rows sized them for the pass's rows; nothing else is in them while the rows are sparse): the
     // retry in global order, sort_rows4, finds a complete dense copy of the rows where it reads its input
     DevBuf* dst_w = W == 4 ? ctx->out_w : ctx->srt_w;
@@ -743,10 +721,9 @@ int sort_rows_partition_order(dskgpu_ctx* ctx, u64 n, Round* r) {
     u32* sc = ctx->scalars.as<u32>();
     hipLaunchKernelGGL(k_set_rs_scalars, dim3(1), dim3(64), 0, ctx->stream, sc + SC_RSLEN, 0u, 1u, sc + SC_SORTFLAG, (u32*)nullptr);
     u32 np = 0;
-    RowsOut o4{};
-    if (W == 4) for (int x = 0; x < 4; ++x) o4.w[x] = dst_w[x].as<u64>();
-    { const int rc = launch_part_sort(ctx, W, spr, spr2, spr4, dst_w[0].as<u64>(), dst_ab.as<u32>(), Rows2{W == 2 ? dst_w[1].as<u64>() : nullptr, dst_w[0].as<u64>(), dst_ab.as<u32>()}, o4,
-                                      ctx->rs.part_off.as<u32>(), sc + SC_SORTFLAG, &np, nullptr); if (rc) return rc; }
+    RowsOut out{};
+    for (int x = 0; x < W; ++x) out.w[x] = dst_w[x].as<u64>();
+    { const int rc = launch_part_sort(ctx, rows, out, dst_ab.as<u32>(), ctx->rs.part_off.as<u32>(), sc + SC_SORTFLAG, &np); if (rc) return rc; }
     CK(hipMemcpyAsync(ctx->rs.h_part_off, ctx->rs.part_off.p, ((size_t)nparts + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
     ctx->rs.part_mode = true; ctx->rs.n_parts = nparts; ctx->rs.h_part_off64.clear();
     r->back = 2;            // (the flag travels with the histogram)
@@ -820,8 +797,9 @@ int sort_rows4(dskgpu_ctx* ctx, u64 n, Round* r) {
     return DSKGPU_OK;
 }
 
-// ---- the first round of a row sort: the path for (W, n, flags, switches), which order_rows finishes
-int sort_rows(dskgpu_ctx* ctx, u64 n, bool global, Round* r) {
+// ---- the first round of a row sort: the path for (W, n, flags, switches), which order_rows finishes.  rows: where the rows lie while they are
+// still sparse (W = 0: dense in out_*)
+int sort_rows(dskgpu_ctx* ctx, u64 n, const SparseRows& rows, bool global, Round* r) {
     const int W = ctx->W;
     for (int x = 0; x < 4; ++x) ctx->res_w[x] = x < W ? ctx->out_w[x].as<u64>() : nullptr;
     ctx->res_ab = ctx->out_ab.as<u32>();
@@ -829,13 +807,12 @@ int sort_rows(dskgpu_ctx* ctx, u64 n, bool global, Round* r) {
     ctx->rs.listed = 0;
     // (four-word rows have one sparse reader, the partition-order pass: sparse rows that it will not take are an error, not a quiet detour)
     const bool part = (ctx->cfg.flags & DSKGPU_F_PARTITION_ORDER) && !global && n < 0xFFFF0000ull;
-    if ((ctx->sp_rows.valid && (n == 0 || (ctx->cfg.flags & DSKGPU_F_NO_SORT) || W != 1)) || (ctx->sp_rows2.valid && (n == 0 || (ctx->cfg.flags & DSKGPU_F_NO_SORT) || W != 2)) ||
-        (ctx->sp_rows4.valid && (n == 0 || (ctx->cfg.flags & DSKGPU_F_NO_SORT) || W != 4 || !part)))
+    if (rows.W && (n == 0 || (ctx->cfg.flags & DSKGPU_F_NO_SORT) || rows.W != W || (W == 4 && !part)))
         return fail(ctx, DSKGPU_E_STATE, "row sort: sparse rows on a path that cannot read them");
     if (n == 0 || (ctx->cfg.flags & DSKGPU_F_NO_SORT)) return DSKGPU_OK;
-    if ((ctx->sp_rows.valid || ctx->sp_rows2.valid || ctx->sp_rows4.valid) && part) return sort_rows_partition_order(ctx, n, r);
-    if (ctx->sp_rows.valid) return sort_rows_msd(ctx, n, r);      // the rows of a single one-word pass, still in the count kernel's regions (run_one_pass made sure this sort takes them)
-    if (ctx->sp_rows2.valid) return sort_rows2_msd(ctx, n, r);    // (the two-word twin)
+    if (rows.W && part) return sort_rows_partition_order(ctx, rows, n, r);
+    if (rows.W == 1) return sort_rows_msd(ctx, n, r, &rows);      // the rows of a single one-word pass, still in the count kernel's regions (pass_rows made sure this sort takes them)
+    if (rows.W == 2) return sort_rows2_msd(ctx, n, r, &rows);     // (the two-word twin)
     const u64 rs_max = rs_max_rows(ctx);
     // 2^32 rows and more (or DSKGPU_RS_SLAB_ROWS: tests): step A slab by slab with 64-bit bucket offsets
     if ((n >= 0xFFFF0000ull || ctx->tune.rs_slab_rows) && W <= 2 && (W == 1 || 2u * ctx->cfg.kmer_size > 64u)) return W == 1 ? sort_rows_huge<1>(ctx, n) : sort_rows_huge<2>(ctx, n);
@@ -851,39 +828,40 @@ int sort_rows(dskgpu_ctx* ctx, u64 n, bool global, Round* r) {
 }  // namespace
 
 // ---- the row order of a count: the n solid rows in out_* (npass > 1: the job's rows, each pass's partitions already ordered when
-// ctx->mp_part_ok held) -> ctx->res_* ascending, globally or inside the partitions of ctx->rs (DSKGPU_F_PARTITION_ORDER).  Finishes
+// ctx->rs.mp.ok held) -> ctx->res_* ascending, globally or inside the partitions of ctx->rs (DSKGPU_F_PARTITION_ORDER).  Finishes
 // what the first round left (k_sort_back's read-back, the listed sub-buckets, the full-width library fallback: stats.sort_fallback)
 // and, for a single pass (hist_back), copies the abundance histogram to ctx->hist with the same read-back.  Synchronous.
 int order_rows(dskgpu_ctx* ctx, u64 n, u32 npass) {
     const int W = ctx->W;
     RowSort& rs = ctx->rs;
+    PartPasses& mp = rs.mp;
+    // the rows of a single pass where the count kernel left them (W = 0: dense in out_*).  The partition order's retry in global order reads the
+    // same sparse rows, except four-word ones: sort_rows4 reads the dense rows the partition pass left in out_*
+    const SparseRows sparse = ctx->take_sparse_rows();
     // partition order over all passes: every pass ordered its partitions on the way in -- nothing left to sort unless a block gave up
-    if (npass > 1 && ctx->mp_part_ok && !ctx->mp_parts.empty()) {
+    if (npass > 1 && mp.ok && !mp.passes.empty()) {
         u32 h_flag = 1;
-        ctx->h_mp_off.resize(ctx->mp_off_used);
-        CK(hipMemcpyAsync(&h_flag, ctx->mp_flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-        CK(hipMemcpyAsync(ctx->h_mp_off.data(), ctx->mp_part_off.p, (size_t)ctx->mp_off_used * 4, hipMemcpyDeviceToHost, ctx->stream));
+        mp.h_off.resize(mp.off_used);
+        CK(hipMemcpyAsync(&h_flag, mp.flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+        CK(hipMemcpyAsync(mp.h_off.data(), mp.part_off.p, (size_t)mp.off_used * 4, hipMemcpyDeviceToHost, ctx->stream));
         CK(hipStreamSynchronize(ctx->stream));
         if (!h_flag) {
             rs.h_part_off64.clear();
-            for (const auto& mp : ctx->mp_parts)
-                for (u32 i = 0; i < mp.nparts; ++i) rs.h_part_off64.push_back(mp.row_base + ctx->h_mp_off[mp.off_index + i]);
+            for (const auto& pass : mp.passes)
+                for (u32 i = 0; i < pass.nparts; ++i) rs.h_part_off64.push_back(pass.row_base + mp.h_off[pass.off_index + i]);
             rs.h_part_off64.push_back(n);
             rs.part_mode = true; rs.n_parts = (u32)(rs.h_part_off64.size() - 1);
             for (int x = 0; x < 4; ++x) ctx->res_w[x] = x < W ? ctx->out_w[x].as<u64>() : nullptr;
             ctx->res_ab = ctx->out_ab.as<u32>();
-            ctx->sp_rows.valid = false; ctx->sp_rows2.valid = false; ctx->sp_rows4.valid = false;
             rs.flag = 0; rs.listed = 0;
             return DSKGPU_OK;
         }
         if (ctx->tune.verbose) fprintf(stderr, "[dskgpu] row order: a partition of one pass exceeds what one block orders -- global order over all passes instead\n");
     }
-    const dskgpu_ctx::SparseRows sp_rows = ctx->sp_rows;      // (the partition order's retry in global order reads the same sparse rows)
-    const dskgpu_ctx::SparseRows2 sp_rows2 = ctx->sp_rows2;
     bool global = false;
     for (;;) {
         Round r;
-        int rc = sort_rows(ctx, n, global, &r);
+        int rc = sort_rows(ctx, n, global && sparse.W == 4 ? SparseRows{} : sparse, global, &r);
         if (rc) return rc;
         ctx->mark("sort");
         const size_t nh = ctx->hist.size();
@@ -905,7 +883,6 @@ int order_rows(dskgpu_ctx* ctx, u64 n, u32 npass) {
         if (rs.part_mode && rs.flag) {      // a partition (or a value bin of one) above what a block orders in LDS: the global sort, on the same sparse rows
             if (ctx->tune.verbose) fprintf(stderr, "[dskgpu] row sort: a partition exceeds what one block orders -- global order instead of partition order\n");
             rs.part_mode = false; rs.flag = 0;
-            ctx->sp_rows = sp_rows; ctx->sp_rows2 = sp_rows2;      // (four-word rows: the partition pass left them dense in out_*, sort_rows4's input)
             global = true;
             continue;
         }

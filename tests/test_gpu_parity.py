@@ -1638,8 +1638,9 @@ def test_partition_order_is_the_reference_contract(oracle, golden_dir, dev, monk
     output partition, partition after partition (utils/dsk2ascii.cpp:61,77,85-104) -- from one pass over the rows instead of the
     three of the global order.  Checked: same multiset of (k-mer, abundance) rows and same histogram as the oracle, every
     partition strictly ascending, no partition above what a block orders, the partition sizes add up; a partition / value bin a
-    block cannot order (provoked: DSKGPU_PS_MAXC=1) takes the global sort and the rows come out globally ascending; paths the flag
-    does not cover (k > 64, several passes) keep the global order."""
+    block cannot order (provoked: DSKGPU_PS_MAXC=1) takes the global sort and the rows come out globally ascending, for one- and
+    two-word rows alike; the passes of a multi-pass count order their partitions one pass after the other; four-word rows (k > 64)
+    take the flag too (their order: test_gpu_partition_order_wide.py)."""
     from dsk_amd import KmerCounter, synth
     g = synth.make_genome(600_000, dev)
     reads = synth.make_reads(g, 250_000, 150)
@@ -1713,11 +1714,18 @@ def test_partition_order_is_the_reference_contract(oracle, golden_dir, dev, monk
         inside = np.ones(len(asc), dtype=bool); inside[starts[(starts > 0) & (starts <= len(asc))] - 1] = False
         assert asc[inside].all() and not asc.all(), (k, amin)
     check(skew, 63, 1, expect_parts=None)
+    monkeypatch.setenv("DSKGPU_PS_MAXC", "1")                      # two-word rows whose blocks give up: the global sort reads the same sparse rows
+    kk, ab, sizes, hist, st = run(reads.cpu().numpy(), 63, 1)
+    monkeypatch.delenv("DSKGPU_PS_MAXC")
+    ref = oracle.count(reads.cpu().numpy(), 63)
+    assert (kk == ref.words()).all() and (ab == ref.ab).all() and (hist == ref.histogram(10000)).all()
+    assert ((kk[1:, 1] > kk[:-1, 1]) | ((kk[1:, 1] == kk[:-1, 1]) & (kk[1:, 0] > kk[:-1, 0]))).all(), "global order expected"
+    assert st["n_partitions"] == 4 and sizes.sum() == kk.shape[0] == st["n_solid"], st
     kk, ab, sizes, hist, st = run(reads.cpu().numpy(), 63, 1, max_pass_mkeys=2)          # two-word rows, several passes
     ref = oracle.count(reads.cpu().numpy(), 63)
     order = np.lexsort(kk.T)
     assert st["n_passes"] > 4 and (kk[order] == ref.words()).all() and (ab[order] == ref.ab).all() and sizes.max() <= 2048 and len(sizes) > 4 * st["n_passes"]
-    check(reads.cpu().numpy(), 101, 2, expect_parts=None)                        # four-word rows: not covered by the flag, global order
+    check(reads.cpu().numpy(), 101, 2, expect_parts=None)                        # four-word rows: partition order as well (rows and histogram here, the order in test_gpu_partition_order_wide.py)
 
 
 def test_multi_pass_count_leaves_the_sender_state_alone(oracle, dev):
