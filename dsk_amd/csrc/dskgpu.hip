@@ -139,17 +139,7 @@ int run_encode(dskgpu_ctx* ctx, const uint8_t* d_bytes, u64 n, u64* nwords_out) 
     ctx->enc_fresh = false;
     CK(ctx->packed.ensure((nwords + 1) * 8));
     CK(ctx->inval.ensure((nwords + 1) * 4));
-    if (nwords) {
-        const u64 nb = (nwords + 255) / 256;
-        const unsigned grid = (unsigned)std::min<u64>(nb, (u64)ctx->num_cu * 16);
-        if ((reinterpret_cast<uintptr_t>(d_bytes) & 15) == 0)
-            hipLaunchKernelGGL(k_encode<true>, dim3(grid), dim3(256), 0, ctx->stream, d_bytes, n,
-                               ctx->packed.as<u64>(), ctx->inval.as<u32>(), nwords);
-        else
-            hipLaunchKernelGGL(k_encode<false>, dim3(grid), dim3(256), 0, ctx->stream, d_bytes, n,
-                               ctx->packed.as<u64>(), ctx->inval.as<u32>(), nwords);
-        CKL("k_encode");
-    }
+    if (const int rc = encode_into(ctx, d_bytes, n, ctx->packed.as<u64>(), ctx->inval.as<u32>())) return rc;
     *nwords_out = nwords;
     return DSKGPU_OK;
 }
@@ -162,6 +152,20 @@ int encode_current(dskgpu_ctx* ctx, u64* nwords_out) {
 }
 
 }  // namespace
+
+// ---- K1 into buffers of the caller's choice: the context's own (run_encode) or a query's (query.hip)
+int encode_into(dskgpu_ctx* ctx, const uint8_t* d_bytes, u64 n, u64* packed, u32* inval) {
+    const u64 nwords = (n + 31) / 32;
+    if (!nwords) return DSKGPU_OK;
+    const u64 nb = (nwords + 255) / 256;
+    const unsigned grid = (unsigned)std::min<u64>(nb, (u64)ctx->num_cu * 16);
+    if ((reinterpret_cast<uintptr_t>(d_bytes) & 15) == 0)
+        hipLaunchKernelGGL(k_encode<true>, dim3(grid), dim3(256), 0, ctx->stream, d_bytes, n, packed, inval, nwords);
+    else
+        hipLaunchKernelGGL(k_encode<false>, dim3(grid), dim3(256), 0, ctx->stream, d_bytes, n, packed, inval, nwords);
+    CKL("k_encode");
+    return DSKGPU_OK;
+}
 
 // ---- scan launcher: exclusive scan of a[0..*d_len) in place, total -> a[*d_len]
 int run_scan(dskgpu_ctx* ctx, u32* a, const u32* d_len, u64 max_len) {
@@ -1401,7 +1405,7 @@ int rec_l0_sweep(dskgpu_ctx* ctx, const RecL0& rl, u32 olo, u32 ohi, u64 (&base_
 template <int W>
 int run_pipeline(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_keys_in, u64 nkeys_in) {
     typedef typename KeyT<W>::T Key;
-    ctx->have_result = false;
+    ctx->drop_result();
     ctx->sink = dskgpu_ctx::RowSink{};
     if (from_reads) { ctx->st_names.clear(); ctx->st_ms.clear(); }   // from keys: keep the mg_scatter stages of this step
     ctx->marks.clear(); ctx->ev_used = 0;
@@ -1909,7 +1913,7 @@ int sk_count(dskgpu_ctx* ctx, const u64* d_rec, u64 recv_words, u64 n_kmers_hint
     if (rc == REC_RESIZE) { ctx->rec_hint_est = false; rc = run_pipeline<W>(ctx, false, nullptr, ctx->rec_hint); ctx->rec_hint = 0; }
     ctx->rec_src = nullptr;
     if (rc == DSKGPU_OK && ctx->rec_hint && !ctx->rec_hint_est && ctx->stats.n_kmers != ctx->rec_hint) {
-        ctx->have_result = false;
+        ctx->drop_result();
         return fail(ctx, DSKGPU_E_ARG, "dskgpu_mg_count_sized: n_kmers does not match the k-mers inside the records");
     }
     return rc;
@@ -1980,7 +1984,7 @@ int banks_finish(dskgpu_ctx* ctx) {
     const u32 B = (u32)j.ends.size();
     const u64 nu = j.nu, total = j.total, tot_kmers = j.tot_kmers; const u32 passes = j.passes, retries = j.retries;
     banks_abort(ctx);                          // configuration and read stream back
-    ctx->have_result = false;
+    ctx->drop_result();
     int rc = DSKGPU_OK;
     if (nu >= 0xFFFF0000ull) return fail(ctx, DSKGPU_E_ARG, "too many distinct k-mers over the banks for the merge");
     // ---- sort the union by k-mer
@@ -2157,6 +2161,7 @@ void dskgpu_destroy(dskgpu_ctx* ctx) {
                       &ctx->sk_sums, &ctx->sk_cbase, &ctx->sk_keys, &ctx->sk_table, &ctx->sk_load, &ctx->sk_sent, &ctx->cur_state, &ctx->smp_keys, &ctx->sk_lay, &ctx->sk_cb64, &ctx->back_dev};
     if (ctx->back_host) (void)hipHostFree(ctx->back_host);
     ctx->rs.release();
+    ctx->query.release();
     if (ctx->land) (void)hipHostFree(ctx->land);
     for (DevBuf* b : bufs) b->release();
     for (int i = 0; i < 4; ++i) { ctx->out_w[i].release(); ctx->srt_w[i].release(); ctx->acc_w[i].release(); ctx->u_w[i].release(); ctx->s_w[i].release(); }
@@ -2604,7 +2609,7 @@ int dskgpu_mg_count_sliced(dskgpu_ctx* ctx, const void* d_recv, uint32_t nslices
                          : sk_count<2>(ctx, static_cast<const u64*>(d_recv), words, n_kmers_est, true);
     const std::string err = ctx->err;
     (void)rec_gate_all(ctx);                             // (an error path may have left early: the caller's gates are all passed when this returns)
-    if (ctx->rec_gate_failed) { ctx->have_result = false; if (rc == DSKGPU_OK) rc = DSKGPU_E_STATE; else ctx->err = err; }
+    if (ctx->rec_gate_failed) { ctx->drop_result(); if (rc == DSKGPU_OK) rc = DSKGPU_E_STATE; else ctx->err = err; }
     ctx->rec_gate = nullptr; ctx->rec_gate_user = nullptr; ctx->rec_slice_end.clear();
     return rc;
 }

@@ -1,6 +1,7 @@
-// engine.h -- what the two host translation units of libdskgpu share: the context (dskgpu_ctx) with its buffers and switches,
+// engine.h -- what the host translation units of libdskgpu share: the context (dskgpu_ctx) with its buffers and switches,
 // the error macros, and the functions one of them calls in the other.  dskgpu.hip runs the count path and the C-ABI;
-// rowsort.hip orders the solid rows (order_rows) and owns the row sort's state (dskgpu_ctx::rs).  Private to the library.
+// rowsort.hip orders the solid rows (order_rows) and owns the row sort's state (dskgpu_ctx::rs); query.hip answers lookups in the
+// last result (dskgpu_query_*) and owns dskgpu_ctx::query.  Private to the library.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -130,6 +131,16 @@ struct RowSort {
     }
 };
 
+// Lookups in the last result (query.hip): one open-addressing hash table over the result rows, built on the first query after a count.
+// A slot is (fingerprint << 32 | row number), all ones = empty; cap is a power of two >= 2 * rows.  packed / inval: the 2-bit form of the
+// QUERIED stream (dskgpu_query_reads) -- buffers of the query's own, so that the context's reads and their kept encoding stay untouched.
+struct Query {
+    DevBuf table, packed, inval;
+    u64 cap = 0;
+    bool valid = false;            // the table indexes the current result (dskgpu_ctx::drop_result clears it)
+    void release() { table.release(); packed.release(); inval.release(); cap = 0; valid = false; }
+};
+
 // state of a per-bank count in steps (banks_begin .. banks_finish below)
 struct BankJob { dskgpu_config cfg; const uint8_t* base; u64 total; std::vector<u64> ends; u64 nu, tot_kmers; u32 passes, retries; bool active = false; };
 
@@ -223,6 +234,10 @@ struct dskgpu_ctx {
     const u64* res_w[4] = {nullptr, nullptr, nullptr, nullptr}; const u32* res_ab = nullptr;
     dskgpu_stats stats{};
     std::vector<u64> hist;
+    Query query;
+    // a count starts, or its result is not to be read: the index of the old rows goes with them, and so does its memory -- up to 32 bytes
+    // per row that the count about to run may need (a no-op for a context that was never queried)
+    void drop_result() { have_result = false; query.release(); }
 
     // timing
     std::vector<Stage> marks;
@@ -269,6 +284,7 @@ struct dskgpu_ctx {
 inline int fail(dskgpu_ctx* ctx, int code, const std::string& msg) { ctx->err = msg; return code; }
 
 // dskgpu.hip
+int encode_into(dskgpu_ctx* ctx, const uint8_t* d_bytes, u64 n, u64* packed, u32* inval);      // k_encode of n bytes into (n + 31) / 32 words of the caller's buffers
 int run_scan(dskgpu_ctx* ctx, u32* a, const u32* d_len, u64 max_len);
 int allow_big_lds(dskgpu_ctx* ctx, const void* fn, int bytes = 160 * 1024);      // (bytes: kernels with static LDS next to the dynamic block ask for what they use)
 

@@ -88,7 +88,7 @@ EXPORTS = [
     "dskgpu_mg_send_capacity_words", "dskgpu_mg_count", "dskgpu_mg_sent_kmers", "dskgpu_mg_count_sized",
     "dskgpu_mg_slices_prepare", "dskgpu_mg_scatter_slice", "dskgpu_mg_slices_finish", "dskgpu_mg_count_sliced", "dskgpu_get_stats", "dskgpu_histogram",
     "dskgpu_set_row_order", "dskgpu_num_partitions", "dskgpu_partition_size", "dskgpu_partition_offsets", "dskgpu_partition_copy", "dskgpu_result_device",
-    "dskgpu_stage_times", "dskgpu_k_encode", "dskgpu_k_enumerate", "dskgpu_k_minimizers",
+    "dskgpu_stage_times", "dskgpu_query_prepare", "dskgpu_query_kmers", "dskgpu_query_reads", "dskgpu_k_encode", "dskgpu_k_enumerate", "dskgpu_k_minimizers",
     "dskgpu_group_create", "dskgpu_group_destroy", "dskgpu_group_last_error", "dskgpu_group_size", "dskgpu_group_ctx",
     "dskgpu_group_transport", "dskgpu_group_count", "dskgpu_group_exchanged_words", "dskgpu_group_sliced_steps", "dskgpu_group_histogram", "dskgpu_group_histogram2d",
     "dskgpu_group_get_stats", "dskgpu_group_num_partitions", "dskgpu_group_partition_size", "dskgpu_group_partition_copy",
@@ -163,6 +163,12 @@ def load_library():
     lib.dskgpu_partition_copy.argtypes = [vp, u32, vp, vp]
     lib.dskgpu_result_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(u64)]
     lib.dskgpu_stage_times.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int]
+    lib.dskgpu_query_prepare.argtypes = [vp]
+    lib.dskgpu_query_prepare.restype = C.c_int
+    lib.dskgpu_query_kmers.argtypes = [vp, vp, u64, vp]
+    lib.dskgpu_query_kmers.restype = C.c_int
+    lib.dskgpu_query_reads.argtypes = [vp, vp, u64, vp]
+    lib.dskgpu_query_reads.restype = C.c_int
     lib.dskgpu_k_encode.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_enumerate.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_minimizers.argtypes = [vp, vp, u64, vp, vp]
@@ -482,6 +488,45 @@ class KmerCounter:
         ms = (C.c_float * cap)()
         n = self._lib.dskgpu_stage_times(self._h, names, ms, cap)
         return [(names[i].decode(), float(ms[i])) for i in range(min(n, cap))]
+
+    # -- lookups in the last result (include/dskgpu.h: dskgpu_query_*)
+    def query_prepare(self) -> None:
+        """Build the lookup index of the last result now (the first query after a count builds it otherwise)."""
+        self._ck(self._lib.dskgpu_query_prepare(self._h))
+
+    def query_kmers(self, d_kmers: int, n: int, d_out: int) -> None:
+        """d_kmers: n values of `words` u64 each on the device (LSW first); d_out: n u32 on the device <- abundance, 0 = not a solid row."""
+        self._ck(self._lib.dskgpu_query_kmers(self._h, C.c_void_p(d_kmers), n, C.c_void_p(d_out)))
+
+    def query_reads(self, d_bytes: int, nbytes: int, d_out: int) -> None:
+        """d_bytes: a read stream on the device; d_out: nbytes u32 on the device <- abundance of the k-mer of the window ending at every byte, or 0."""
+        self._ck(self._lib.dskgpu_query_reads(self._h, C.c_void_p(d_bytes), nbytes, C.c_void_p(d_out)))
+
+    def query_kmers_tensor(self, kmers):
+        """kmers: CUDA tensor of n x `words` 64-bit values (int64 or uint64 bit patterns, LSW first; a 1-D tensor for words == 1).
+        -> int32 tensor of n abundances, to be viewed as u32 (.view(torch.uint32))."""
+        import torch
+        if not kmers.is_cuda or kmers.element_size() != 8:
+            raise ValueError("query_kmers_tensor: a CUDA tensor of 64-bit words is needed")
+        kmers = kmers.contiguous()
+        if kmers.numel() % self.words:
+            raise ValueError("query_kmers_tensor: %d words are not whole values of %d words" % (kmers.numel(), self.words))
+        n = kmers.numel() // self.words
+        out = torch.zeros(n, dtype=torch.int32, device=kmers.device)
+        torch.cuda.current_stream(kmers.device).synchronize()      # the context's stream is not torch's: what torch enqueued is done before the lookup reads it
+        self.query_kmers(kmers.data_ptr(), n, out.data_ptr())
+        return out
+
+    def query_reads_tensor(self, stream):
+        """stream: CUDA uint8 tensor holding a read stream.  -> int32 tensor, one abundance per byte (view as u32), 0 = no valid window / not a solid row."""
+        import torch
+        if not stream.is_cuda or stream.dtype != torch.uint8:
+            raise ValueError("query_reads_tensor: a CUDA uint8 tensor is needed")
+        stream = stream.contiguous()
+        out = torch.zeros(stream.numel(), dtype=torch.int32, device=stream.device)
+        torch.cuda.current_stream(stream.device).synchronize()
+        self.query_reads(stream.data_ptr(), stream.numel(), out.data_ptr())
+        return out
 
     # -- kernel-level entry points (parity tests)
     def k_encode(self, d_bytes: int, nbytes: int, d_packed: int, d_invalid: int) -> None:

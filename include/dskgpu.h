@@ -289,8 +289,37 @@ int dskgpu_partition_copy(const dskgpu_ctx* ctx, uint32_t p, uint64_t* kmers, ui
 int dskgpu_result_device(const dskgpu_ctx* ctx, const void** d_kmers, const void** d_abundance, uint64_t* n_rows);
 
 /* Per-stage device time of the last count (flag DSKGPU_F_TIMING).  Returns the
- * number of stages; fills up to `cap` entries.  names[i] are static strings. */
+ * number of stages; fills up to `cap` entries.  names[i] are static strings.  The lookups below add the stages "query index" and
+ * "query" (summed over the calls since the last count). */
 int dskgpu_stage_times(const dskgpu_ctx* ctx, const char** names, float* ms, int cap);
+
+/* ---- lookups in the last result: what the readers of `Partition<Count> "solid"` do with a count next -- how often does this k-mer, or
+ * every k-mer of this read, occur? (gatb-core's consumers iterate and probe the partitions; Jellyfish `query`, KMC `CheckKmer`).
+ * On the device, for every k (1..128) and every result a context can hold: either row order, one pass or several, DSKGPU_F_NO_SORT,
+ * the per-bank modes (the answer is whatever the row's abundance column holds), a rank's rows after dskgpu_mg_count* /
+ * dskgpu_group_count.  A rank's rows are the solid k-mers that rank owns and every k-mer has one owner, so the answer of a GROUP is the
+ * sum over the ranks of the per-rank answers, asked through dskgpu_group_ctx(g, r); there is no routed group query.
+ * The index is one hash table over the rows in HBM (8 bytes per slot, 2 .. 4 slots per row: 16 .. 32 bytes per row), built by the
+ * first query after a count or by dskgpu_query_prepare, dropped -- and its memory freed -- when the next count starts and by
+ * dskgpu_destroy; a query after the next count answers from the new rows.  A lookup costs two dependent memory accesses whatever
+ * the number of rows.  Limits: at most 2^32 - 2 rows (more: DSKGPU_E_STATE, the text says so); an index that does not fit in the
+ * free HBM: DSKGPU_E_NOMEM, and the context and its result stay usable.
+ * All three run on the context's stream and are synchronous on return.  Like dskgpu_k_*, they do not wait for other streams:
+ * bytes that another stream is still writing into d_kmers / d_bytes must be ordered by the caller.  A query changes nothing else in
+ * the context: the reads (a kept encoding of dskgpu_encode_reads included), the result, the stats and the sender state stay as they
+ * are -- count, query another stream, count again gives identical rows.
+ * Errors: no result DSKGPU_E_STATE; n / nbytes == 0: DSKGPU_OK, nothing is done; a null pointer DSKGPU_E_ARG.  A result with zero
+ * rows answers 0 everywhere. */
+/* Build the index now (optional: both calls below build it on first use). */
+int dskgpu_query_prepare(dskgpu_ctx* ctx);
+/* d_kmers: n k-mer values on the device, each `words` = ceil(k / 32) u64, row-major, least-significant word first -- the layout of
+ * dskgpu_partition_copy and dskgpu_k_enumerate.  d_abundance: n u32 on the device; out[i] = abundance of the solid row with that
+ * value, 0 when no row has it (a row's abundance is never 0).  A value that is not canonical, or is >= 4^k, is simply not found. */
+int dskgpu_query_kmers(dskgpu_ctx* ctx, const void* d_kmers, uint64_t n, void* d_abundance);
+/* d_bytes: a read stream on the device (the input convention above; any alignment).  d_abundance: nbytes u32 on the device; out[p] =
+ * abundance of the canonical k-mer of the window ending at byte p when that window is valid and the k-mer is a solid row, else 0.
+ * Positions and validity are exactly those of dskgpu_k_enumerate. */
+int dskgpu_query_reads(dskgpu_ctx* ctx, const void* d_bytes, uint64_t nbytes, void* d_abundance);
 
 /* ---- the same call on N GPUs of one node, inside ONE process (what `dsk -nb-gpus N` runs): the reference's
  * single `execute()` (src/DSK.cpp:55-60) still leaves ONE storage with a flat list of solid partitions
