@@ -1,7 +1,8 @@
 // engine.h -- what the host translation units of libdskgpu share: the context (dskgpu_ctx) with its buffers and switches,
 // the error macros, and the functions one of them calls in the other.  dskgpu.hip runs the count path and the C-ABI;
 // rowsort.hip orders the solid rows (order_rows) and owns the row sort's state (dskgpu_ctx::rs); query.hip answers lookups in the
-// last result (dskgpu_query_*) and owns dskgpu_ctx::query.  Private to the library.
+// last result (dskgpu_query_*) and owns dskgpu_ctx::query; graph.hip answers the de Bruijn neighbourhood of k-mers from the same index
+// (dskgpu_graph_*).  Private to the library.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -134,11 +135,12 @@ struct RowSort {
 // Lookups in the last result (query.hip): one open-addressing hash table over the result rows, built on the first query after a count.
 // A slot is (fingerprint << 32 | row number), all ones = empty; cap is a power of two >= 2 * rows.  packed / inval: the 2-bit form of the
 // QUERIED stream (dskgpu_query_reads) -- buffers of the query's own, so that the context's reads and their kept encoding stay untouched.
+// deg: the 25 x u64 degree counters of dskgpu_graph_adjacency (graph.hip), which probes the same table.
 struct Query {
-    DevBuf table, packed, inval;
+    DevBuf table, packed, inval, deg;
     u64 cap = 0;
     bool valid = false;            // the table indexes the current result (dskgpu_ctx::drop_result clears it)
-    void release() { table.release(); packed.release(); inval.release(); cap = 0; valid = false; }
+    void release() { table.release(); packed.release(); inval.release(); deg.release(); cap = 0; valid = false; }
 };
 
 // state of a per-bank count in steps (banks_begin .. banks_finish below)
@@ -296,3 +298,11 @@ u32 part_sort_nparts(const SparseRows& rows);
 int launch_part_sort(dskgpu_ctx* ctx, const SparseRows& rows, RowsOut out, u32* out_ab, u32* d_part_off, u32* d_flag, u32* nparts_out);
 u32 rows_partitions(const dskgpu_ctx* ctx);
 void rows_partition_range(const dskgpu_ctx* ctx, u32 p, u64* b, u64* e);
+
+// query.hip (QTable: query.h)
+struct QTable;
+int ensure_index(dskgpu_ctx* ctx);                       // the index of the current result: there already, or enqueued now; no result: DSKGPU_E_STATE
+QTable query_table(const dskgpu_ctx* ctx);               // what a kernel takes to probe it
+int query_ensure(dskgpu_ctx* ctx, DevBuf& b, size_t bytes, const char* what);
+void query_begin(dskgpu_ctx* ctx);                       // stage marks of a call from "query start" on ...
+int query_finish(dskgpu_ctx* ctx);                       // ... and the wait for the stream that resolves them

@@ -88,7 +88,7 @@ EXPORTS = [
     "dskgpu_mg_send_capacity_words", "dskgpu_mg_count", "dskgpu_mg_sent_kmers", "dskgpu_mg_count_sized",
     "dskgpu_mg_slices_prepare", "dskgpu_mg_scatter_slice", "dskgpu_mg_slices_finish", "dskgpu_mg_count_sliced", "dskgpu_get_stats", "dskgpu_histogram",
     "dskgpu_set_row_order", "dskgpu_num_partitions", "dskgpu_partition_size", "dskgpu_partition_offsets", "dskgpu_partition_copy", "dskgpu_result_device",
-    "dskgpu_stage_times", "dskgpu_query_prepare", "dskgpu_query_kmers", "dskgpu_query_reads", "dskgpu_k_encode", "dskgpu_k_enumerate", "dskgpu_k_minimizers",
+    "dskgpu_stage_times", "dskgpu_query_prepare", "dskgpu_query_kmers", "dskgpu_query_reads", "dskgpu_graph_adjacency", "dskgpu_graph_neighbors", "dskgpu_k_encode", "dskgpu_k_enumerate", "dskgpu_k_minimizers",
     "dskgpu_group_create", "dskgpu_group_destroy", "dskgpu_group_last_error", "dskgpu_group_size", "dskgpu_group_ctx",
     "dskgpu_group_transport", "dskgpu_group_count", "dskgpu_group_exchanged_words", "dskgpu_group_sliced_steps", "dskgpu_group_histogram", "dskgpu_group_histogram2d",
     "dskgpu_group_get_stats", "dskgpu_group_num_partitions", "dskgpu_group_partition_size", "dskgpu_group_partition_copy",
@@ -169,6 +169,10 @@ def load_library():
     lib.dskgpu_query_kmers.restype = C.c_int
     lib.dskgpu_query_reads.argtypes = [vp, vp, u64, vp]
     lib.dskgpu_query_reads.restype = C.c_int
+    lib.dskgpu_graph_adjacency.argtypes = [vp, vp, C.POINTER(u64)]
+    lib.dskgpu_graph_adjacency.restype = C.c_int
+    lib.dskgpu_graph_neighbors.argtypes = [vp, vp, u64, vp]
+    lib.dskgpu_graph_neighbors.restype = C.c_int
     lib.dskgpu_k_encode.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_enumerate.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_minimizers.argtypes = [vp, vp, u64, vp, vp]
@@ -225,12 +229,13 @@ class KmerCounter:
     """One counting context on one GPU (not thread-safe; one per device)."""
 
     @classmethod
-    def _borrowed(cls, handle, kmer_size: int, histo_max: int, world_size: int) -> "KmerCounter":
+    def _borrowed(cls, handle, kmer_size: int, histo_max: int, world_size: int, device: int = 0) -> "KmerCounter":
         """A view of a ctx owned by somebody else (a KmerGroup rank): never destroyed from here."""
         self = cls.__new__(cls)
         self._lib = load_library()
         self._h = C.c_void_p(handle)
         self._owned = False
+        self.device = device
         self.kmer_size, self.histo_max, self.world_size = kmer_size, histo_max, world_size
         self.words = (kmer_size + 31) // 32
         return self
@@ -251,6 +256,7 @@ class KmerCounter:
                            minimizer_size, max_pass_mkeys, solidity_kind, solidity_custom, histo2d, mg_explicit, place, partition_order)
         self.kmer_size = kmer_size
         self.histo_max = histo_max
+        self.device = device
         self.words = (kmer_size + 31) // 32          # 64-bit words of a k-mer at the ABI (1..4)
         self.world_size = world_size
         h = C.c_void_p()
@@ -528,6 +534,40 @@ class KmerCounter:
         self.query_reads(stream.data_ptr(), stream.numel(), out.data_ptr())
         return out
 
+    # -- the rows' de Bruijn neighbours (include/dskgpu.h: dskgpu_graph_*)
+    def graph_adjacency(self, d_adj: int = 0) -> np.ndarray:
+        """d_adj: n_rows bytes on the device (result order) <- bit b: successor b of the row is a row, bit 4 + b: predecessor b is; 0 = only
+        the degree table.  -> uint64[5, 5], [i, o] = rows with i predecessors and o successors."""
+        deg = np.zeros((5, 5), dtype=np.uint64)
+        self._ck(self._lib.dskgpu_graph_adjacency(self._h, C.c_void_p(d_adj) if d_adj else None, deg.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return deg
+
+    def graph_adjacency_tensor(self):
+        """-> (uint8 CUDA tensor of n_rows adjacency bytes in result order, the degree table of graph_adjacency)."""
+        import torch
+        n = self.result_device()[2]
+        out = torch.zeros(n, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        torch.cuda.current_stream(out.device).synchronize()       # the context's stream is not torch's: the zero fill is done before the kernel writes
+        return out, self.graph_adjacency(out.data_ptr())
+
+    def graph_neighbors(self, d_kmers: int, n: int, d_adj: int) -> None:
+        """d_kmers: n values of `words` u64 each on the device (LSW first), canonical or not; d_adj: n bytes on the device <- their adjacency bytes."""
+        self._ck(self._lib.dskgpu_graph_neighbors(self._h, C.c_void_p(d_kmers), n, C.c_void_p(d_adj)))
+
+    def graph_neighbors_tensor(self, kmers):
+        """kmers: CUDA tensor of n x `words` 64-bit values (as query_kmers_tensor takes them).  -> uint8 tensor of n adjacency bytes."""
+        import torch
+        if not kmers.is_cuda or kmers.element_size() != 8:
+            raise ValueError("graph_neighbors_tensor: a CUDA tensor of 64-bit words is needed")
+        kmers = kmers.contiguous()
+        if kmers.numel() % self.words:
+            raise ValueError("graph_neighbors_tensor: %d words are not whole values of %d words" % (kmers.numel(), self.words))
+        n = kmers.numel() // self.words
+        out = torch.zeros(n, dtype=torch.uint8, device=kmers.device)
+        torch.cuda.current_stream(kmers.device).synchronize()
+        self.graph_neighbors(kmers.data_ptr(), n, out.data_ptr())
+        return out
+
     # -- kernel-level entry points (parity tests)
     def k_encode(self, d_bytes: int, nbytes: int, d_packed: int, d_invalid: int) -> None:
         self._ck(self._lib.dskgpu_k_encode(self._h, C.c_void_p(d_bytes), nbytes, C.c_void_p(d_packed), C.c_void_p(d_invalid)))
@@ -559,7 +599,7 @@ class KmerGroup:
         self.size = len(devices)
         self.kmer_size, self.histo_max = kmer_size, histo_max
         self.words = (kmer_size + 31) // 32
-        self._ranks = [KmerCounter._borrowed(self._lib.dskgpu_group_ctx(self._h, r), kmer_size, histo_max, self.size)
+        self._ranks = [KmerCounter._borrowed(self._lib.dskgpu_group_ctx(self._h, r), kmer_size, histo_max, self.size, devices[r])
                        for r in range(self.size)]
 
     def _ck(self, rc: int) -> None:

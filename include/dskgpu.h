@@ -321,6 +321,33 @@ int dskgpu_query_kmers(dskgpu_ctx* ctx, const void* d_kmers, uint64_t n, void* d
  * Positions and validity are exactly those of dskgpu_k_enumerate. */
 int dskgpu_query_reads(dskgpu_ctx* ctx, const void* d_bytes, uint64_t nbytes, void* d_abundance);
 
+/* ---- the rows' de Bruijn neighbours: DSK's output is the node set of a de Bruijn graph, and what gatb-core's consumers (the `Graph`
+ * built from the solid k-mers, Minia, BCALM, Bloocoo) ask every node first is which of its four successors and four predecessors are
+ * solid too -- branching nodes, tips, isolated nodes and unitig ends all follow from that one byte per node.
+ * For a k-mer value x < 4^k read as the string s[0..k-1] (A=0 C=1 T=2 G=3, first base most significant):
+ *   succ_b(x) = s[1..k-1].b = ((x << 2) | b) & (4^k - 1)        pred_b(x) = b.s[0..k-2] = (x >> 2) | (b << 2(k-1))
+ * adj(x) is one byte: bit b (b = 0..3) is set iff canonical(succ_b(x)) is a row of the current result, bit 4 + b iff canonical(pred_b(x))
+ * is one -- "row" exactly as dskgpu_query_kmers means it, for every k (1..128) and every result a context can hold (either row order,
+ * DSKGPU_F_NO_SORT, several passes, the per-bank modes, a rank's rows).  Nothing is special-cased: a self-loop (poly-A: succ_A(x) = x) sets
+ * its bit because x is a row; a palindrome (even k) has successor and predecessor bits that name the same canonical neighbour.  For a row,
+ * x is the row's (canonical) value; in- and out-degree in that orientation are the popcounts of the high and the low nibble.
+ * A rank's rows are the k-mers that rank owns and every k-mer has one owner, so the adjacency of a GROUP's rows is the bitwise OR over the
+ * ranks of dskgpu_graph_neighbors, asked with the same values on every rank's context (dskgpu_group_ctx(g, r)); there is no routed group
+ * call.
+ * Both calls probe the lookup index above (built on first use, dropped with the result; its limit of 2^32 - 2 rows and its
+ * DSKGPU_E_NOMEM hold here too), run on the context's stream, are synchronous on return and change nothing else in the context: the
+ * reads (a kept encoding included), the result, the stats and the sender state stay as they are.  Stage time: "graph" (and "query index"
+ * when the call built the index).
+ * Errors: no result DSKGPU_E_STATE; a null ctx DSKGPU_E_ARG; dskgpu_graph_neighbors with n == 0: DSKGPU_OK, nothing is done; a null
+ * d_kmers / d_adj with n > 0, or d_adj and degrees both null: DSKGPU_E_ARG.  A result with zero rows: dskgpu_graph_adjacency writes
+ * nothing to d_adj and zero-fills degrees; dskgpu_graph_neighbors answers 0 everywhere. */
+/* d_adj: n_rows bytes on the device (dskgpu_result_device's n_rows, result order), may be NULL;
+ * degrees: 25 uint64 on the HOST, degrees[i * 5 + o] = rows with i predecessors and o successors, may be NULL; not both NULL. */
+int dskgpu_graph_adjacency(dskgpu_ctx* ctx, void* d_adj, uint64_t* degrees);
+/* adj() of n caller-supplied values (layout of dskgpu_query_kmers: `words` u64 each, LSW first), canonical or not,
+ * whether or not the value itself is a row; a value >= 4^k answers 0.  d_adj: n bytes on the device. */
+int dskgpu_graph_neighbors(dskgpu_ctx* ctx, const void* d_kmers, uint64_t n, void* d_adj);
+
 /* ---- the same call on N GPUs of one node, inside ONE process (what `dsk -nb-gpus N` runs): the reference's
  * single `execute()` (src/DSK.cpp:55-60) still leaves ONE storage with a flat list of solid partitions
  * (utils/dsk2ascii.cpp:61,77).  A group owns one ctx per rank (world_size = n_ranks, rank r on devices[r], its own
