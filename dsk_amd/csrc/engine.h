@@ -2,7 +2,7 @@
 // the error macros, and the functions one of them calls in the other.  dskgpu.hip runs the count path and the C-ABI;
 // rowsort.hip orders the solid rows (order_rows) and owns the row sort's state (dskgpu_ctx::rs); query.hip answers lookups in the
 // last result (dskgpu_query_*) and owns dskgpu_ctx::query; graph.hip answers the de Bruijn neighbourhood of k-mers from the same index
-// (dskgpu_graph_*).  Private to the library.
+// (dskgpu_graph_*); unitigs.hip compacts the rows' graph into unitigs (dskgpu_unitigs*) and owns dskgpu_ctx::unitigs.  Private to the library.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -72,6 +72,7 @@ struct Tuning {
     bool l0_keys = false;                       // DSKGPU_L0_KEYS: level 0 as key arrays (k_level0) even where the record-based one applies (experiments, tests)
     u32 mp_pass_mkeys = 0;                      // DSKGPU_MP_PASS_MKEYS: keys (millions) per pass of an input that needs several passes (default 1000)
     u64 rs_slab_rows = 0;                       // DSKGPU_RS_SLAB_ROWS: rows per slab of the row sort for >= 2^32 rows (tests: forces that path, with small slabs, on a small input)
+    bool unitig_stages = false;                 // DSKGPU_UNITIG_STAGES: the build of the unitigs marks "unitig links" / "unitig ranking" / "unitig numbering" instead of "unitigs" (tools/bench_unitigs.py)
     void read() {
         auto on = [](const char* n) { return getenv(n) != nullptr; };
         auto num = [](const char* n, u64 dflt) { const char* e = getenv(n); return e ? (u64)atoll(e) : dflt; };
@@ -84,6 +85,7 @@ struct Tuning {
         max_ext = getenv("DSKGPU_MAX_EXT") ? atoll(getenv("DSKGPU_MAX_EXT")) : -1;
         no_sample = on("DSKGPU_NO_SAMPLE"); no_heavy = on("DSKGPU_NO_HEAVY"); verbose = on("DSKGPU_VERBOSE"); no_level0 = on("DSKGPU_NO_LEVEL0"); l0_passes = (u32)num("DSKGPU_L0_PASSES", 0); mp_pass_mkeys = (u32)num("DSKGPU_MP_PASS_MKEYS", 0); rs_max_rows = num("DSKGPU_RS_MAX_ROWS", 0); l0_keys = on("DSKGPU_L0_KEYS"); sk_generic = on("DSKGPU_SK_GENERIC"); ps_maxc = (u32)num("DSKGPU_PS_MAXC", 0);
         rs_slab_rows = num("DSKGPU_RS_SLAB_ROWS", 0);
+        unitig_stages = on("DSKGPU_UNITIG_STAGES");
         rs_block_rows = (u32)num("DSKGPU_RS_BLOCK_ROWS", 0); rs_bbits = (u32)num("DSKGPU_RS_BBITS", 0); rs_heavy = (u32)num("DSKGPU_RS_HEAVY", 0);
     }
 };
@@ -141,6 +143,15 @@ struct Query {
     u64 cap = 0;
     bool valid = false;            // the table indexes the current result (dskgpu_ctx::drop_result clears it)
     void release() { table.release(); packed.release(); inval.release(); deg.release(); cap = 0; valid = false; }
+};
+
+// The rows' de Bruijn graph compacted into unitigs (unitigs.hip), built on the first dskgpu_unitigs* call after a count: per row the unitig
+// number and (position << 1 | orientation), per unitig the stream offset (n_unitigs + 1 of them), the abundance sum and the kind.
+struct Unitigs {
+    DevBuf unitig, pos, offsets, ab_sum, kind;
+    dskgpu_unitig_stats stats{};
+    bool valid = false;            // they compact the current result (dskgpu_ctx::drop_result clears it)
+    void release() { for (DevBuf* b : {&unitig, &pos, &offsets, &ab_sum, &kind}) b->release(); stats = dskgpu_unitig_stats{}; valid = false; }
 };
 
 // state of a per-bank count in steps (banks_begin .. banks_finish below)
@@ -237,9 +248,10 @@ struct dskgpu_ctx {
     dskgpu_stats stats{};
     std::vector<u64> hist;
     Query query;
-    // a count starts, or its result is not to be read: the index of the old rows goes with them, and so does its memory -- up to 32 bytes
-    // per row that the count about to run may need (a no-op for a context that was never queried)
-    void drop_result() { have_result = false; query.release(); }
+    Unitigs unitigs;
+    // a count starts, or its result is not to be read: the index of the old rows and their unitigs go with them, and so does their memory
+    // -- up to 32 + 8 bytes per row that the count about to run may need (a no-op for a context that was never queried)
+    void drop_result() { have_result = false; query.release(); unitigs.release(); }
 
     // timing
     std::vector<Stage> marks;

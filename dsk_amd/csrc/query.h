@@ -61,12 +61,15 @@ __global__ __launch_bounds__(256) void k_query_build(RowsIn rows, u64 n, u64* __
     }
 }
 
-// out[j] = abundance of c[j] for the keys whose bit is set in `pend`, 0 for the others and for keys that are no row
-template <int W, int N>
+#define Q_NO_ROW 0xFFFFFFFFu               // q_lookup<W, N, true>: the key is no row
+
+// out[j] = abundance of c[j] for the keys whose bit is set in `pend`, 0 for the others and for keys that are no row.  ROW: the row
+// NUMBER instead (unitigs.h), Q_NO_ROW for the others and for keys that are no row; the abundance column is not read then.
+template <int W, int N, bool ROW = false>
 __device__ __forceinline__ void q_lookup(const QTable& T, const KN<W> (&c)[N], u32 pend, u32 (&out)[N]) {
     u64 h[N];
 #pragma unroll
-    for (int j = 0; j < N; ++j) { h[j] = q_hash<W>(c[j]); out[j] = 0u; }
+    for (int j = 0; j < N; ++j) { h[j] = q_hash<W>(c[j]); out[j] = ROW ? Q_NO_ROW : 0u; }
     for (u64 d = 0; pend; ++d) {
         u64 v[N];
 #pragma unroll
@@ -84,7 +87,7 @@ __device__ __forceinline__ void q_lookup(const QTable& T, const KN<W> (&c)[N], u
             if ((cand >> j) & 1u) {
 #pragma unroll
                 for (int x = 0; x < W; ++x) rk[j].w[x] = T.rows.w[x][r];
-                ra[j] = T.ab[r];
+                if constexpr (ROW) ra[j] = r; else ra[j] = T.ab[r];
             } else {
 #pragma unroll
                 for (int x = 0; x < W; ++x) rk[j].w[x] = 0ull;

@@ -59,6 +59,18 @@ class _Stats(C.Structure):
     ]
 
 
+class _UnitigStats(C.Structure):
+    _fields_ = [
+        ("n_unitigs", C.c_uint64),
+        ("n_cycles", C.c_uint64),
+        ("n_single", C.c_uint64),
+        ("max_nodes", C.c_uint64),
+        ("stream_bytes", C.c_uint64),
+        ("n_rounds", C.c_uint64),
+        ("reserved", C.c_uint64 * 2),
+    ]
+
+
 MG_BUCKETS = 4096      # DSKGPU_MG_BUCKETS
 MG_SPLIT = 255         # DSKGPU_MG_SPLIT
 
@@ -88,7 +100,8 @@ EXPORTS = [
     "dskgpu_mg_send_capacity_words", "dskgpu_mg_count", "dskgpu_mg_sent_kmers", "dskgpu_mg_count_sized",
     "dskgpu_mg_slices_prepare", "dskgpu_mg_scatter_slice", "dskgpu_mg_slices_finish", "dskgpu_mg_count_sliced", "dskgpu_get_stats", "dskgpu_histogram",
     "dskgpu_set_row_order", "dskgpu_num_partitions", "dskgpu_partition_size", "dskgpu_partition_offsets", "dskgpu_partition_copy", "dskgpu_result_device",
-    "dskgpu_stage_times", "dskgpu_query_prepare", "dskgpu_query_kmers", "dskgpu_query_reads", "dskgpu_graph_adjacency", "dskgpu_graph_neighbors", "dskgpu_k_encode", "dskgpu_k_enumerate", "dskgpu_k_minimizers",
+    "dskgpu_stage_times", "dskgpu_query_prepare", "dskgpu_query_kmers", "dskgpu_query_reads", "dskgpu_graph_adjacency", "dskgpu_graph_neighbors",
+    "dskgpu_unitigs", "dskgpu_unitigs_rows", "dskgpu_unitigs_table", "dskgpu_unitigs_stream", "dskgpu_k_encode", "dskgpu_k_enumerate", "dskgpu_k_minimizers",
     "dskgpu_group_create", "dskgpu_group_destroy", "dskgpu_group_last_error", "dskgpu_group_size", "dskgpu_group_ctx",
     "dskgpu_group_transport", "dskgpu_group_count", "dskgpu_group_exchanged_words", "dskgpu_group_sliced_steps", "dskgpu_group_histogram", "dskgpu_group_histogram2d",
     "dskgpu_group_get_stats", "dskgpu_group_num_partitions", "dskgpu_group_partition_size", "dskgpu_group_partition_copy",
@@ -173,6 +186,14 @@ def load_library():
     lib.dskgpu_graph_adjacency.restype = C.c_int
     lib.dskgpu_graph_neighbors.argtypes = [vp, vp, u64, vp]
     lib.dskgpu_graph_neighbors.restype = C.c_int
+    lib.dskgpu_unitigs.argtypes = [vp, C.POINTER(_UnitigStats)]
+    lib.dskgpu_unitigs.restype = C.c_int
+    lib.dskgpu_unitigs_rows.argtypes = [vp, vp, vp]
+    lib.dskgpu_unitigs_rows.restype = C.c_int
+    lib.dskgpu_unitigs_table.argtypes = [vp, vp, vp, vp]
+    lib.dskgpu_unitigs_table.restype = C.c_int
+    lib.dskgpu_unitigs_stream.argtypes = [vp, vp, u64]
+    lib.dskgpu_unitigs_stream.restype = C.c_int
     lib.dskgpu_k_encode.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_enumerate.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_minimizers.argtypes = [vp, vp, u64, vp, vp]
@@ -566,6 +587,59 @@ class KmerCounter:
         out = torch.zeros(n, dtype=torch.uint8, device=kmers.device)
         torch.cuda.current_stream(kmers.device).synchronize()
         self.graph_neighbors(kmers.data_ptr(), n, out.data_ptr())
+        return out
+
+    # -- the rows' de Bruijn graph compacted into unitigs (include/dskgpu.h: dskgpu_unitigs*)
+    def unitigs(self) -> dict:
+        """Build the compaction of the last result (the first of these calls after a count does) -> its stats: n_unitigs, n_cycles, n_single,
+        max_nodes, stream_bytes, n_rounds."""
+        st = _UnitigStats()
+        self._ck(self._lib.dskgpu_unitigs(self._h, C.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in _UnitigStats._fields_ if name != "reserved"}
+
+    def unitigs_rows(self, d_unitig: int, d_pos: int) -> None:
+        """d_unitig / d_pos: n_rows u32 each on the device (result order) <- the row's unitig / (position << 1) | orientation; either may be 0."""
+        self._ck(self._lib.dskgpu_unitigs_rows(self._h, C.c_void_p(d_unitig) if d_unitig else None, C.c_void_p(d_pos) if d_pos else None))
+
+    def unitigs_table(self, d_offsets: int, d_ab_sum: int, d_kind: int) -> None:
+        """d_offsets: n_unitigs + 1 u64, d_ab_sum: n_unitigs u64, d_kind: n_unitigs bytes, all on the device; any may be 0."""
+        self._ck(self._lib.dskgpu_unitigs_table(self._h, *(C.c_void_p(p) if p else None for p in (d_offsets, d_ab_sum, d_kind))))
+
+    def unitigs_stream(self, d_bytes: int, capacity: int) -> None:
+        """d_bytes: `capacity` >= stream_bytes bytes on the device <- the unitig sequences, each followed by a newline."""
+        self._ck(self._lib.dskgpu_unitigs_stream(self._h, C.c_void_p(d_bytes) if d_bytes else None, capacity))
+
+    def unitigs_rows_tensor(self):
+        """-> (int32[n_rows] unitig of every row, int32[n_rows] (position << 1) | orientation), CUDA tensors in result order."""
+        import torch
+        self.unitigs()
+        n = self.result_device()[2]
+        dev = torch.device("cuda", self.device)
+        unitig, pos = torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()              # the context's stream is not torch's: the zero fill is done before the copies write
+        if n:
+            self.unitigs_rows(unitig.data_ptr(), pos.data_ptr())
+        return unitig, pos
+
+    def unitigs_table_tensor(self):
+        """-> (int64[n_unitigs + 1] stream offsets, int64[n_unitigs] abundance sums, uint8[n_unitigs] kind: 1 = cycle), CUDA tensors."""
+        import torch
+        nu = self.unitigs()["n_unitigs"]
+        dev = torch.device("cuda", self.device)
+        off, ab = torch.zeros(nu + 1, dtype=torch.int64, device=dev), torch.zeros(nu, dtype=torch.int64, device=dev)
+        kind = torch.zeros(nu, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        self.unitigs_table(off.data_ptr(), ab.data_ptr() if nu else 0, kind.data_ptr() if nu else 0)
+        return off, ab, kind
+
+    def unitigs_stream_tensor(self):
+        """-> uint8[stream_bytes] CUDA tensor: the unitig stream, a read stream that set_reads_device takes."""
+        import torch
+        nb = self.unitigs()["stream_bytes"]
+        out = torch.zeros(nb, dtype=torch.uint8, device=torch.device("cuda", self.device))
+        torch.cuda.current_stream(out.device).synchronize()
+        if nb:
+            self.unitigs_stream(out.data_ptr(), nb)
         return out
 
     # -- kernel-level entry points (parity tests)

@@ -348,6 +348,50 @@ int dskgpu_graph_adjacency(dskgpu_ctx* ctx, void* d_adj, uint64_t* degrees);
  * whether or not the value itself is a row; a value >= 4^k answers 0.  d_adj: n bytes on the device. */
 int dskgpu_graph_neighbors(dskgpu_ctx* ctx, const void* d_kmers, uint64_t n, void* d_adj);
 
+/* ---- the rows' de Bruijn graph compacted into unitigs: what Minia, BCALM and gatb-core's `Graph` do with the node set next -- every
+ * maximal non-branching path of solid k-mers becomes one sequence.  On the device, for every k (1..128) and every result a context of
+ * world_size 1 can hold (either row order, DSKGPU_F_NO_SORT, several passes, the per-bank modes).
+ * Row r (a row number of dskgpu_result_device) with the canonical string S(r) gives two ORIENTED nodes o = 2 r + s: str(o) = S(r) for
+ * s = 0, its reverse complement for s = 1; flip(o) = o ^ 1.  succ(o) = the oriented nodes p with str(p) = str(o)[1..] . b for a base b
+ * and row(p) a row; outdeg(o) = the popcount of the low (s = 0) or high (s = 1) nibble of the row's adjacency byte above;
+ * indeg(p) = outdeg(flip(p)).  LINK: next(o) = p when outdeg(o) = 1 and p is that successor, indeg(p) = 1, row(p) != row(o) (no
+ * self-loop such as poly-A, no hairpin such as the AT repeat at odd k) and neither row is its own reverse complement (a palindrome, even k
+ * only, is a unitig by itself).  Links are symmetric: next(o) = p <=> next(flip(p)) = flip(o).
+ * A UNITIG is a maximal path o_0 -> .. -> o_{L-1} of links; every row lies in exactly one, at one position, in one orientation:
+ *   chain        no link into o_0, none out of o_{L-1}, L >= 2: of its two readings the one with row(o_0) < row(o_{L-1});
+ *   single node  L = 1, reported forward (s = 0);
+ *   cycle        every node has a link into it: starts at the smallest row number on it, forward (o_0 = 2 r_min).
+ * Unitigs are numbered 0 .. n_unitigs - 1 by ascending row(o_0).  The sequence of a unitig is str(o_0) followed by the last base of
+ * every further str(o_i): k + L - 1 letters of "ACTG".  The unitig STREAM is these sequences, each followed by '\n' -- a read stream by
+ * the input convention above: offsets[u] = (rows in unitigs before u) + u * k, stream_bytes = n_rows + n_unitigs * k, and counting
+ * the stream with abundance_min = 1 gives back exactly the rows, each once.  The row order changes the numbering, the orientation
+ * and where a cycle is cut, never the set of unitigs.
+ * The compaction is kept in the context like the lookup index (8 bytes per row + 17 per unitig; about 45 bytes per row more while it
+ * is built): built on first use by any of the four calls, dropped when the next count starts and by dskgpu_destroy.  All four probe
+ * the lookup index (its DSKGPU_E_NOMEM holds here too, and the context and its result stay usable), run on the context's stream, are
+ * synchronous on return and change nothing else in the context: the reads (a kept encoding included), the result, the stats and the sender
+ * state stay as they are.  The build ranks the nodes of every path by pointer jumping: at most 33 rounds per phase by construction
+ * (2^33 > 2 * rows); a phase that has not finished by then is DSKGPU_E_DEVICE.  Stage times: "unitigs" (the build), "unitig stream", and
+ * "graph" / "query index" when the call computed the adjacency / built the index.
+ * Errors: a null ctx DSKGPU_E_ARG; no result DSKGPU_E_STATE; more than 2^31 - 1 rows DSKGPU_E_STATE (oriented node numbers are 32 bits;
+ * the text says so); a context with world_size > 1 DSKGPU_E_STATE: a rank holds only the k-mers it owns, and the unitigs of a rank's rows
+ * do NOT combine into the group's unitigs the way the adjacency bytes OR -- a path ends wherever its next k-mer has another owner.  A
+ * result with zero rows: all-zero stats, offsets[0] = 0, nothing else is written. */
+typedef struct dskgpu_unitig_stats {
+    uint64_t n_unitigs, n_cycles, n_single, max_nodes, stream_bytes, n_rounds, reserved[2];
+} dskgpu_unitig_stats;                                   /* 64 bytes */
+/* Build the compaction now (optional) and fill `stats` (may be NULL): unitigs, those that are cycles, those of one node, rows of the
+ * longest, bytes of the stream, pointer-jumping launches of the build (all phases together). */
+int dskgpu_unitigs(dskgpu_ctx* ctx, dskgpu_unitig_stats* stats);
+/* Per row, on the device, result order: d_unitig u32[n_rows] = the row's unitig, d_pos u32[n_rows] = (position in it << 1) | s.
+ * Either may be NULL; both NULL: DSKGPU_E_ARG. */
+int dskgpu_unitigs_rows(dskgpu_ctx* ctx, void* d_unitig, void* d_pos);
+/* Per unitig, on the device: d_offsets u64[n_unitigs + 1] byte offsets into the stream, d_ab_sum u64[n_unitigs] sum of the member rows'
+ * abundances (BCALM's km, kept exact), d_kind u8[n_unitigs] 0 = chain or single node, 1 = cycle.  Any may be NULL; all NULL: DSKGPU_E_ARG. */
+int dskgpu_unitigs_table(dskgpu_ctx* ctx, void* d_offsets, void* d_ab_sum, void* d_kind);
+/* The unitig stream into d_bytes (device, any alignment).  capacity < stream_bytes, or a null d_bytes: DSKGPU_E_ARG, nothing is written. */
+int dskgpu_unitigs_stream(dskgpu_ctx* ctx, void* d_bytes, uint64_t capacity);
+
 /* ---- the same call on N GPUs of one node, inside ONE process (what `dsk -nb-gpus N` runs): the reference's
  * single `execute()` (src/DSK.cpp:55-60) still leaves ONE storage with a flat list of solid partitions
  * (utils/dsk2ascii.cpp:61,77).  A group owns one ctx per rank (world_size = n_ranks, rank r on devices[r], its own
