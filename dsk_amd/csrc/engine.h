@@ -2,7 +2,7 @@
 // the error macros, and the functions one of them calls in the other.  dskgpu.hip runs the count path and the C-ABI;
 // rowsort.hip orders the solid rows (order_rows) and owns the row sort's state (dskgpu_ctx::rs); query.hip answers lookups in the
 // last result (dskgpu_query_*) and owns dskgpu_ctx::query; graph.hip answers the de Bruijn neighbourhood of k-mers from the same index
-// (dskgpu_graph_*); unitigs.hip compacts the rows' graph into unitigs (dskgpu_unitigs*) and owns dskgpu_ctx::unitigs.  Private to the library.
+// (dskgpu_graph_*); unitigs.hip compacts the rows' graph into unitigs and links them (dskgpu_unitigs*, dskgpu_unitig_edges*) and owns dskgpu_ctx::unitigs.  Private to the library.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -147,11 +147,17 @@ struct Query {
 
 // The rows' de Bruijn graph compacted into unitigs (unitigs.hip), built on the first dskgpu_unitigs* call after a count: per row the unitig
 // number and (position << 1 | orientation), per unitig the stream offset (n_unitigs + 1 of them), the abundance sum and the kind.
+// The edges between the unitigs, built on the first dskgpu_unitig_edges* call on top of the compaction: per oriented unitig U = 2 u + t its
+// last node (ends) and the CSR offset of its targets (e_offsets, 2 n_unitigs + 1 of them), per edge the oriented unitig it leads to.
 struct Unitigs {
     DevBuf unitig, pos, offsets, ab_sum, kind;
+    DevBuf ends, e_offsets, e_targets;
     dskgpu_unitig_stats stats{};
+    dskgpu_unitig_edge_stats e_stats{};
     bool valid = false;            // they compact the current result (dskgpu_ctx::drop_result clears it)
-    void release() { for (DevBuf* b : {&unitig, &pos, &offsets, &ab_sum, &kind}) b->release(); stats = dskgpu_unitig_stats{}; valid = false; }
+    bool e_valid = false;          // ... and the edges are those of that compaction
+    void release_edges() { for (DevBuf* b : {&ends, &e_offsets, &e_targets}) b->release(); e_stats = dskgpu_unitig_edge_stats{}; e_valid = false; }
+    void release() { for (DevBuf* b : {&unitig, &pos, &offsets, &ab_sum, &kind}) b->release(); stats = dskgpu_unitig_stats{}; valid = false; release_edges(); }
 };
 
 // state of a per-bank count in steps (banks_begin .. banks_finish below)

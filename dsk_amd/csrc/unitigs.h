@@ -23,7 +23,19 @@
 //   k_unitig_number     per row: unitig number and (position << 1 | s); the first node writes offsets[] and kind[]; abundance sums
 //   k_unitig_stream<W>  the letters: every node its last one, the first node its k - 1 leading ones, the last node the '\n'
 //
-// Every kernel is one pass over its nodes or rows: no loop on the device depends on the data but q_lookup's probe run.
+// The EDGES between the unitigs (dskgpu_unitig_edges*): an oriented unitig is U = 2 u + t, t = 1 reads unitig u backwards;
+// first(2u) = o_0, last(2u) = o_{L-1}, first(2u + 1) = flip(o_{L-1}), last(2u + 1) = flip(o_0); U -> V <=> first(V) is in succ(last(U)).
+//
+//   k_unitig_ends       per row: the row at position 0 writes ends[2u + 1] = flip(its node), the one at position nodes - 1 ends[2u] = its
+//                       node -- ends[U] = last(U), and first(V) = flip(ends[flip(V)])
+//   k_unitig_edges<W>   per oriented unitig: the row of last(U), oriented; its four successors (g_* helpers) probed as one batch for their ROW
+//                       NUMBERS; a hit (p, sp) is first(V) of exactly one V of unitig[p]: the one with ends[V ^ 1] = flip(2 p + sp).  Neither
+//                       of the two: the edge would land inside a unitig, which the links exclude -- counted, the host turns it into an error.
+//                       Writes four target slots (base order A, C, T, G; U_NONE = no edge) and the degree; counts edges, self edges, dead ends,
+//                       the largest degree per block in LDS
+//   k_unitig_edge_fill  per oriented unitig: its slots that hold a target, in order, to targets[] from offsets[U] (the scan of the degrees) on
+//
+// Every kernel is one pass over its nodes, rows or unitigs: no loop on the device depends on the data but q_lookup's probe run.
 #pragma once
 #include "graph.h"
 
@@ -38,6 +50,12 @@
 template <int W> struct UBatch { static constexpr int R = W == 1 ? 4 : W == 2 ? 2 : 1; };
 
 enum UStat { US_CYCLES = 0, US_SINGLE, US_MAX, US_COUNT };
+
+// oriented unitigs per thread of k_unitig_edges: four keys each, 16 / 8 / 4 keys in flight (QBatch's budget: the probe is followed by two
+// dependent levels of one word each, unitig[] and the ends, not by a neighbour's byte per key as in k_unitig_links)
+template <int W> struct UEBatch { static constexpr int R = W == 1 ? 4 : W == 2 ? 2 : 1; };
+
+enum UEStat { UE_EDGES = 0, UE_SELF, UE_DEAD, UE_BROKEN, UE_MAXDEG, UE_COUNT };
 
 template <int W> __device__ __forceinline__ bool u_less(const KN<W>& a, const KN<W>& b) {
     bool lt = false, decided = false;
@@ -267,4 +285,112 @@ __global__ __launch_bounds__(256) void k_unitig_stream(RowsIn rows, u64 n, int k
     if (pos == 0u)
         for (int i = 0; i < k - 1; ++i) out[off + (u64)i] = u_letter(s ? u_base<W>(x, i) ^ 2u : u_base<W>(x, k - 1 - i));
     if ((u64)pos + 1ull == nodes) out[off + (u64)k + pos] = '\n';
+}
+
+// ends[] arrives filled with U_NONE: an end that no row writes (it cannot be) stays a value that is no node and fails every guard after it
+__global__ __launch_bounds__(256) void k_unitig_ends(const u32* __restrict__ unitig, const u32* __restrict__ pos_s, const u64* __restrict__ offsets, u64 n, int k,
+                                                     u64 n_unitigs, u32* __restrict__ ends) {
+    const u64 r = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (r >= n) return;
+    const u32 u = unitig[r], ps = pos_s[r];
+    if (u >= n_unitigs) return;                                               // (cannot be: k_unitig_number numbered every row; no index leaves an array)
+    const u64 nodes = offsets[u + 1] - offsets[u] - (u64)k;
+    const u32 o = 2u * (u32)r + (ps & 1u);
+    if ((ps >> 1) == 0u) ends[2u * u + 1u] = o ^ 1u;
+    if ((u64)(ps >> 1) + 1ull == nodes) ends[2u * u] = o;
+}
+
+template <int W>
+__global__ __launch_bounds__(256) void k_unitig_edges(RowsIn rows, u64 n, int k, QTable T, const u32* __restrict__ unitig, const u32* __restrict__ ends,
+                                                      u64 n_unitigs, u32* __restrict__ slots, u64* __restrict__ deg, u64* __restrict__ stat) {
+    constexpr int R = UEBatch<W>::R, N = 4 * R;
+    __shared__ u32 s_stat[UE_COUNT];
+    if (threadIdx.x < UE_COUNT) s_stat[threadIdx.x] = 0u;
+    __syncthreads();
+    const u64 n_or = 2 * n_unitigs;
+    const u64 base = (u64)blockIdx.x * (256u * R) + threadIdx.x;
+    u64 msk[W];
+    g_masks<W>(k, msk);
+    const int top = 2 * k - 2, tw = top >> 6, tb = top & 63;
+    u32 e[R];
+#pragma unroll
+    for (int i = 0; i < R; ++i) { const u64 U = base + (u64)i * 256u; e[i] = U < n_or ? ends[U] : U_NONE; }
+    KN<W> c[N];
+    u32 pend = 0, flipped = 0, broken = 0;
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        const u64 U = base + (u64)i * 256u;
+        const u64 r = e[i] >> 1;
+        const bool in = U < n_or && r < n;                                    // (an end that is no node: nothing is probed, the unitig is counted as broken)
+        if (U < n_or && !in) ++broken;
+        KN<W> x;
+#pragma unroll
+        for (int q = 0; q < W; ++q) x.w[q] = in ? rows.w[q][r] : 0ull;
+        const KN<W> rc = g_revcomp<W>(x, k, msk);
+        const bool odd = e[i] & 1u;
+        KN<W> fw, bw;                                                         // str(last(U)) and its reverse complement
+#pragma unroll
+        for (int q = 0; q < W; ++q) { fw.w[q] = odd ? rc.w[q] : x.w[q]; bw.w[q] = odd ? x.w[q] : rc.w[q]; }
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const KN<W> f = g_push_low<W>(fw, (u64)b, msk);                   // the successor as last(U) reads it
+            const KN<W> v = g_push_top<W>(bw, (u64)(b ^ 2), tw, tb);          // its reverse complement
+            const bool sp = u_less<W>(v, f);                                  // (a palindrome: equal, forward)
+#pragma unroll
+            for (int q = 0; q < W; ++q) c[4 * i + b].w[q] = sp ? v.w[q] : f.w[q];
+            if (in) pend |= 1u << (4 * i + b);
+            if (sp) flipped |= 1u << (4 * i + b);
+        }
+    }
+    u32 prow[N];
+    q_lookup<W, N, true>(T, c, pend, prow);
+    u32 pu[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) pu[j] = prow[j] < n ? unitig[prow[j]] : U_NONE;
+    uint2 pe[N];                                                              // (ends[2v], ends[2v + 1]) of the hit's unitig v
+#pragma unroll
+    for (int j = 0; j < N; ++j) pe[j] = pu[j] < n_unitigs ? reinterpret_cast<const uint2*>(ends)[pu[j]] : make_uint2(U_NONE, U_NONE);
+    u32 edges = 0, self = 0, dead = 0, maxdeg = 0;
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        const u64 U = base + (u64)i * 256u;
+        u32 tg[4], d = 0;
+#pragma unroll
+        for (int b = 0; b < 4; ++b) {
+            const int j = 4 * i + b;
+            tg[b] = U_NONE;
+            if (prow[j] == Q_NO_ROW) continue;
+            const u32 back = (2u * prow[j] + ((flipped >> j) & 1u)) ^ 1u;      // flip(first(V)) = ends[flip(V)]
+            if (pu[j] < n_unitigs && pe[j].y == back) tg[b] = 2u * pu[j];
+            else if (pu[j] < n_unitigs && pe[j].x == back) tg[b] = 2u * pu[j] + 1u;
+            else { ++broken; continue; }
+            ++d;
+            self += (u64)(tg[b] >> 1) == (U >> 1) ? 1u : 0u;
+        }
+        if (U < n_or) {
+            reinterpret_cast<uint4*>(slots)[U] = make_uint4(tg[0], tg[1], tg[2], tg[3]);
+            deg[U] = (u64)d;
+            edges += d; dead += d == 0u ? 1u : 0u; maxdeg = max(maxdeg, d);
+        }
+    }
+    if (edges) atomicAdd(&s_stat[UE_EDGES], edges);
+    if (self) atomicAdd(&s_stat[UE_SELF], self);
+    if (dead) atomicAdd(&s_stat[UE_DEAD], dead);
+    if (broken) atomicAdd(&s_stat[UE_BROKEN], broken);
+    if (maxdeg) atomicMax(&s_stat[UE_MAXDEG], maxdeg);
+    __syncthreads();
+    if (threadIdx.x < UE_MAXDEG && s_stat[threadIdx.x]) atomicAdd(reinterpret_cast<unsigned long long*>(&stat[threadIdx.x]), (unsigned long long)s_stat[threadIdx.x]);
+    if (threadIdx.x == UE_MAXDEG && s_stat[UE_MAXDEG]) atomicMax(reinterpret_cast<unsigned long long*>(&stat[UE_MAXDEG]), (unsigned long long)s_stat[UE_MAXDEG]);
+}
+
+// offsets[U] .. offsets[U + 1]: where the targets of U go (n_or + 1 offsets, the last one = n_edges)
+__global__ __launch_bounds__(256) void k_unitig_edge_fill(const u32* __restrict__ slots, const u64* __restrict__ offsets, u64 n_or, u64 n_edges, u32* __restrict__ targets) {
+    const u64 U = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (U >= n_or) return;
+    const uint4 s = reinterpret_cast<const uint4*>(slots)[U];
+    const u32 tg[4] = {s.x, s.y, s.z, s.w};
+    u64 at = offsets[U];
+#pragma unroll
+    for (int b = 0; b < 4; ++b)
+        if (tg[b] != U_NONE && at < n_edges) targets[at++] = tg[b];           // (at < n_edges: the host checked that the degrees add up; the same guard)
 }

@@ -1,7 +1,9 @@
-// unitigs.hip -- the rows' de Bruijn graph compacted into unitigs: dskgpu_unitigs / _rows / _table / _stream (include/dskgpu.h).  Host side
+// unitigs.hip -- the rows' de Bruijn graph compacted into unitigs: dskgpu_unitigs / _rows / _table / _stream, and the edges between the
+// unitigs: dskgpu_unitig_edges / _edges_table (include/dskgpu.h).  Host side
 // of unitigs.h; owns dskgpu_ctx::unitigs.  Probes the lookup index of query.hip (ensure_index builds it on first use) and reads the result
 // (res_w / res_ab / n_rows); nothing else of the context.  What is kept after the build is 8 bytes per row and 17 per unitig; the
-// links, the ranking words and the scan live only while build() runs.
+// links, the ranking words and the scan live only while build() runs.  The edges add 12 bytes per oriented unitig and 4 per edge; their
+// target slots and degrees live only while build_edges() runs.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
 
@@ -173,6 +175,78 @@ int finish(dskgpu_ctx* ctx) {
     return rc;
 }
 
+template <int W>
+void launch_edges(dskgpu_ctx* ctx, u32* slots, u64* deg, u64* stat) {
+    const Unitigs& U = ctx->unitigs;
+    hipLaunchKernelGGL(k_unitig_edges<W>, dim3(blocks(2 * U.stats.n_unitigs, 256ull * UEBatch<W>::R)), dim3(256), 0, ctx->stream, result_rows(ctx), ctx->n_rows,
+                       (int)ctx->cfg.kmer_size, query_table(ctx), U.unitig.as<u32>(), U.ends.as<u32>(), U.stats.n_unitigs, slots, deg, stat);
+}
+
+// the scratch of the edges: freed when build_edges() returns, whatever way
+struct EdgeScratch {
+    DevBuf slots, deg, tmp, stat;
+    ~EdgeScratch() { for (DevBuf* b : {&slots, &deg, &tmp, &stat}) b->release(); }
+};
+
+int build_edges(dskgpu_ctx* ctx) {
+    Unitigs& U = ctx->unitigs;
+    const u64 n = ctx->n_rows, nu = U.stats.n_unitigs, n_or = 2 * nu;
+    U.e_stats = dskgpu_unitig_edge_stats{};
+    if (const int rc = query_ensure(ctx, U.e_offsets, (n_or + 1) * 8, "unitig edge offsets")) return rc;
+    if (n == 0) {
+        CK(hipMemsetAsync(U.e_offsets.p, 0, 8, ctx->stream));
+        ctx->mark("unitig edges");
+        return DSKGPU_OK;
+    }
+    EdgeScratch S;
+    if (const int rc = query_ensure(ctx, U.ends, n_or * 4, "unitig ends")) return rc;
+    if (const int rc = query_ensure(ctx, S.slots, n_or * 16, "unitig edge slots")) return rc;
+    if (const int rc = query_ensure(ctx, S.deg, (n_or + 1) * 8, "unitig degrees")) return rc;
+    if (const int rc = query_ensure(ctx, S.stat, UE_COUNT * 8, "unitig edge counters")) return rc;
+    CK(hipMemsetAsync(U.ends.p, 0xFF, n_or * 4, ctx->stream));
+    CK(hipMemsetAsync(S.deg.as<u64>() + n_or, 0, 8, ctx->stream));                   // the scan's last input: offsets[n_or] = n_edges
+    CK(hipMemsetAsync(S.stat.p, 0, UE_COUNT * 8, ctx->stream));
+    hipLaunchKernelGGL(k_unitig_ends, dim3(blocks(n, 256)), dim3(256), 0, ctx->stream, U.unitig.as<u32>(), U.pos.as<u32>(), U.offsets.as<u64>(), n,
+                       (int)ctx->cfg.kmer_size, nu, U.ends.as<u32>());
+    CKL("k_unitig_ends");
+    u64* deg = S.deg.as<u64>(); u64* stat = S.stat.as<u64>();
+    if (ctx->W == 1) launch_edges<1>(ctx, S.slots.as<u32>(), deg, stat);
+    else if (ctx->W == 2) launch_edges<2>(ctx, S.slots.as<u32>(), deg, stat);
+    else launch_edges<4>(ctx, S.slots.as<u32>(), deg, stat);
+    CKL("k_unitig_edges");
+    u64* off = U.e_offsets.as<u64>();
+    size_t tmp_bytes = 0;
+    CK(rocprim::exclusive_scan(nullptr, tmp_bytes, deg, off, 0ull, (size_t)(n_or + 1), rocprim::plus<u64>(), ctx->stream));      // LIBRARY SCAN (rocprim): plumbing, 8 bytes per oriented unitig
+    if (const int rc = query_ensure(ctx, S.tmp, tmp_bytes ? tmp_bytes : 8, "unitig edge scan")) return rc;
+    CK(rocprim::exclusive_scan(S.tmp.p, tmp_bytes, deg, off, 0ull, (size_t)(n_or + 1), rocprim::plus<u64>(), ctx->stream));
+    u64 total = 0, h_stat[UE_COUNT] = {0};
+    CK(hipMemcpyAsync(&total, off + n_or, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (const int rc = read_back(ctx, h_stat, stat, sizeof(h_stat))) return rc;
+    if (h_stat[UE_BROKEN] || total != h_stat[UE_EDGES] || total > 4 * n_or || h_stat[UE_MAXDEG] > 4)
+        return fail(ctx, DSKGPU_E_DEVICE, "dskgpu_unitig_edges: an edge does not lead to the end of a unitig, or the degrees do not add up (internal error)");
+    if (const int rc = query_ensure(ctx, U.e_targets, total ? total * 4 : 4, "unitig edge targets")) return rc;
+    hipLaunchKernelGGL(k_unitig_edge_fill, dim3(blocks(n_or, 256)), dim3(256), 0, ctx->stream, S.slots.as<u32>(), off, n_or, total, U.e_targets.as<u32>());
+    CKL("k_unitig_edge_fill");
+    ctx->mark("unitig edges");
+    CK(hipStreamSynchronize(ctx->stream));                                          // the scratch goes when this returns
+    U.e_stats.n_edges = total; U.e_stats.n_self = h_stat[UE_SELF]; U.e_stats.n_dead_ends = h_stat[UE_DEAD]; U.e_stats.max_degree = h_stat[UE_MAXDEG];
+    return DSKGPU_OK;
+}
+
+// the edges of the current result's compaction: there already, or built now (the compaction and the index below them too)
+int ensure_edges(dskgpu_ctx* ctx, const char* who) {
+    if (const int rc = ensure_unitigs(ctx, who)) return rc;
+    if (ctx->unitigs.e_valid) return DSKGPU_OK;
+    const int rc = build_edges(ctx);
+    if (rc != DSKGPU_OK) {                                                          // the compaction stays: it is whole
+        (void)hipStreamSynchronize(ctx->stream);
+        ctx->unitigs.release_edges(); ctx->marks.clear(); ctx->ev_used = 0;
+        return rc;
+    }
+    ctx->unitigs.e_valid = true;
+    return DSKGPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -228,6 +302,26 @@ int dskgpu_unitigs_stream(dskgpu_ctx* ctx, void* d_bytes, uint64_t capacity) {
         CKL("k_unitig_stream");
     }
     ctx->mark("unitig stream");
+    return finish(ctx);
+}
+
+int dskgpu_unitig_edges(dskgpu_ctx* ctx, dskgpu_unitig_edge_stats* stats) {
+    if (!ctx) return DSKGPU_E_ARG;
+    if (const int rc = ensure_edges(ctx, "dskgpu_unitig_edges")) return rc;
+    if (const int rc = finish(ctx)) return rc;
+    if (stats) *stats = ctx->unitigs.e_stats;
+    return DSKGPU_OK;
+}
+
+int dskgpu_unitig_edges_table(dskgpu_ctx* ctx, void* d_offsets, void* d_targets, void* d_ends) {
+    if (!ctx) return DSKGPU_E_ARG;
+    if (!d_offsets && !d_targets && !d_ends) return fail(ctx, DSKGPU_E_ARG, "dskgpu_unitig_edges_table: no output pointer");
+    if (const int rc = ensure_edges(ctx, "dskgpu_unitig_edges_table")) return rc;
+    const Unitigs& U = ctx->unitigs;
+    const u64 n_or = 2 * U.stats.n_unitigs, ne = U.e_stats.n_edges;
+    if (d_offsets) CK(hipMemcpyAsync(d_offsets, U.e_offsets.p, (n_or + 1) * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    if (ne && d_targets) CK(hipMemcpyAsync(d_targets, U.e_targets.p, ne * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    if (n_or && d_ends) CK(hipMemcpyAsync(d_ends, U.ends.p, n_or * 4, hipMemcpyDeviceToDevice, ctx->stream));
     return finish(ctx);
 }
 

@@ -71,6 +71,16 @@ class _UnitigStats(C.Structure):
     ]
 
 
+class _UnitigEdgeStats(C.Structure):
+    _fields_ = [
+        ("n_edges", C.c_uint64),
+        ("n_self", C.c_uint64),
+        ("n_dead_ends", C.c_uint64),
+        ("max_degree", C.c_uint64),
+        ("reserved", C.c_uint64 * 4),
+    ]
+
+
 MG_BUCKETS = 4096      # DSKGPU_MG_BUCKETS
 MG_SPLIT = 255         # DSKGPU_MG_SPLIT
 
@@ -101,7 +111,8 @@ EXPORTS = [
     "dskgpu_mg_slices_prepare", "dskgpu_mg_scatter_slice", "dskgpu_mg_slices_finish", "dskgpu_mg_count_sliced", "dskgpu_get_stats", "dskgpu_histogram",
     "dskgpu_set_row_order", "dskgpu_num_partitions", "dskgpu_partition_size", "dskgpu_partition_offsets", "dskgpu_partition_copy", "dskgpu_result_device",
     "dskgpu_stage_times", "dskgpu_query_prepare", "dskgpu_query_kmers", "dskgpu_query_reads", "dskgpu_graph_adjacency", "dskgpu_graph_neighbors",
-    "dskgpu_unitigs", "dskgpu_unitigs_rows", "dskgpu_unitigs_table", "dskgpu_unitigs_stream", "dskgpu_k_encode", "dskgpu_k_enumerate", "dskgpu_k_minimizers",
+    "dskgpu_unitigs", "dskgpu_unitigs_rows", "dskgpu_unitigs_table", "dskgpu_unitigs_stream", "dskgpu_unitig_edges", "dskgpu_unitig_edges_table",
+    "dskgpu_k_encode", "dskgpu_k_enumerate", "dskgpu_k_minimizers",
     "dskgpu_group_create", "dskgpu_group_destroy", "dskgpu_group_last_error", "dskgpu_group_size", "dskgpu_group_ctx",
     "dskgpu_group_transport", "dskgpu_group_count", "dskgpu_group_exchanged_words", "dskgpu_group_sliced_steps", "dskgpu_group_histogram", "dskgpu_group_histogram2d",
     "dskgpu_group_get_stats", "dskgpu_group_num_partitions", "dskgpu_group_partition_size", "dskgpu_group_partition_copy",
@@ -194,6 +205,10 @@ def load_library():
     lib.dskgpu_unitigs_table.restype = C.c_int
     lib.dskgpu_unitigs_stream.argtypes = [vp, vp, u64]
     lib.dskgpu_unitigs_stream.restype = C.c_int
+    lib.dskgpu_unitig_edges.argtypes = [vp, C.POINTER(_UnitigEdgeStats)]
+    lib.dskgpu_unitig_edges.restype = C.c_int
+    lib.dskgpu_unitig_edges_table.argtypes = [vp, vp, vp, vp]
+    lib.dskgpu_unitig_edges_table.restype = C.c_int
     lib.dskgpu_k_encode.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_enumerate.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_minimizers.argtypes = [vp, vp, u64, vp, vp]
@@ -641,6 +656,50 @@ class KmerCounter:
         if nb:
             self.unitigs_stream(out.data_ptr(), nb)
         return out
+
+    # -- the edges between the unitigs (include/dskgpu.h: dskgpu_unitig_edges*)
+    def unitig_edges(self) -> dict:
+        """Build the edges between the oriented unitigs U = 2 u + t of the last result (the first of these calls after a count does, with
+        the compaction below them) -> their stats: n_edges, n_self, n_dead_ends, max_degree."""
+        st = _UnitigEdgeStats()
+        self._ck(self._lib.dskgpu_unitig_edges(self._h, C.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in _UnitigEdgeStats._fields_ if name != "reserved"}
+
+    def unitig_edges_table(self, d_offsets: int, d_targets: int, d_ends: int) -> None:
+        """d_offsets: 2 * n_unitigs + 1 u64 (CSR), d_targets: n_edges u32 (the oriented unitigs V), d_ends: 2 * n_unitigs u32 (last(U) as an
+        oriented node 2 r + s), all on the device; any may be 0."""
+        self._ck(self._lib.dskgpu_unitig_edges_table(self._h, *(C.c_void_p(p) if p else None for p in (d_offsets, d_targets, d_ends))))
+
+    def unitig_edges_tensor(self):
+        """-> (int64[2 * n_unitigs + 1] CSR offsets, int32[n_edges] targets V, int32[2 * n_unitigs] last nodes), CUDA tensors."""
+        import torch
+        ne = self.unitig_edges()["n_edges"]
+        n_or = 2 * self.unitigs()["n_unitigs"]
+        dev = torch.device("cuda", self.device)
+        off = torch.zeros(n_or + 1, dtype=torch.int64, device=dev)
+        targets, ends = torch.zeros(ne, dtype=torch.int32, device=dev), torch.zeros(n_or, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()              # the context's stream is not torch's: the zero fill is done before the copies write
+        self.unitig_edges_table(off.data_ptr(), targets.data_ptr() if ne else 0, ends.data_ptr() if n_or else 0)
+        return off, targets, ends
+
+    def write_gfa(self, path: str) -> dict:
+        """The compacted graph of the last result as GFA 1: one S line per unitig (LN = letters, KC = sum of the member rows' abundances),
+        one L line per edge U -> V with the overlap of k - 1 letters.  Plumbing on the host over the stream, the table and the edges.
+        -> dict(n_segments, n_links)."""
+        text = bytes(self.unitigs_stream_tensor().cpu().numpy())
+        ab_sum = self.unitigs_table_tensor()[1].cpu().numpy()
+        off, targets, _ = (t.cpu().numpy() for t in self.unitig_edges_tensor())
+        seqs = text.decode().split("\n")[:-1]
+        assert len(seqs) == len(ab_sum)
+        overlap = "%dM" % (self.kmer_size - 1)
+        with open(path, "w") as f:
+            f.write("H\tVN:Z:1.0\n")
+            for u, seq in enumerate(seqs):
+                f.write("S\t%d\t%s\tLN:i:%d\tKC:i:%d\n" % (u, seq, len(seq), int(ab_sum[u])))
+            for U in range(2 * len(seqs)):
+                for V in targets[off[U]: off[U + 1]]:
+                    f.write("L\t%d\t%s\t%d\t%s\t%s\n" % (U >> 1, "-" if U & 1 else "+", int(V) >> 1, "-" if int(V) & 1 else "+", overlap))
+        return {"n_segments": len(seqs), "n_links": int(len(targets))}
 
     # -- kernel-level entry points (parity tests)
     def k_encode(self, d_bytes: int, nbytes: int, d_packed: int, d_invalid: int) -> None:

@@ -392,6 +392,40 @@ int dskgpu_unitigs_table(dskgpu_ctx* ctx, void* d_offsets, void* d_ab_sum, void*
 /* The unitig stream into d_bytes (device, any alignment).  capacity < stream_bytes, or a null d_bytes: DSKGPU_E_ARG, nothing is written. */
 int dskgpu_unitigs_stream(dskgpu_ctx* ctx, void* d_bytes, uint64_t capacity);
 
+/* ---- unitig links: the EDGES of the compacted de Bruijn graph -- what BCALM writes on every FASTA header (L:+:17:-) and GFA on its L
+ * lines, and where tip clipping, bubble popping and every traversal start: "what hangs on this end of this unitig".
+ * An ORIENTED UNITIG is U = 2 u + t: t = 0 reads unitig u as dskgpu_unitigs_stream gives it, t = 1 reads its reverse complement;
+ * flip(U) = U ^ 1.  With the path o_0 .. o_{L-1} of unitig u (above): first(2u) = o_0, last(2u) = o_{L-1}, first(2u + 1) = flip(o_{L-1}),
+ * last(2u + 1) = flip(o_0).  EDGE U -> V <=> first(V) is in succ(last(U)), succ on oriented nodes as above.  A row that is its own reverse
+ * complement is named only by its forward node 2 r (as its adjacency bits are), so an edge into a palindrome's unitig v always has V = 2 v.
+ * What follows from the definition of the links:
+ *   - every successor of last(U) is first(V) for exactly one V: no edge ever lands inside a unitig (the build checks it; a violation is
+ *     DSKGPU_E_DEVICE, an internal error);
+ *   - the targets of one U are distinct and at most 4, so there are at most 8 * n_unitigs edges;
+ *   - a cycle has exactly the edges 2u -> 2u and 2u + 1 -> 2u + 1: the link that closes it;
+ *   - outside the unitigs of palindromes, U -> V <=> flip(V) -> flip(U).
+ * The edges of U are ordered by the base appended to str(last(U)), in the order A, C, T, G.  The sequences of U and V overlap by k - 1
+ * letters (GFA: "<k-1>M").
+ * The edges are kept in the context with the compaction (about 12 bytes per oriented unitig + 4 per edge; 24 bytes per oriented unitig
+ * more while they are built): built on first use by either call -- which builds the compaction and the lookup index below them when they
+ * are not there yet --, dropped when the next count starts and by dskgpu_destroy.  Both calls run on the context's stream, are synchronous
+ * on return and change nothing else in the context: the reads (a kept encoding included), the result, the stats and the sender state stay as
+ * they are.  Stage time: "unitig edges" (and those of the compaction when the call built it).
+ * Errors: a null ctx DSKGPU_E_ARG; no result DSKGPU_E_STATE; more than 2^31 - 1 rows DSKGPU_E_STATE; a context with world_size > 1
+ * DSKGPU_E_STATE (the text names world_size): a rank's unitigs are not the group's; the index, the compaction or the edges do not fit
+ * DSKGPU_E_NOMEM, and the context, its result and what was built before stay usable.  A result with zero rows: all-zero stats,
+ * d_offsets[0] = 0, nothing else is written. */
+typedef struct dskgpu_unitig_edge_stats {
+    uint64_t n_edges, n_self, n_dead_ends, max_degree, reserved[4];
+} dskgpu_unitig_edge_stats;                              /* 64 bytes */
+/* Build the edges now (optional) and fill `stats` (may be NULL): edges, those whose two unitigs are the same u, oriented unitigs without
+ * an edge, the most edges of one oriented unitig (0..4). */
+int dskgpu_unitig_edges(dskgpu_ctx* ctx, dskgpu_unitig_edge_stats* stats);
+/* On the device: d_offsets u64[2 * n_unitigs + 1], the edges of U are d_targets[d_offsets[U] .. d_offsets[U + 1]) (CSR;
+ * d_offsets[2 * n_unitigs] = n_edges); d_targets u32[n_edges] the oriented unitigs V; d_ends u32[2 * n_unitigs], ends[U] = last(U) as an
+ * oriented node number 2 r + s -- the way back from a unitig to its rows.  Any may be NULL; all NULL: DSKGPU_E_ARG. */
+int dskgpu_unitig_edges_table(dskgpu_ctx* ctx, void* d_offsets, void* d_targets, void* d_ends);
+
 /* ---- the same call on N GPUs of one node, inside ONE process (what `dsk -nb-gpus N` runs): the reference's
  * single `execute()` (src/DSK.cpp:55-60) still leaves ONE storage with a flat list of solid partitions
  * (utils/dsk2ascii.cpp:61,77).  A group owns one ctx per rank (world_size = n_ranks, rank r on devices[r], its own
