@@ -14,7 +14,7 @@
 #include <system_error>
 #include "engine.h"
 #include "kernels.h"
-#include "superkmer.h"
+#include "superkmer_recv.h"
 #include "rawparse.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -144,14 +144,14 @@ int run_encode(dskgpu_ctx* ctx, const uint8_t* d_bytes, u64 n, u64* nwords_out) 
     return DSKGPU_OK;
 }
 
+}  // namespace
+
 // the 2-bit form of the context's current reads: encoded now, or kept from dskgpu_encode_reads (the ASCII bytes may be gone by then)
 int encode_current(dskgpu_ctx* ctx, u64* nwords_out) {
     if (ctx->enc_keep) { *nwords_out = (ctx->n_bytes + 31) / 32; ctx->enc_fresh = false; return DSKGPU_OK; }
     if (!ctx->d_reads && ctx->n_bytes) return fail(ctx, DSKGPU_E_STATE, "the reads were released (dskgpu_encode_reads) and their 2-bit form has been overwritten: set the reads again");
     return run_encode(ctx, ctx->d_reads, ctx->n_bytes, nwords_out);
 }
-
-}  // namespace
 
 // ---- K1 into buffers of the caller's choice: the context's own (run_encode) or a query's (query.hip)
 int encode_into(dskgpu_ctx* ctx, const uint8_t* d_bytes, u64 n, u64* packed, u32* inval) {
@@ -415,7 +415,7 @@ int rec_gate_upto(dskgpu_ctx* ctx, u32 upto) {
 int rec_gate_all(dskgpu_ctx* ctx) { return rec_gate_upto(ctx, 0xFFFFFFFFu); }
 
 int sk_sizes(dskgpu_ctx* ctx, u64* total_out) {
-    const u64 nrec = ctx->rec_n; const u32 R = ctx->sk_sp.R;
+    const u64 nrec = ctx->rec_n; const u32 R = ctx->sender.sp.R;
     { const int e = rec_gate_all(ctx); if (e) return e; }      // (a sliced receive: every record has to be there)
     u64 nch = std::min<u64>((nrec + SKX_NT - 1) / SKX_NT, (u64)ctx->num_cu * 16);
     u64 rpc = (nrec + nch - 1) / nch;
@@ -450,7 +450,7 @@ int expand_records(dskgpu_ctx* ctx, u64 total) {
     }
     { const int e = rec_gate_all(ctx); if (e) return e; }
     CK(ctx->sk_keys.ensure((total + 1) * sizeof(Key)));
-    hipLaunchKernelGGL(k_sk_expand<W>, dim3((unsigned)ctx->rec_nch), dim3(SKX_NT), 0, ctx->stream, ctx->rec_src, ctx->rec_n, ctx->sk_sp.R,
+    hipLaunchKernelGGL(k_sk_expand<W>, dim3((unsigned)ctx->rec_nch), dim3(SKX_NT), 0, ctx->stream, ctx->rec_src, ctx->rec_n, ctx->sender.sp.R,
                        (int)ctx->cfg.kmer_size, (u32)ctx->rec_rpc, ctx->sk_cbase.as<u64>(), ctx->sk_keys.as<Key>());
     CKL("k_sk_expand");
     ctx->rec_expanded = true;
@@ -686,7 +686,7 @@ int pass_layout1(dskgpu_ctx* ctx, PassState<W>& ps) {
     const KeySource<W>& src = ps.src;
     const Plan& pl = ps.pl;
     Opt1Spec& o1 = ps.o1;
-    o1 = Opt1Spec{nullptr, 0u, 0u, ps.sc + SC_OVF1, nullptr, ctx->sk_sp.R, ctx->gstats.as<u64>() + 2, nullptr, nullptr, 0u, nullptr, 0ull, {0ull, 0ull, 0ull, 0ull}, 0u};
+    o1 = Opt1Spec{nullptr, 0u, 0u, ps.sc + SC_OVF1, nullptr, ctx->sender.sp.R, ctx->gstats.as<u64>() + 2, nullptr, nullptr, 0u, nullptr, 0ull, {0ull, 0ull, 0ull, 0ull}, 0u};
     // (the per-bin slice ends need 4 more bytes of LDS per bin: plans above 1634 level-1 bins keep UNIFORM slices, mean-sized, no sample)
     const bool uniform1 = scatter_lds(W, pl.P1, true) > 160 * 1024;
     if (ps.opt1) {
@@ -736,7 +736,7 @@ int pass_layout1(dskgpu_ctx* ctx, PassState<W>& ps) {
                 CK(ctx->smp_keys.ensure(rec_units * sizeof(Key) + nchk * 8 + 64));
                 u64* d_cbeg = reinterpret_cast<u64*>(ctx->smp_keys.as<char>() + rec_units * sizeof(Key));
                 CK(hipMemcpyAsync(d_cbeg, cbeg.data(), nchk * 8, hipMemcpyHostToDevice, ctx->stream));
-                hipLaunchKernelGGL(k_sk_sample_keys<W>, dim3((unsigned)nchk), dim3(SKX_NT), 0, ctx->stream, ctx->rec_src, ctx->rec_n, ctx->sk_sp.R, (int)ctx->cfg.kmer_size,
+                hipLaunchKernelGGL(k_sk_sample_keys<W>, dim3((unsigned)nchk), dim3(SKX_NT), 0, ctx->stream, ctx->rec_src, ctx->rec_n, ctx->sender.sp.R, (int)ctx->cfg.kmer_size,
                                    (const u64*)d_cbeg, (u32)NR, ctx->smp_keys.as<Key>());
                 CKL("k_sk_sample_keys");
                 d_keys_s = ctx->smp_keys.as<Key>();
@@ -1295,110 +1295,6 @@ int level0_materialise(dskgpu_ctx* ctx, u64 nwords, u32 lo, u32 npass, u64 reser
     return DSKGPU_OK;
 }
 
-// ---- level 0 of a multi-pass count as super-k-mer RECORDS: the passes are "virtual owners"
-// What the multi-GPU step does between GPUs, one GPU does between its passes: the pass of a k-mer is the OWNER that the minimizer
-// repartition gives its window (owner = table[bucket of the minimizer], G owners = G passes; heavy buckets are split by k-mer),
-// a sweep over the 2-bit reads writes the records of as many owners as HBM holds (k_sk_scatter with an owner window, every owner
-// with its own slice length and region), and every pass then runs its level 1 straight from its records (k_scatter<W, 2, 1>),
-// sized from a sample of them.  Records are 2.3-2.5 bytes per k-mer where a key array takes 8 (16 for two-word keys): a 90 Gbp
-// input goes through in 2-3 sweeps instead of 7, 30 Gbp in one -- and the sender never forms a k-mer, which makes a sweep cheaper
-// than the key-array one as well.  DSK writes super-k-mers to its partition files for the same reason (CHANGELOG.md:13;
-// doc/paper.tex:65-67 for the passes).  Needs 20 <= k <= 64 (records) and <= SK_MAX_OWNERS passes; anything else, or a slice
-// of the sampled layout that overflows, takes the key-array level 0 / the pass filter instead (ctx->rec_l0_off).
-void sk_geometry(dskgpu_ctx* ctx, u64 nwords);
-// the sender kernels with k and m at compile time for the BASELINE configs (superkmer.h: sk_tile_fx), at run time otherwise
-#define SK_DISPATCH(ctx_, SP_, CALL) do { \
-        if (!(ctx_)->tune.sk_generic && (SP_).k == 31 && (SP_).m == 10) { CALL(31, 10); } \
-        else if (!(ctx_)->tune.sk_generic && (SP_).k == 63 && (SP_).m == 10) { CALL(63, 10); } \
-        else { CALL(0, 0); } } while (0)
-int upload_table(dskgpu_ctx* ctx);
-struct RecL0 { u32 G = 0; u64 nch = 0; u32 slice[SK_MAX_OWNERS] = {0}; u64 region[SK_MAX_OWNERS] = {0}; };      // region[o]: records of owner o's region (nch * slice[o])
-#define REC_L0_NO 2001             // rec_l0_prepare / _sweep: this input does not take the record path (not an error)
-
-int rec_l0_prepare(dskgpu_ctx* ctx, u64 nwords, u32 G, RecL0* rl) {
-    SkParams& sp = ctx->sk_sp;
-    sk_geometry(ctx, nwords);
-    sp.G = G; sp.olo = 0; sp.ohi = G; sp.oslice = nullptr; sp.obase = nullptr;
-    const u64 nch = sp.nchunks, tpc = sp.tiles_per_chunk;
-    const u32 step = tpc >= 16 ? 16u : 1u;
-    // 1. the repartition table for G owners, from the sampled k-mer load of every minimizer bucket
-    {
-        SkParams ss = sp; ss.sample_step = step; ss.table = nullptr;
-        CK(ctx->sk_load.ensure((size_t)SK_BUCKETS * 8));
-        CK(hipMemsetAsync(ctx->sk_load.p, 0, (size_t)SK_BUCKETS * 8, ctx->stream));
-#define SK_CALL(K_, M_) hipLaunchKernelGGL((k_sk_sample<K_, M_>), dim3(ss.nchunks), dim3(SK_NT), 0, ctx->stream, ctx->packed.as<u64>(), ctx->inval.as<u32>(), ss, ctx->sk_load.as<unsigned long long>())
-        SK_DISPATCH(ctx, ss, SK_CALL);
-#undef SK_CALL
-        CKL("k_sk_sample");
-        std::vector<uint64_t> loads(SK_BUCKETS);
-        CK(hipMemcpyAsync(loads.data(), ctx->sk_load.p, (size_t)SK_BUCKETS * 8, hipMemcpyDeviceToHost, ctx->stream));
-        CK(hipStreamSynchronize(ctx->stream));
-        ctx->h_table.resize(SK_BUCKETS);
-        dskgpu_mg_make_table(loads.data(), G, ctx->h_table.data());
-        ctx->table_dirty = true;
-        const int rc = upload_table(ctx);
-        if (rc) return rc;
-    }
-    // 2. records per (owner, chunk), counted on every 16th tile (all tiles of a small input): the slice of an (owner, chunk) pair
-    const u64 M = (u64)G * nch;
-    CK(ctx->mat1.ensure((M + 1) * 4));
-    CK(ctx->sk_sent.ensure(3 * SK_MAX_OWNERS * 8));
-    CK(hipMemsetAsync(ctx->sk_sent.as<u64>() + SK_MAX_OWNERS, 0, SK_MAX_OWNERS * 8, ctx->stream));
-    sp.sample_step = step;
-#define SK_CALL(K_, M_) hipLaunchKernelGGL((k_sk_hist<K_, M_>), dim3((unsigned)nch), dim3(SK_NT), 0, ctx->stream, ctx->packed.as<u64>(), ctx->inval.as<u32>(), sp, ctx->mat1.as<u32>(), \
-                                          ctx->sk_sent.as<unsigned long long>() + SK_MAX_OWNERS)
-    SK_DISPATCH(ctx, sp, SK_CALL);
-#undef SK_CALL
-    CKL("k_sk_hist");
-    std::vector<u32> cells(M);
-    CK(hipMemcpyAsync(cells.data(), ctx->mat1.p, M * 4, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    const u64 sampled_tiles = (tpc + step - 1) / step;
-    rl->G = G; rl->nch = nch;
-    for (u32 o = 0; o < G; ++o) {
-        u64 tot = 0, mx = 0;
-        for (u64 c = 0; c < nch; ++c) { const u64 v = cells[(size_t)o * nch + c]; tot += v; mx = std::max(mx, v); }
-        u64 sl;
-        if (step == 1) sl = mx + 8;                                                        // every tile counted: the busiest chunk's figure is exact
-        else { sl = tot * tpc / (sampled_tiles * nch) + 1; sl += sl * 2 / 25 + 128; }      // the mean per chunk, scaled, + 8 % + 128 (as the multi-GPU sender)
-        if (ctx->tune.sk_slice) sl = ctx->tune.sk_slice;                                   // tests
-        if (sl * nch >= 0xFFFF0000ull) return REC_L0_NO;                                   // (record positions inside an owner's region stay 32-bit on the reading side)
-        rl->slice[o] = (u32)sl; rl->region[o] = sl * nch;
-    }
-    ctx->mark("level0_size");
-    return DSKGPU_OK;
-}
-
-// one sweep: the records of owners [olo, ohi) into ctx->l0buf; base[o] = first 8-byte word of owner o's region.  -> REC_L0_NO when a
-// slice overflowed (the sampled layout did not hold: the caller starts over on the key-array path)
-int rec_l0_sweep(dskgpu_ctx* ctx, const RecL0& rl, u32 olo, u32 ohi, u64 (&base_words)[SK_MAX_OWNERS]) {
-    SkParams sp = ctx->sk_sp;
-    u64 obase[SK_MAX_OWNERS] = {0}; u32 osl[SK_MAX_OWNERS] = {0};
-    u64 tot = 0;
-    for (u32 o = 0; o < rl.G; ++o) { osl[o] = rl.slice[o]; obase[o] = tot; if (o >= olo && o < ohi) tot += rl.region[o]; base_words[o] = obase[o] * sp.R; }
-    CK(ctx->l0buf.ensure(tot * sp.R * 8 + 64));
-    CK(ctx->sk_lay.ensure(SK_MAX_OWNERS * 12));
-    CK(hipMemcpyAsync(ctx->sk_lay.p, obase, sizeof obase, hipMemcpyHostToDevice, ctx->stream));
-    CK(hipMemcpyAsync(ctx->sk_lay.as<u64>() + SK_MAX_OWNERS, osl, sizeof osl, hipMemcpyHostToDevice, ctx->stream));
-    sp.olo = olo; sp.ohi = ohi; sp.obase = ctx->sk_lay.as<unsigned long long>(); sp.oslice = reinterpret_cast<const u32*>(ctx->sk_lay.as<u64>() + SK_MAX_OWNERS);
-    sp.c0 = 0; sp.c0g = 0; sp.clen = (u32)rl.nch; sp.rbase = 0; sp.slice = 0;
-    u32* sc = ctx->scalars.as<u32>();
-    CK(hipMemsetAsync(ctx->sk_sent.p, 0, SK_MAX_OWNERS * 8, ctx->stream));
-    CK(hipMemsetAsync(sc + SC_OVF1, 0, 4, ctx->stream));
-#define SK_CALL(K_, M_) hipLaunchKernelGGL((k_sk_scatter<true, K_, M_>), dim3(sp.nchunks), dim3(SK_NT), 0, ctx->stream, ctx->packed.as<u64>(), ctx->inval.as<u32>(), sp, \
-                                          (const unsigned long long*)nullptr, ctx->l0buf.as<u64>(), sc + SC_OVF1, ctx->sk_sent.as<unsigned long long>())
-    SK_DISPATCH(ctx, sp, SK_CALL);
-#undef SK_CALL
-    CKL("k_sk_scatter(passes)");
-    ctx->mark("level0");
-    CK(hipMemcpyAsync(&ctx->h_ovf1, sc + SC_OVF1, 4, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipMemcpyAsync(ctx->h_sk_sent, ctx->sk_sent.p, SK_MAX_OWNERS * 8, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));        // (obase / osl are locals)
-    if (ctx->tune.verbose) fprintf(stderr, "[dskgpu] level 0 (records): passes %u..%u of %u materialised, %.2f GB%s\n", olo, ohi - 1, rl.G, (double)tot * sp.R * 8e-9,
-                                   ctx->h_ovf1 ? " -- a slice overflowed: starting over on the key-array path" : "");
-    return ctx->h_ovf1 ? REC_L0_NO : DSKGPU_OK;
-}
-
 // The pipeline behind dskgpu_count / dskgpu_mg_count: encode once, then one or several passes over
 // the key space (several when the input holds more k-mers than a pass may: < 2^32 offsets, and the
 // ping-pong buffers must fit HBM -- the in-memory counterpart of DSK's disk passes), then the row sort.
@@ -1453,20 +1349,15 @@ int run_pipeline(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_
     // two-word keys: a pass holds what 32-bit key indices address (regions of 2180 keys at <= 60 % fill)
     const u64 hard_max = W == 2 && !ctx->max_keys_per_pass ? std::min<u64>(max_keys, 2400000000ull) : max_keys;
     u32 npass = (u32)std::max<u64>(1, (n_keys + pass_keys - 1) / pass_keys);
-    // Several passes from reads, 20 <= k <= 64: the passes are virtual OWNERS and a sweep materialises super-k-mer records (above).
+    // Several passes from reads, 20 <= k <= 64: the passes are virtual OWNERS and a sweep materialises super-k-mer records (sender.hip: rec_l0_*).
     bool rec_l0 = W <= 2 && from_reads && ctx->have_nvalid && ctx->sk_mode && ctx->cfg.world_size == 1 && !ctx->tune.no_level0 && !ctx->tune.l0_keys && !ctx->rec_l0_off &&
                   (npass > 1 || n_keys > hard_max);
     RecL0 rl;
-    // The record-based level 0 borrows the multi-GPU sender state of this context (sk_sp: G "owners" = passes, the owner window, the
-    // repartition table for G owners).  Whatever way this function is left, the context gets back the state dskgpu_create /
-    // dskgpu_mg_set_table gave it: a later dskgpu_mg_* call on a world_size = 1 context must see ONE owner again (it
-    // looped over up to 64 owners into the caller's world_size-sized arrays).
-    struct SenderStateGuard {
-        dskgpu_ctx* c; SkParams sp; std::vector<uint8_t> table; bool armed = false;
-        ~SenderStateGuard() { if (armed) { c->sk_sp = sp; c->h_table.swap(table); c->table_dirty = true; c->sk_prepared = false; c->enc_fresh = false; } }
-    } sender_guard{ctx, ctx->sk_sp, ctx->h_table};
+    // The level 0 has a Sender of its own (owners = passes, a table for that many) and leaves the exchange's alone.  Only scratch is shared: the
+    // passes overwrite ctx->packed / mat1, so a send layout or an encoding kept for the exchange is void from here on, however this function is left.
+    // Clearing the two flags once, here, covers every exit below: only sk_prepare and dskgpu_mg_sample set them, and nothing in this function calls either.
     if (rec_l0) {
-        sender_guard.armed = true;
+        ctx->sender.prepared = false; ctx->enc_fresh = false;
         u64 want = ctx->max_keys_per_pass ? max_keys : ctx->tune.mp_pass_mkeys ? (u64)ctx->tune.mp_pass_mkeys * 1000000ull : (W == 1 ? 1200000000ull : 1000000000ull);
         u64 G = (n_keys + want - 1) / want;
         if (G < 2) G = 2;
@@ -1474,7 +1365,7 @@ int run_pipeline(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_
         // (owners are balanced to a few per cent by the repartition table: 15 % head-room under what a pass may hold)
         if (n_keys / G + n_keys / G / 7 > hard_max && !ctx->max_keys_per_pass) rec_l0 = false;
         else {
-            const int rc = rec_l0_prepare(ctx, nwords, (u32)G, &rl);
+            const int rc = rec_l0_prepare(ctx, ctx->l0_sender, nwords, (u32)G, &rl);
             if (rc == REC_L0_NO) rec_l0 = false; else if (rc) return rc;
             else npass = (u32)G;
         }
@@ -1527,19 +1418,19 @@ int run_pipeline(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_
                     const u64 rows_want = rows_sized ? 0 : n_keys / 16 * (8ull * W + 4);
                     const u64 need = nper * (W == 1 ? 30ull : 50ull) + (4ull << 30) + (rows_want > rows_have ? rows_want - rows_have : 0);
                     const u64 room = free_b + have > need ? free_b + have - need : 0;
-                    const u64 R8 = (u64)ctx->sk_sp.R * 8;
+                    const u64 R8 = (u64)ctx->l0_sender.sp.R * 8;
                     u64 left = 0; for (u32 o = p; o < npass; ++o) left += rl.region[o] * R8;
                     const u64 nsw = std::max<u64>(1, (left + std::max<u64>(room, 1) - 1) / std::max<u64>(room, 1));      // sweeps still needed: equal shares
                     const u64 target = (left + nsw - 1) / nsw;
                     u64 acc = 0; u32 hi = p;
                     while (hi < npass && (hi == p || (acc + rl.region[hi] * R8 <= room && acc < target))) { acc += rl.region[hi] * R8; ++hi; }
                     if (ctx->tune.l0_passes) hi = std::min<u32>(npass, p + ctx->tune.l0_passes);      // tests
-                    rc = rec_l0_sweep(ctx, rl, p, hi, r_base);
+                    rc = rec_l0_sweep(ctx, ctx->l0_sender, rl, p, hi, r_base);
                     if (rc == REC_L0_NO) { restart = true; break; }
                     if (rc) return rc;
                     r_hi = hi; ++sweeps;
                 }
-                const u64 nk_in = ctx->h_sk_sent[p];
+                const u64 nk_in = ctx->l0_sender.h_sent[p];
                 ctx->rec_src = ctx->l0buf.as<u64>() + r_base[p]; ctx->rec_n = rl.region[p]; ctx->rec_expanded = false; ctx->rec_sized = false;
                 ctx->rec_hint = 0; ctx->rec_hint_est = false; ctx->rec_slice_end.clear(); ctx->rec_gate = nullptr;
                 if (nk_in == 0) { rc = DSKGPU_OK; CK(hipMemsetAsync(ctx->ghist.p, 0, ((size_t)ctx->cfg.histo_max + 1) * 8, ctx->stream)); }
@@ -1596,7 +1487,7 @@ int run_pipeline(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_
             }
             tot_rows += ns;
         }
-        if (rec_l0) { ctx->sk_prepared = false; ctx->enc_fresh = false; }      // (the sender state of this context was used for the passes)
+        if (rec_l0) { ctx->sender.prepared = false; ctx->enc_fresh = false; }      // (packed / mat1 were the passes' scratch)
         if (restart) {          // the record layout did not hold for these reads: the same count on the key-array path
             ctx->rec_l0_off = true;
             ctx->resolve_marks();
@@ -1635,9 +1526,6 @@ int run_pipeline(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_
     }
 }
 
-}  // namespace
-
-namespace {
 template <int W>
 int mg_scatter_impl(dskgpu_ctx* ctx, void* d_send, uint64_t* send_words) {
     typedef typename KeyT<W>::T Key;
@@ -1675,218 +1563,11 @@ int mg_scatter_impl(dskgpu_ctx* ctx, void* d_send, uint64_t* send_words) {
     return DSKGPU_OK;
 }
 
-// ---- repartition table of the super-k-mer owner map (superkmer.h)
-void default_table(uint32_t world, uint8_t* table) { for (u32 b = 0; b < SK_BUCKETS; ++b) table[b] = (uint8_t)((b * world) / SK_BUCKETS); }
-int upload_table(dskgpu_ctx* ctx) {
-    if (ctx->h_table.size() != SK_BUCKETS) { ctx->h_table.resize(SK_BUCKETS); default_table(ctx->cfg.world_size, ctx->h_table.data()); ctx->table_dirty = true; }
-    if (ctx->table_dirty) {
-        CK(ctx->sk_table.ensure(SK_BUCKETS));
-        CK(hipMemcpyAsync(ctx->sk_table.p, ctx->h_table.data(), SK_BUCKETS, hipMemcpyHostToDevice, ctx->stream));
-        CK(hipStreamSynchronize(ctx->stream));
-        ctx->table_dirty = false;
-    }
-    ctx->sk_sp.table = ctx->sk_table.as<unsigned char>();
-    ctx->sk_sp.has_split = std::find(ctx->h_table.begin(), ctx->h_table.end(), (uint8_t)SK_SPLIT) != ctx->h_table.end() ? 1u : 0u;
-    return DSKGPU_OK;
-}
-// tiles / chunks of the sender kernels over the encoded stream
-void sk_geometry(dskgpu_ctx* ctx, u64 nwords) {
-    SkParams& sp = ctx->sk_sp;
-    sp.ngroups = nwords * 2;
-    sp.ntiles = std::max<u64>(1, (sp.ngroups + SK_GROUPS - 1) / SK_GROUPS);
-    // whole rounds of blocks: the k = 31 kernels (68 VGPRs, 50 KB of LDS) run three 512-thread blocks per CU, the others two
-    const u64 per_cu = (!ctx->tune.sk_generic && sp.k == 31 && sp.m == 10) ? 9 : 8;
-    u64 nch = std::min<u64>(std::max<u64>(1, sp.ntiles / 8), (u64)ctx->num_cu * per_cu);     // >= 8 tiles per chunk when there are that many
-    const u64 tpc = (sp.ntiles + nch - 1) / nch;
-    nch = (sp.ntiles + tpc - 1) / tpc;
-    sp.tiles_per_chunk = (u32)tpc; sp.nchunks = (u32)nch;
-    sp.c0 = 0; sp.c0g = 0; sp.clen = (u32)nch; sp.rbase = 0;      // one layout group: the whole step
-}
-
-// ---- multi-GPU exchange as super-k-mer records (superkmer.h)
-// Sender, step 1: encode + count the records per (owner, chunk) + scan.  Leaves the record range of every
-// owner in h_starts; the exact send size is known before the caller allocates the send buffer.
-int sk_prepare(dskgpu_ctx* ctx) {
-    ctx->st_names.clear(); ctx->st_ms.clear(); ctx->marks.clear(); ctx->ev_used = 0;
-    ctx->sk_prepared = false;
-    ctx->mark("start");
-    u64 nwords = 0;
-    int rc = DSKGPU_OK;
-    if (ctx->enc_fresh) { nwords = (ctx->n_bytes + 31) / 32; ctx->enc_fresh = false; }      // (the repartition sample of this step just encoded these reads)
-    else if ((rc = encode_current(ctx, &nwords))) return rc;
-    ctx->mark("encode");
-    SkParams& sp = ctx->sk_sp;
-    sk_geometry(ctx, nwords);
-    if ((rc = upload_table(ctx))) return rc;
-    const u64 nch = sp.nchunks, tpc = sp.tiles_per_chunk;
-    const u64 M = (u64)sp.G * nch;
-    CK(ctx->scalars.ensure(SC_COUNT * 4));
-    u32* h_sc = ctx->h_sc;
-    std::memset(h_sc, 0, sizeof(ctx->h_sc));
-    u32* sc = ctx->scalars.as<u32>();
-    CK(hipMemcpyAsync(sc, h_sc, sizeof(ctx->h_sc), hipMemcpyHostToDevice, ctx->stream));
-    CK(ctx->mat1.ensure((M + 1) * 4));
-    // Exact layout: count every record, one scan places them.  Slice layout (default): count the records of every
-    // 16th tile only, give every (owner, chunk) pair one slice of the estimated mean + 8 % + 128 records; the scatter
-    // pads the slices with zero-length records.  Saves the full counting pass (1.95 of 5 ms); ~8 % more words to send.
-    // Either way every record position is 64-bit from here on (the count matrix -- <= 64 owners x 2048 chunks of u32 -- comes to
-    // the host, where it is summed / scanned in 64 bits): a rank's shard may be of any size.  The reference's own human run is
-    // ONE execute() over 160 GB of reads (doc/human_log:3-4,20-24; README.md:126-130); on 8 GPUs that is 11.3 GB per rank.
-    const bool slices = !ctx->sk_exact && !ctx->tune.sk_exact && tpc >= 8;
-    sp.sample_step = slices ? 16u : 1u;
-    CK(ctx->sk_sent.ensure(3 * SK_MAX_OWNERS * 8));            // [k-mers sent per owner | sampled k-mers per owner | overflow flag of a sliced step]
-    CK(hipMemsetAsync(ctx->sk_sent.as<u64>() + SK_MAX_OWNERS, 0, SK_MAX_OWNERS * 8, ctx->stream));
-#define SK_CALL(K_, M_) hipLaunchKernelGGL((k_sk_hist<K_, M_>), dim3((unsigned)nch), dim3(SK_NT), 0, ctx->stream, ctx->packed.as<u64>(), ctx->inval.as<u32>(), sp, ctx->mat1.as<u32>(), \
-                                          ctx->sk_sent.as<unsigned long long>() + SK_MAX_OWNERS)
-    SK_DISPATCH(ctx, sp, SK_CALL);
-#undef SK_CALL
-    CKL("k_sk_hist");
-    CK(hipMemcpyAsync(ctx->h_sk_est, ctx->sk_sent.as<u64>() + SK_MAX_OWNERS, SK_MAX_OWNERS * 8, hipMemcpyDeviceToHost, ctx->stream));
-    ctx->mark("mg_hist");
-    ctx->h_sk_cells.resize(M);
-    CK(hipMemcpyAsync(ctx->h_sk_cells.data(), ctx->mat1.p, M * 4, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    ctx->h_rstart.assign(sp.G + 1, 0);
-    ctx->sk_slices = false;
-    if (slices) {
-        u64 worst = 0;                                       // sampled records of the busiest owner
-        for (u32 o = 0; o < sp.G; ++o) { u64 t = 0; for (u64 c = 0; c < nch; ++c) t += ctx->h_sk_cells[(size_t)o * nch + c]; worst = std::max(worst, t); }
-        const u64 sampled_tiles = (tpc + sp.sample_step - 1) / sp.sample_step;            // per chunk
-        u64 slice = worst * tpc / (sampled_tiles * nch) + 1;                              // records per (owner, chunk), estimated
-        const u64 min_slice = ctx->tune.sk_minslice;                                      // (tests lower it)
-        const bool small = slice < min_slice || worst < 20000;    // fixed slack too visible in the send volume, or too few sampled records to trust the estimate
-        slice += slice * 2 / 25 + 128;
-        if (ctx->tune.sk_slice) slice = ctx->tune.sk_slice;                               // tests
-        if (!small && slice < 0xFFFF0000ull) {                                            // (a block's cursor inside ONE slice is 32-bit)
-            sp.slice = (u32)slice;
-            for (u32 o = 0; o < sp.G; ++o) ctx->h_sk_est[o] = ctx->h_sk_est[o] * tpc / sampled_tiles;      // sampled tiles -> all tiles
-            for (u32 o = 0; o <= sp.G; ++o) ctx->h_rstart[o] = (u64)o * nch * slice;
-            ctx->sk_slices = true;
-        } else {                                             // small input: count exactly after all
-            ctx->sk_exact = true;
-            return sk_prepare(ctx);
-        }
-    } else {
-        // exact layout: the 64-bit exclusive scan of the owner-major count matrix
-        ctx->h_sk_cb64.resize(M + 1);
-        u64 run = 0;
-        for (u64 i = 0; i < M; ++i) { ctx->h_sk_cb64[i] = run; run += ctx->h_sk_cells[i]; }
-        ctx->h_sk_cb64[M] = run;
-        for (u32 o = 0; o <= sp.G; ++o) ctx->h_rstart[o] = ctx->h_sk_cb64[(u64)o * nch];
-        CK(ctx->sk_cb64.ensure((M + 1) * 8));
-        CK(hipMemcpyAsync(ctx->sk_cb64.p, ctx->h_sk_cb64.data(), (M + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        CK(hipStreamSynchronize(ctx->stream));
-    }
-    ctx->resolve_marks();
-    ctx->sk_prepared = true;
-    return DSKGPU_OK;
-}
-
-// Sender, step 2: write the records, grouped by owner, into the caller's buffer.
-int sk_scatter(dskgpu_ctx* ctx, void* d_send, uint64_t capacity_words, uint64_t* send_words) {
-    int rc;
-    if (!ctx->sk_prepared && (rc = sk_prepare(ctx))) return rc;
-    const SkParams& sp = ctx->sk_sp;
-    if (capacity_words < ctx->h_rstart[sp.G] * sp.R) return fail(ctx, DSKGPU_E_ARG, "send buffer too small");
-    ctx->marks.clear(); ctx->ev_used = 0;
-    ctx->mark("start");
-    u32* sc = ctx->scalars.as<u32>();
-    CK(hipMemsetAsync(ctx->sk_sent.p, 0, SK_MAX_OWNERS * 8, ctx->stream));
-    if (ctx->sk_slices) {
-        CK(hipMemsetAsync(sc + SC_OVF1, 0, 4, ctx->stream));
-#define SK_CALL(K_, M_) hipLaunchKernelGGL((k_sk_scatter<true, K_, M_>), dim3(sp.nchunks), dim3(SK_NT), 0, ctx->stream, ctx->packed.as<u64>(), ctx->inval.as<u32>(), sp, \
-                                          (const unsigned long long*)nullptr, static_cast<u64*>(d_send), sc + SC_OVF1, ctx->sk_sent.as<unsigned long long>())
-        SK_DISPATCH(ctx, sp, SK_CALL);
-#undef SK_CALL
-    } else {
-#define SK_CALL(K_, M_) hipLaunchKernelGGL((k_sk_scatter<false, K_, M_>), dim3(sp.nchunks), dim3(SK_NT), 0, ctx->stream, ctx->packed.as<u64>(), ctx->inval.as<u32>(), sp, \
-                                          (const unsigned long long*)ctx->sk_cb64.as<unsigned long long>(), static_cast<u64*>(d_send), sc + SC_OVF1, ctx->sk_sent.as<unsigned long long>())
-        SK_DISPATCH(ctx, sp, SK_CALL);
-#undef SK_CALL
-    }
-    CKL("k_sk_scatter");
-    ctx->mark("mg_scatter");
-    if (ctx->sk_slices) CK(hipMemcpyAsync(&ctx->h_ovf1, sc + SC_OVF1, 4, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipMemcpyAsync(ctx->h_sk_sent, ctx->sk_sent.p, SK_MAX_OWNERS * 8, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    ctx->resolve_marks();
-    if (ctx->sk_slices && ctx->h_ovf1) {      // a slice overflowed: exact counts for these reads from now on (and right away)
-        ctx->sk_exact = true; ctx->sk_prepared = false;
-        if ((rc = sk_prepare(ctx))) return rc;
-        return sk_scatter(ctx, d_send, capacity_words, send_words);      // may report "send buffer too small": ask for the capacity again
-    }
-    for (u32 o = 0; o < sp.G; ++o) send_words[o] = (ctx->h_rstart[o + 1] - ctx->h_rstart[o]) * sp.R;
-    ctx->sk_prepared = false;      // packed/mat1 are scratch of the next call
-    return DSKGPU_OK;
-}
-
-// ---- a step in slices (the exchange of slice i overlaps the sender's slice i + 1 and the receiver's level 1 of slice i - 1).
-// Only with the sampled send layout (its sizes are known before a record exists): slice s = the chunks [s * nch / S, (s + 1) * nch / S),
-// a layout group of its own in the send buffer (SkParams::c0g, clen, rbase), owner-major inside.
-void sk_slice_range(const SkParams& sp, u32 S, u32 s, u32* cb, u32* ce) { *cb = (u32)((u64)s * sp.nchunks / S); *ce = (u32)((u64)(s + 1) * sp.nchunks / S); }
-
-int sk_slices_prepare(dskgpu_ctx* ctx, u32 want, u32* nslices, uint64_t* send_words, uint64_t* kmers_est) {
-    int rc;
-    *nslices = 0; ctx->sk_nslices = 0;
-    if (!ctx->sk_prepared && (rc = sk_prepare(ctx))) return rc;
-    const SkParams& sp = ctx->sk_sp;
-    if (!ctx->sk_slices || want < 2) return DSKGPU_OK;          // exact layout (small input, or a slice overflowed before): one piece
-    const u32 S = std::min<u32>(want, sp.nchunks);
-    if (S < 2) return DSKGPU_OK;
-    for (u32 sl = 0; sl < S; ++sl) {
-        u32 cb, ce; sk_slice_range(sp, S, sl, &cb, &ce);
-        for (u32 o = 0; o < sp.G; ++o) send_words[(size_t)sl * sp.G + o] = (u64)(ce - cb) * sp.slice * sp.R;
-    }
-    for (u32 o = 0; o < sp.G; ++o) kmers_est[o] = ctx->h_sk_est[o];
-    *nslices = S; ctx->sk_nslices = S;
-    return DSKGPU_OK;
-}
-
-// launch the scatter of slice s (asynchronous on the context's stream: the caller records an event behind it and starts the exchange)
-int sk_scatter_slice(dskgpu_ctx* ctx, void* d_send, uint64_t capacity_words, u32 sl) {
-    if (!ctx->sk_prepared || !ctx->sk_slices || sl >= ctx->sk_nslices) return fail(ctx, DSKGPU_E_STATE, "dskgpu_mg_scatter_slice without dskgpu_mg_slices_prepare");
-    SkParams sp = ctx->sk_sp;
-    if (capacity_words < ctx->h_rstart[sp.G] * sp.R) return fail(ctx, DSKGPU_E_ARG, "send buffer too small");
-    if (sl == 0) {
-        ctx->marks.clear(); ctx->ev_used = 0;
-        ctx->mark("start");
-        CK(hipMemsetAsync(ctx->sk_sent.p, 0, SK_MAX_OWNERS * 8, ctx->stream));
-        CK(hipMemsetAsync(ctx->sk_sent.as<u64>() + 2 * SK_MAX_OWNERS, 0, 8, ctx->stream));
-    }
-    u32 cb, ce; sk_slice_range(sp, ctx->sk_nslices, sl, &cb, &ce);
-    sp.c0 = cb; sp.c0g = cb; sp.clen = ce - cb; sp.rbase = (u64)cb * sp.G * sp.slice;
-    // (the overflow flag of a sliced step lives apart from the scalars: the receiver's pipeline, which runs before the flag is
-    //  read, resets those)
-    if (ce > cb) {
-#define SK_CALL(K_, M_) hipLaunchKernelGGL((k_sk_scatter<true, K_, M_>), dim3(ce - cb), dim3(SK_NT), 0, ctx->stream, ctx->packed.as<u64>(), ctx->inval.as<u32>(), sp, \
-                                          (const unsigned long long*)nullptr, static_cast<u64*>(d_send), reinterpret_cast<u32*>(ctx->sk_sent.as<u64>() + 2 * SK_MAX_OWNERS), \
-                                          ctx->sk_sent.as<unsigned long long>())
-        SK_DISPATCH(ctx, sp, SK_CALL);
-#undef SK_CALL
-    }
-    CKL("k_sk_scatter");
-    if (sl + 1 == ctx->sk_nslices) ctx->mark("mg_scatter");
-    return DSKGPU_OK;
-}
-
-// end of the sender's part: did a slice of the send layout overflow (then the records of this step are incomplete -- every rank
-// repeats the step in one piece; this context will use exact counts), and the k-mers that were packed
-int sk_slices_finish(dskgpu_ctx* ctx, int* overflowed) {
-    if (!ctx->sk_nslices) return fail(ctx, DSKGPU_E_STATE, "dskgpu_mg_slices_finish without dskgpu_mg_slices_prepare");
-    CK(hipMemcpyAsync(&ctx->h_ovf1, ctx->sk_sent.as<u64>() + 2 * SK_MAX_OWNERS, 4, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipMemcpyAsync(ctx->h_sk_sent, ctx->sk_sent.p, SK_MAX_OWNERS * 8, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    *overflowed = ctx->h_ovf1 ? 1 : 0;
-    if (ctx->h_ovf1) ctx->sk_exact = true;
-    ctx->sk_prepared = false; ctx->sk_nslices = 0;
-    return DSKGPU_OK;
-}
-
 // Receiver: records -> dense mixed keys -> the ordinary partition + count over a key array.
 template <int W>
 int sk_count(dskgpu_ctx* ctx, const u64* d_rec, u64 recv_words, u64 n_kmers_hint, bool hint_is_estimate = false) {
     typedef typename KeyT<W>::T Key;
-    const u32 R = ctx->sk_sp.R;
+    const u32 R = ctx->sender.sp.R;
     if (recv_words % R) return fail(ctx, DSKGPU_E_ARG, "recv_words is not a whole number of super-k-mer records");
     const u64 nrec = recv_words / R;
     if (hint_is_estimate && ctx->marks.size() > 1) {      // a sliced step: the sender's marks are still open (its launches returned at once)
@@ -1919,12 +1600,6 @@ int sk_count(dskgpu_ctx* ctx, const u64* d_rec, u64 recv_words, u64 n_kmers_hint
     return rc;
 }
 
-
-
-}  // namespace
-
-namespace {
-
 // Multi-bank count: every bank is counted on its own (all distinct k-mers kept), the per-bank rows are
 // united and sorted by k-mer, and k_merge_banks applies the solidity kind / builds the histograms.  In steps, so that the
 // in-process group (group.hip) can put its own count -- scatter, exchange, mg_count -- between them:
@@ -1954,7 +1629,7 @@ void banks_select(dskgpu_ctx* ctx, u32 b) {
     if (!j.active) return;
     if (b >= j.ends.size()) { ctx->d_reads = j.base; ctx->n_bytes = j.total; }
     else { const u64 beg = b ? j.ends[b - 1] : 0; ctx->d_reads = j.base + beg; ctx->n_bytes = j.ends[b] - beg; }
-    ctx->enc_fresh = false; ctx->sk_prepared = false;
+    ctx->enc_fresh = false; ctx->sender.prepared = false;
 }
 void banks_abort(dskgpu_ctx* ctx) {      // (an error inside a per-bank count: the context gets its configuration and its read stream back)
     BankJob& j = ctx->bank_job;
@@ -2099,6 +1774,28 @@ static void launch_raw_chunk(dskgpu_ctx* ctx, u32 n, uint8_t* out) {
                        ctx->raw_bstate.as<u32>(), st, out);
 }
 
+// The raw pushes' result: the stream's length comes back from the device (the one synchronisation of a raw ingest), the terminator is set.
+int raw_finish(dskgpu_ctx* ctx, u64* lines) {
+    if (!ctx->raw_pending) return DSKGPU_OK;
+    RawState s;
+    CK(hipMemcpyAsync(&s, ctx->raw_state.p, sizeof(RawState), hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    ctx->raw_pending = false;
+    uint8_t* dst = ctx->reads_own.as<uint8_t>();
+    if (!rp_file_ok(s)) s.bad = 1;      // (the last file, now that it is complete: its quality lines must add up to its sequence lines)
+    if (s.bad) {             // the text is not what the device parser handles: the raw pushes are dropped, the stream is what it was before them
+        ctx->reads_len = ctx->raw_base;
+        ctx->d_reads = dst; ctx->n_bytes = ctx->reads_len;
+        return fail(ctx, DSKGPU_E_FORMAT, "dskgpu_push_raw: the text is not 4-line FASTQ / FASTA as declared (the raw pushes were dropped: parse on the host and push the reads)");
+    }
+    if (s.out_len + 1 > ctx->reads_own.cap) return fail(ctx, DSKGPU_E_STATE, "dskgpu_push_raw: stream longer than its bound");
+    CK(hipMemsetAsync(dst + s.out_len, '\n', 1, ctx->stream));
+    ctx->reads_len = s.out_len + 1;
+    if (lines) *lines = s.recs;
+    ctx->d_reads = dst; ctx->n_bytes = ctx->reads_len; ctx->enc_keep = false; ctx->reads_changed();
+    return DSKGPU_OK;
+}
+
 extern "C" {
 
 const char* dskgpu_version(void) { return DSKGPU_VERSION; }
@@ -2137,9 +1834,11 @@ int dskgpu_create(const dskgpu_config* cfg, dskgpu_ctx** out) {
     // (world_size == 1 is the degenerate exchange: every record goes to owner 0; dskgpu_count never looks at sk_mode)
     ctx->sk_mode = cfg->kmer_size >= 20 && cfg->kmer_size <= 64 && !(cfg->flags & DSKGPU_F_MG_EXPLICIT);
     if (ctx->sk_mode) {
-        ctx->sk_sp.k = cfg->kmer_size; ctx->sk_sp.G = ws;
-        ctx->sk_sp.m = std::min<u32>(std::min<u32>(ctx->cfg.minimizer_size, 16u), cfg->kmer_size - 15u);
-        ctx->sk_sp.R = sk_record_words(cfg->kmer_size);
+        SkParams& sp = ctx->sender.sp;
+        sp.k = cfg->kmer_size; sp.G = ws;
+        sp.m = std::min<u32>(std::min<u32>(ctx->cfg.minimizer_size, 16u), cfg->kmer_size - 15u);
+        sp.R = sk_record_words(cfg->kmer_size);
+        ctx->l0_sender.sp = sp;      // (the same k, m and R; its G is the passes of the count that uses it)
     }
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && cus > 0) ctx->num_cu = cus; }      // (one attribute, not the whole property block)
     e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
@@ -2158,9 +1857,10 @@ void dskgpu_destroy(dskgpu_ctx* ctx) {
                       &ctx->out_ab, &ctx->srt_ab, &ctx->srt_tmp,
                       &ctx->srt_idx, &ctx->srt_idx2, &ctx->srt_k, &ctx->srt_k2, &ctx->abund2, &ctx->acc_ab, &ctx->u_val,
                       &ctx->s_val, &ctx->m_flag, &ctx->m_pos, &ctx->m_sum, &ctx->gh2d,
-                      &ctx->sk_sums, &ctx->sk_cbase, &ctx->sk_keys, &ctx->sk_table, &ctx->sk_load, &ctx->sk_sent, &ctx->cur_state, &ctx->smp_keys, &ctx->sk_lay, &ctx->sk_cb64, &ctx->back_dev};
+                      &ctx->sk_sums, &ctx->sk_cbase, &ctx->sk_keys, &ctx->cur_state, &ctx->smp_keys, &ctx->back_dev};
     if (ctx->back_host) (void)hipHostFree(ctx->back_host);
     ctx->rs.release();
+    ctx->sender.release(); ctx->l0_sender.release();
     ctx->query.release();
     ctx->unitigs.release();
     if (ctx->land) (void)hipHostFree(ctx->land);
@@ -2212,7 +1912,6 @@ static int ensure_pinned(dskgpu_ctx* ctx) {      // the two pinned staging buffe
     return DSKGPU_OK;
 }
 
-static int raw_finish(dskgpu_ctx* ctx, u64* lines);
 int dskgpu_push_reads(dskgpu_ctx* ctx, const char* bytes, uint64_t nbytes) {
     if (!ctx || (!bytes && nbytes)) return DSKGPU_E_ARG;
     CK(hipSetDevice(ctx->cfg.device));
@@ -2247,32 +1946,9 @@ int dskgpu_push_reads(dskgpu_ctx* ctx, const char* bytes, uint64_t nbytes) {
     //  device copy -- the count, a later growth of the buffer -- is ordered behind the DMA on the context's stream.  A bank that
     //  hands over a few MB per call keeps the link busy this way instead of paying a round trip per call.)
     ctx->reads_len += nbytes + 1;
-    ctx->d_reads = dst; ctx->n_bytes = ctx->reads_len; ctx->enc_keep = false; ctx->enc_fresh = false; ctx->sk_prepared = false; ctx->sk_exact = false; ctx->opt2_off = false; ctx->opt1_off = false; ctx->mw_v3_off = false; ctx->rec_l0_off = false; ctx->last_rows = 0;
+    ctx->d_reads = dst; ctx->n_bytes = ctx->reads_len; ctx->enc_keep = false; ctx->reads_changed();
     return DSKGPU_OK;
 }
-
-// The raw pushes' result: the stream's length comes back from the device (the one synchronisation of a raw ingest), the terminator is set.
-static int raw_finish(dskgpu_ctx* ctx, u64* lines) {
-    if (!ctx->raw_pending) return DSKGPU_OK;
-    RawState s;
-    CK(hipMemcpyAsync(&s, ctx->raw_state.p, sizeof(RawState), hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    ctx->raw_pending = false;
-    uint8_t* dst = ctx->reads_own.as<uint8_t>();
-    if (!rp_file_ok(s)) s.bad = 1;      // (the last file, now that it is complete: its quality lines must add up to its sequence lines)
-    if (s.bad) {             // the text is not what the device parser handles: the raw pushes are dropped, the stream is what it was before them
-        ctx->reads_len = ctx->raw_base;
-        ctx->d_reads = dst; ctx->n_bytes = ctx->reads_len;
-        return fail(ctx, DSKGPU_E_FORMAT, "dskgpu_push_raw: the text is not 4-line FASTQ / FASTA as declared (the raw pushes were dropped: parse on the host and push the reads)");
-    }
-    if (s.out_len + 1 > ctx->reads_own.cap) return fail(ctx, DSKGPU_E_STATE, "dskgpu_push_raw: stream longer than its bound");
-    CK(hipMemsetAsync(dst + s.out_len, '\n', 1, ctx->stream));
-    ctx->reads_len = s.out_len + 1;
-    if (lines) *lines = s.recs;
-    ctx->d_reads = dst; ctx->n_bytes = ctx->reads_len; ctx->enc_keep = false; ctx->enc_fresh = false; ctx->sk_prepared = false; ctx->sk_exact = false; ctx->opt2_off = false; ctx->opt1_off = false; ctx->mw_v3_off = false; ctx->rec_l0_off = false; ctx->last_rows = 0;
-    return DSKGPU_OK;
-}
-#define RAW_SYNC(ctx) do { if ((ctx)->raw_pending) { const int e_ = raw_finish(ctx, nullptr); if (e_) return e_; } } while (0)
 
 int dskgpu_raw_finish(dskgpu_ctx* ctx, uint64_t* stream_bytes, uint64_t* records) {
     if (!ctx) return DSKGPU_E_ARG;
@@ -2349,7 +2025,7 @@ int dskgpu_rewind_reads(dskgpu_ctx* ctx, uint64_t stream_bytes) {
     if (stream_bytes > ctx->reads_len) return fail(ctx, DSKGPU_E_ARG, "dskgpu_rewind_reads: the stream is shorter than that");
     ctx->reads_len = stream_bytes;
     while (!ctx->bank_ends.empty() && ctx->bank_ends.back() > stream_bytes) ctx->bank_ends.pop_back();
-    ctx->d_reads = ctx->reads_own.as<uint8_t>(); ctx->n_bytes = ctx->reads_len; ctx->enc_fresh = false; ctx->sk_prepared = false; ctx->sk_exact = false; ctx->opt2_off = false; ctx->opt1_off = false; ctx->mw_v3_off = false; ctx->rec_l0_off = false; ctx->last_rows = 0;
+    ctx->d_reads = ctx->reads_own.as<uint8_t>(); ctx->n_bytes = ctx->reads_len; ctx->reads_changed();
     return DSKGPU_OK;
 }
 
@@ -2409,7 +2085,7 @@ int dskgpu_set_reads_device(dskgpu_ctx* ctx, const void* d_bytes, uint64_t nbyte
     CK(hipSetDevice(ctx->cfg.device));
     CK(hipDeviceSynchronize());
     ctx->raw_pending = false;
-    ctx->d_reads = static_cast<const uint8_t*>(d_bytes); ctx->enc_keep = false; ctx->enc_fresh = false; ctx->sk_prepared = false; ctx->sk_exact = false; ctx->opt2_off = false; ctx->opt1_off = false; ctx->mw_v3_off = false; ctx->rec_l0_off = false; ctx->last_rows = 0;
+    ctx->d_reads = static_cast<const uint8_t*>(d_bytes); ctx->enc_keep = false; ctx->reads_changed();
     ctx->n_bytes = nbytes;
     ctx->reads_len = 0;
     ctx->bank_ends.clear();
@@ -2478,8 +2154,7 @@ uint64_t dskgpu_mg_send_capacity_words(dskgpu_ctx* ctx) {
     if (ctx->raw_pending && (hipSetDevice(ctx->cfg.device) != hipSuccess || raw_finish(ctx, nullptr) != DSKGPU_OK)) return 0;
     if (!ctx->sk_mode) return (ctx->n_bytes + 1) * (u64)ctx->W;
     if (hipSetDevice(ctx->cfg.device) != hipSuccess) return 0;
-    if (!ctx->sk_prepared && sk_prepare(ctx) != DSKGPU_OK) return 0;     // the error text stays in the ctx; dskgpu_mg_scatter reports it
-    return ctx->h_rstart[ctx->sk_sp.G] * ctx->sk_sp.R + 1;
+    return sk_send_capacity_words(ctx);
 }
 
 int dskgpu_mg_scatter(dskgpu_ctx* ctx, void* d_send, uint64_t capacity_words, uint64_t* send_words) {
@@ -2491,112 +2166,19 @@ int dskgpu_mg_scatter(dskgpu_ctx* ctx, void* d_send, uint64_t capacity_words, ui
     if (ctx->n_bytes >= 0xFFFF0000ull) return fail(ctx, DSKGPU_E_ARG, "explicit-key exchange: a rank's read shard must stay below 4.29 GB (super-k-mer records, 20 <= k <= 64, have no such limit)");
     if (capacity_words < dskgpu_mg_send_capacity_words(ctx)) return fail(ctx, DSKGPU_E_ARG, "send buffer too small");
     const int rc = ctx->W == 1 ? mg_scatter_impl<1>(ctx, d_send, send_words) : ctx->W == 2 ? mg_scatter_impl<2>(ctx, d_send, send_words) : mg_scatter_impl<4>(ctx, d_send, send_words);
-    if (rc == DSKGPU_OK) for (u32 o = 0; o < ctx->cfg.world_size; ++o) ctx->h_sk_sent[o] = send_words[o] / (u64)ctx->W;
+    if (rc == DSKGPU_OK) for (u32 o = 0; o < ctx->cfg.world_size; ++o) ctx->sender.h_sent[o] = send_words[o] / (u64)ctx->W;
     return rc;
-}
-
-int dskgpu_mg_sample(dskgpu_ctx* ctx, uint64_t* loads) {
-    if (!ctx || !loads) return DSKGPU_E_ARG;
-    std::memset(loads, 0, (size_t)SK_BUCKETS * 8);
-    if (!ctx->sk_mode) return DSKGPU_OK;            // explicit keys: the owner is a bit field of the k-mer hash, balanced by construction
-    CK(hipSetDevice(ctx->cfg.device));
-    RAW_SYNC(ctx);
-    u64 nwords = 0;
-    int rc = encode_current(ctx, &nwords);
-    if (rc) return rc;
-    sk_geometry(ctx, nwords);
-    SkParams sp = ctx->sk_sp;
-    sp.sample_step = sp.tiles_per_chunk >= 16 ? 16u : 1u;        // every 16th tile of a large shard, all tiles of a small one
-    sp.table = nullptr;
-    CK(ctx->sk_load.ensure((size_t)SK_BUCKETS * 8));
-    CK(hipMemsetAsync(ctx->sk_load.p, 0, (size_t)SK_BUCKETS * 8, ctx->stream));
-#define SK_CALL(K_, M_) hipLaunchKernelGGL((k_sk_sample<K_, M_>), dim3(sp.nchunks), dim3(SK_NT), 0, ctx->stream, ctx->packed.as<u64>(), ctx->inval.as<u32>(), sp, \
-                                          ctx->sk_load.as<unsigned long long>())
-    SK_DISPATCH(ctx, sp, SK_CALL);
-#undef SK_CALL
-    CKL("k_sk_sample");
-    CK(hipMemcpyAsync(loads, ctx->sk_load.p, (size_t)SK_BUCKETS * 8, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    for (u32 b = 0; b < SK_BUCKETS; ++b) loads[b] *= sp.sample_step;      // an estimate of the whole shard's load
-    ctx->sk_prepared = false;                       // packed / inval were rewritten
-    ctx->enc_fresh = true;                          // ... with the encoding of the current reads: the sender's sizing pass reuses it
-    return DSKGPU_OK;
-}
-
-void dskgpu_mg_make_table(const uint64_t* loads, uint32_t world, uint8_t* table) {
-    if (!table) return;
-    if (world == 0) world = 1;
-    default_table(world, table);
-    if (!loads || world == 1) return;
-    u64 total = 0;
-    for (u32 b = 0; b < SK_BUCKETS; ++b) total += loads[b];
-    if (total == 0) return;
-    // a bucket that alone holds more than a quarter of an owner's fair share is split over all owners by k-mer
-    const u64 heavy = std::max<u64>(1, total / world / 4);
-    std::vector<u64> owner_load(world, 0);
-    std::vector<u32> order;
-    u64 split_load = 0;
-    for (u32 b = 0; b < SK_BUCKETS; ++b) {
-        if (loads[b] > heavy) { table[b] = (uint8_t)SK_SPLIT; split_load += loads[b]; }
-        else if (loads[b]) order.push_back(b);        // (buckets the sample did not see keep their default owner)
-    }
-    for (u32 o = 0; o < world; ++o) owner_load[o] = split_load / world;
-    std::stable_sort(order.begin(), order.end(), [&](u32 a, u32 b) { return loads[a] > loads[b]; });    // largest first, ties by index
-    for (u32 b : order) {
-        u32 best = 0;
-        for (u32 o = 1; o < world; ++o) if (owner_load[o] < owner_load[best]) best = o;
-        table[b] = (uint8_t)best;
-        owner_load[best] += loads[b];
-    }
-}
-
-int dskgpu_mg_set_table(dskgpu_ctx* ctx, const uint8_t* table) {
-    if (!ctx) return DSKGPU_E_ARG;
-    if (table)          // validate before the table in use is touched: a rejected table leaves the context as it was
-        for (u32 b = 0; b < SK_BUCKETS; ++b)
-            if (table[b] != SK_SPLIT && table[b] >= ctx->cfg.world_size) return fail(ctx, DSKGPU_E_ARG, "repartition table names an owner outside the world");
-    ctx->h_table.resize(SK_BUCKETS);
-    if (table) {
-        std::memcpy(ctx->h_table.data(), table, SK_BUCKETS);
-    } else default_table(ctx->cfg.world_size, ctx->h_table.data());
-    ctx->table_dirty = true;
-    ctx->sk_prepared = false;
-    return DSKGPU_OK;
-}
-
-int dskgpu_mg_sent_kmers(dskgpu_ctx* ctx, uint64_t* kmers) {
-    if (!ctx || !kmers) return DSKGPU_E_ARG;
-    for (u32 o = 0; o < ctx->cfg.world_size; ++o) kmers[o] = ctx->h_sk_sent[o];
-    return DSKGPU_OK;
 }
 
 int dskgpu_mg_count(dskgpu_ctx* ctx, const void* d_recv, uint64_t recv_words) { return dskgpu_mg_count_sized(ctx, d_recv, recv_words, 0); }
 
-int dskgpu_mg_slices_prepare(dskgpu_ctx* ctx, uint32_t want_slices, uint32_t* nslices, uint64_t* send_words, uint64_t* kmers_est) {
-    if (!ctx || !nslices || !send_words || !kmers_est) return DSKGPU_E_ARG;
-    *nslices = 0;
-    if (!ctx->sk_mode) return DSKGPU_OK;                 // explicit keys: one piece
-    CK(hipSetDevice(ctx->cfg.device));
-    RAW_SYNC(ctx);
-    return sk_slices_prepare(ctx, want_slices, nslices, send_words, kmers_est);
-}
-int dskgpu_mg_scatter_slice(dskgpu_ctx* ctx, void* d_send, uint64_t capacity_words, uint32_t slice) {
-    if (!ctx || !d_send) return DSKGPU_E_ARG;
-    CK(hipSetDevice(ctx->cfg.device));
-    return sk_scatter_slice(ctx, d_send, capacity_words, slice);
-}
-int dskgpu_mg_slices_finish(dskgpu_ctx* ctx, int* overflowed) {
-    if (!ctx || !overflowed) return DSKGPU_E_ARG;
-    CK(hipSetDevice(ctx->cfg.device));
-    return sk_slices_finish(ctx, overflowed);
-}
 int dskgpu_mg_count_sliced(dskgpu_ctx* ctx, const void* d_recv, uint32_t nslices, const uint64_t* slice_words, uint64_t n_kmers_est,
                            dskgpu_slice_gate gate, void* user) {
     if (!ctx || !nslices || !slice_words || !gate) return DSKGPU_E_ARG;
     if (!ctx->sk_mode) return fail(ctx, DSKGPU_E_STATE, "dskgpu_mg_count_sliced needs super-k-mer records (20 <= k <= 64, no DSKGPU_F_MG_EXPLICIT)");
     CK(hipSetDevice(ctx->cfg.device));
     ctx->stats = dskgpu_stats{};
-    const u32 R = ctx->sk_sp.R;
+    const u32 R = ctx->sender.sp.R;
     u64 words = 0;
     ctx->rec_slice_end.clear();
     for (u32 sl = 0; sl < nslices; ++sl) {

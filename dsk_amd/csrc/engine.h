@@ -1,5 +1,7 @@
 // engine.h -- what the host translation units of libdskgpu share: the context (dskgpu_ctx) with its buffers and switches,
 // the error macros, and the functions one of them calls in the other.  dskgpu.hip runs the count path and the C-ABI;
+// sender.hip turns the 2-bit read stream into super-k-mer records -- for the multi-GPU exchange (dskgpu_mg_sample .. _mg_slices_finish) and for
+// the record-based level 0 of a multi-pass count (rec_l0_*) -- and owns the two Sender states (dskgpu_ctx::sender, ::l0_sender);
 // rowsort.hip orders the solid rows (order_rows) and owns the row sort's state (dskgpu_ctx::rs); query.hip answers lookups in the
 // last result (dskgpu_query_*) and owns dskgpu_ctx::query; graph.hip answers the de Bruijn neighbourhood of k-mers from the same index
 // (dskgpu_graph_*); unitigs.hip compacts the rows' graph into unitigs and links them (dskgpu_unitigs*, dskgpu_unitig_edges*) and owns dskgpu_ctx::unitigs.  Private to the library.
@@ -160,6 +162,30 @@ struct Unitigs {
     void release() { for (DevBuf* b : {&unitig, &pos, &offsets, &ab_sum, &kind}) b->release(); stats = dskgpu_unitig_stats{}; valid = false; release_edges(); }
 };
 
+// The super-k-mer sender's state (sender.hip): what k_sk_sample / k_sk_hist / k_sk_scatter are launched with and what they leave behind.
+// A context has two: `sender`, the multi-GPU exchange's (G = world size; configured by dskgpu_create and dskgpu_mg_set_table), and
+// `l0_sender`, the record-based level 0's of a multi-pass count (G = passes, a table and per-owner layout of its own: rec_l0_*) -- so a
+// count never touches the owners or the table the caller's exchange works with.  k, m and R are the same in both (dskgpu_create).
+struct Sender {
+    SkParams sp{};
+    std::vector<uint8_t> h_table;  // the repartition table in use (SK_BUCKETS owners; default: bucket scaled to G)
+    bool table_dirty = true;       // h_table not yet copied to `table`
+    DevBuf table, load;            // the table on the device; the sampled k-mer load of every minimizer bucket (k_sk_sample)
+    DevBuf sent;                   // [k-mers sent per owner | sampled k-mers per owner | overflow flag of a sliced step]
+    DevBuf lay;                    // level 0: [region base per owner: u64 x 64][slice per owner: u32 x 64] of a sweep
+    DevBuf cb64;                   // exact layout: h_cb64 on the device (k_sk_scatter<false>)
+    bool prepared = false;         // the send layout below is that of the current reads and ctx->packed / mat1 still hold what it was made from
+    bool slices = false;           // the prepared send layout is slices from a sampled estimate (else exact offsets)
+    bool exact = false;            // a slice overflowed on these reads: exact counts from now on
+    u32 nslices = 0;               // dskgpu_mg_slices_prepare: slices of the prepared step (0 = none prepared)
+    std::vector<u64> h_rstart;     // first RECORD of every owner in the send buffer (64-bit: no limit on a rank's shard)
+    std::vector<u32> h_cells;      // records per (owner, chunk) as the sizing pass counted them
+    std::vector<u64> h_cb64;       // exact layout: their exclusive scan (owner-major) = record index of every (owner, chunk) pair
+    u64 h_sent[SK_MAX_OWNERS] = {0};      // k-mers inside the records the last scatter / sweep wrote for every owner
+    u64 h_est[SK_MAX_OWNERS] = {0};       // sampled layout: estimated k-mers per owner (k_sk_hist on every 16th tile, scaled)
+    void release() { for (DevBuf* b : {&table, &load, &sent, &lay, &cb64}) b->release(); table_dirty = true; prepared = false; nslices = 0; }
+};
+
 // state of a per-bank count in steps (banks_begin .. banks_finish below)
 struct BankJob { dskgpu_config cfg; const uint8_t* base; u64 total; std::vector<u64> ends; u64 nu, tot_kmers; u32 passes, retries; bool active = false; };
 
@@ -199,23 +225,19 @@ struct dskgpu_ctx {
     DevBuf u_w[4], s_w[4], u_val, s_val, m_flag, m_pos, m_sum, gh2d;
     std::vector<u64> hist2d;
     std::vector<u32> h_starts;     // explicit-key exchange: first key of every owner in the send buffer
-    std::vector<u64> h_rstart;     // record exchange: first RECORD of every owner in the send buffer (64-bit: no limit on a rank's shard)
-    std::vector<u32> h_sk_cells;   // ... records per (owner, chunk) as the sizing pass counted them
-    std::vector<u64> h_sk_cb64;    // ... exact layout: their exclusive scan (owner-major) = record index of every (owner, chunk) pair
-    DevBuf sk_cb64;                // ... the same on the device (k_sk_scatter<false>)
-    // multi-GPU exchange as super-k-mer records (superkmer.h)
+    // the 2-bit form of the reads (packed / inval) between calls.  Both flags describe ctx->packed, which the count path writes and checks
+    // (run_encode, encode_current) as much as the sender does: they stay here, not in Sender
     bool enc_keep = false;         // dskgpu_encode_reads: packed / inval hold the 2-bit form of the current reads and the ASCII bytes are gone (d_reads == nullptr)
     bool enc_fresh = false;        // packed / inval hold the encoding of the current reads, left by dskgpu_mg_sample for the sender's sizing pass of the same step
-    bool sk_mode = false, sk_prepared = false;
-    bool sk_slices = false;        // the prepared send layout is slices from a sampled estimate (else exact offsets)
-    bool sk_exact = false;         // a slice overflowed on these reads: exact counts from now on
-    SkParams sk_sp{};
-    DevBuf sk_sums, sk_cbase, sk_keys, sk_table, sk_load, sk_sent, sk_lay;      // sk_lay: [region base per owner: u64 x 64][slice per owner: u32 x 64] of a record-based level-0 sweep
-    u64 last_rows = 0;             // solid rows of the last count of the current reads (0 = not counted yet): sizes what a multi-pass count keeps free for its rows
-    bool rec_l0_off = false;       // these reads do not take the record-based level 0 (a slice of its sampled layout overflowed)
-    u64 h_sk_sent[SK_MAX_OWNERS] = {0};      // k-mers inside the records the last mg_scatter wrote for every owner
-    u64 h_sk_est[SK_MAX_OWNERS] = {0};       // sampled layout: estimated k-mers per owner (k_sk_hist on every 16th tile, scaled)
-    u32 sk_nslices = 0;                      // dskgpu_mg_slices_prepare: slices of the prepared step (0 = none prepared)
+    // super-k-mer records (superkmer.h): who writes them ...
+    bool sk_mode = false;          // 20 <= k <= 64 and no DSKGPU_F_MG_EXPLICIT: the exchange and a multi-pass level 0 use records (sender.sp.R words each)
+    Sender sender, l0_sender;
+    // ... and who reads them: the receiver (sk_sizes, expand_records, sk_count, the level-1 scatter with SRC 2)
+    DevBuf sk_sums, sk_cbase, sk_keys;
+    std::vector<u32> h_sk_sums; std::vector<u64> h_sk_cbase;
+    // records handed to dskgpu_mg_count: the level-1 scatter reads them directly (SRC 2); expanded lazily for the exact path
+    const u64* rec_src = nullptr; u64 rec_n = 0; u64 rec_nch = 0, rec_rpc = 0; bool rec_expanded = false;
+    bool rec_sized = false;                  // per-chunk k-mer sums of the records are on the device (k_sk_count ran)
     u64 rec_hint = 0;                        // dskgpu_mg_count_sized: the caller's k-mer total of the records (0 = none)
     bool rec_hint_est = false;               // ... an estimate (sliced step): sizes the fast path only, never checked against the result
     std::vector<u64> rec_slice_end;          // dskgpu_mg_count_sliced: record index where every slice ends; empty = one piece
@@ -223,12 +245,9 @@ struct dskgpu_ctx {
     bool rec_gate_failed = false;            // a gate said its slice will never arrive: the count stops (DSKGPU_E_STATE)
     std::vector<u32> h_slice_chunk;          // first level-1 chunk of every slice (+ the end)
     DevBuf cur_state;                        // parked write cursors of the level-1 blocks between the launches of a sliced receive
-    bool rec_sized = false;                  // per-chunk k-mer sums of the records are on the device (k_sk_count ran)
-    std::vector<uint8_t> h_table;  // the repartition table in use (SK_BUCKETS owners; default: bucket scaled to the world size)
-    bool table_dirty = true;       // h_table not yet copied to sk_table
-    std::vector<u32> h_sk_sums; std::vector<u64> h_sk_cbase;
-    // records handed to dskgpu_mg_count: the level-1 scatter reads them directly (SRC 2); expanded lazily for the exact path
-    const u64* rec_src = nullptr; u64 rec_n = 0; u64 rec_nch = 0, rec_rpc = 0; bool rec_expanded = false;
+    // what the counts of the current reads found out about them
+    u64 last_rows = 0;             // solid rows of the last count of the current reads (0 = not counted yet): sizes what a multi-pass count keeps free for its rows
+    bool rec_l0_off = false;       // these reads do not take the record-based level 0 (a slice of its sampled layout overflowed)
     u64* land = nullptr;                             // 64 KB of pinned host memory: where the small per-step read-backs land (landing())
     DevBuf back_dev; u64* back_host = nullptr;      // the count stage's read-back record (k_gather_back) and its pinned landing zone
     u32 h_back[3] = {0}; u64 h_stats[4] = {0}; u32 h_ovf1 = 0; u64 h_nvalid = 0; bool have_nvalid = false;      // read-back landings; the valid k-mer windows of the reads
@@ -258,6 +277,8 @@ struct dskgpu_ctx {
     // a count starts, or its result is not to be read: the index of the old rows and their unitigs go with them, and so does their memory
     // -- up to 32 + 8 bytes per row that the count about to run may need (a no-op for a context that was never queried)
     void drop_result() { have_result = false; query.release(); unitigs.release(); }
+    // the read stream changed: what was learnt about the old reads -- their kept encoding apart (enc_keep: the caller's to clear) -- goes
+    void reads_changed() { enc_fresh = false; sender.prepared = false; sender.exact = false; opt2_off = false; opt1_off = false; mw_v3_off = false; rec_l0_off = false; last_rows = 0; }
 
     // timing
     std::vector<Stage> marks;
@@ -304,9 +325,20 @@ struct dskgpu_ctx {
 inline int fail(dskgpu_ctx* ctx, int code, const std::string& msg) { ctx->err = msg; return code; }
 
 // dskgpu.hip
+int encode_current(dskgpu_ctx* ctx, u64* nwords_out);    // the 2-bit form of the current reads in ctx->packed / inval: encoded now, or kept (dskgpu_encode_reads)
+int raw_finish(dskgpu_ctx* ctx, u64* lines);             // the raw pushes' result: the stream's length comes back from the device
+#define RAW_SYNC(ctx) do { if ((ctx)->raw_pending) { const int e_ = raw_finish(ctx, nullptr); if (e_) return e_; } } while (0)
 int encode_into(dskgpu_ctx* ctx, const uint8_t* d_bytes, u64 n, u64* packed, u32* inval);      // k_encode of n bytes into (n + 31) / 32 words of the caller's buffers
 int run_scan(dskgpu_ctx* ctx, u32* a, const u32* d_len, u64 max_len);
 int allow_big_lds(dskgpu_ctx* ctx, const void* fn, int bytes = 160 * 1024);      // (bytes: kernels with static LDS next to the dynamic block ask for what they use)
+
+// sender.hip
+#define REC_L0_NO 2001             // rec_l0_prepare / _sweep: this input does not take the record path (not an error)
+struct RecL0 { u32 G = 0; u64 nch = 0; u32 slice[SK_MAX_OWNERS] = {0}; u64 region[SK_MAX_OWNERS] = {0}; };      // region[o]: records of owner o's region (nch * slice[o])
+int rec_l0_prepare(dskgpu_ctx* ctx, Sender& s, u64 nwords, u32 G, RecL0* rl);      // table for G owners + the slice of every owner, both from samples
+int rec_l0_sweep(dskgpu_ctx* ctx, Sender& s, const RecL0& rl, u32 olo, u32 ohi, u64 (&base_words)[SK_MAX_OWNERS]);      // the records of owners [olo, ohi) into ctx->l0buf
+uint64_t sk_send_capacity_words(dskgpu_ctx* ctx);        // the exchange: words the send buffer must hold for the current reads (sizes the send layout if need be)
+int sk_scatter(dskgpu_ctx* ctx, void* d_send, uint64_t capacity_words, uint64_t* send_words);      // ... and the records into it, grouped by owner
 
 // rowsort.hip
 int order_rows(dskgpu_ctx* ctx, u64 n, u32 npass);

@@ -1,7 +1,7 @@
 // layouts.h -- what the kernel headers (kernels.h, superkmer.h, rowsort.h, rowsort2.h, partsort.h) and the host (engine.h)
 // share: the chunk descriptors of the key scatters, the super-k-mer sender's parameters, the layouts of the solid rows, the
 // LDS-only barrier and tile scan of the LDS-staged scatters, and the index gather that the row sort and the bank merge both
-// launch.  No other kernel here: each host translation unit defines its own (dskgpu.hip the count path, rowsort.hip the row
+// launch.  No other kernel here: each host translation unit defines its own (dskgpu.hip the count path, sender.hip the record sender, rowsort.hip the row
 // sort), and a non-template kernel that both included would be defined twice.
 #pragma once
 #include "kmer_device.h"
@@ -84,7 +84,7 @@ struct SkParams {
     u64 rbase;                    // (64-bit: a rank's shard of a 90 Gbp job holds more than 2^32 records' worth of slices)
     const unsigned char* table;   // SK_BUCKETS owners (device memory)
     u32 has_split;                // the table holds SK_SPLIT entries (set with the table: the kernels skip the split bookkeeping otherwise)
-    // k_sk_scatter<true> for the passes of a multi-pass count on ONE GPU ("virtual owners": owner = pass; dskgpu.hip: rec_l0_*): only
+    // k_sk_scatter<true> for the passes of a multi-pass count on ONE GPU ("virtual owners": owner = pass; sender.hip: rec_l0_*): only
     // the records of owners [olo, ohi) are written (a sweep materialises as many passes as HBM holds), every owner has its own slice
     // length oslice[o] (a pass that holds a k-mer with 10^8 occurrences gets longer slices, the others do not pay for it) and its
     // region starts at record obase[o] of the buffer (64-bit: a sweep holds more than 2^32 records).  oslice == nullptr: the

@@ -7,7 +7,9 @@
 // owner and travel as one record of packed bases instead of one 8/16-byte key per k-mer.
 //
 //   sender   : k_sk_hist -> scan -> k_sk_scatter      (reads only the 2-bit stream; never forms k-mers)
-//   receiver : k_sk_count -> prefix -> k_sk_expand    (records -> dense array of mixed keys)
+//   receiver : k_sk_count -> prefix -> k_sk_expand    (records -> dense array of mixed keys; superkmer_recv.h)
+// This header holds the record format -- with the k-mer of a record as a mixed key (sk_key1 / sk_key2), which both sides and the level-1
+// scatter of kernels.h use -- and the sender; it needs nothing of kernels.h, and sender.hip includes nothing else.
 //
 // Minimizer order: the m-mers of a window are compared by a 32-bit hash of their canonical value
 // (a random order balances the owners better than the lexicographic one, which favours poly-A).
@@ -61,8 +63,31 @@ __device__ __forceinline__ u32 sk_owner(const SkThread& s, int i) {
     return (u32)((i < 8 ? s.ow_lo >> (8 * i) : s.ow_hi >> (8 * (i - 8))) & 0xFFu);
 }
 
-__device__ __forceinline__ u64 sk_key1(const u64* r, int j, int k);
-__device__ __forceinline__ K2 sk_key2(const u64* r, int j, int k);
+// k-mer `j` of a staged record -> mixed key (same key as tile_keys_reads would give for that window)
+__device__ __forceinline__ u64 sk_key1(const u64* r, int j, int k) {
+    const u64 x = j ? (r[0] << (2 * j)) | (r[1] >> (64 - 2 * j)) : r[0];
+    const u64 kmask = (k == 32) ? ~0ull : ((1ull << (2 * k)) - 1);
+    const u64 fwd = x >> (64 - 2 * k);
+    const u64 rc = (rev_pairs(fwd) >> (64 - 2 * k)) ^ (0xAAAAAAAAAAAAAAAAull & kmask);
+    return kmix(fwd < rc ? fwd : rc);
+}
+__device__ __forceinline__ K2 sk_key2(const u64* r, int j, int k) {
+    const u64 y0 = j ? (r[0] << (2 * j)) | (r[1] >> (64 - 2 * j)) : r[0];
+    const u64 y1 = j ? (r[1] << (2 * j)) | (r[2] >> (64 - 2 * j)) : r[1];
+    const int sh = 128 - 2 * k;                                // 0..62
+    const int kh = 2 * k - 64;
+    const u64 hmask = (kh == 64) ? ~0ull : ((1ull << kh) - 1);
+    const u64 flo = sh ? (y1 >> sh) | (y0 << (64 - sh)) : y1;
+    const u64 fhi = sh ? (y0 >> sh) : y0;
+    u64 rhi = rev_pairs(flo), rlo = rev_pairs(fhi);
+    if (sh) { rlo = (rlo >> sh) | (rhi << (64 - sh)); rhi >>= sh; }
+    rlo ^= 0xAAAAAAAAAAAAAAAAull;
+    rhi ^= (0xAAAAAAAAAAAAAAAAull & hmask);
+    const bool fl = fhi < rhi || (fhi == rhi && flo < rlo);
+    K2 o; o.w[1] = fl ? fhi : rhi; o.w[0] = fl ? flo : rlo;
+    kmixN(o);
+    return o;
+}
 // bases [bs, bs + nb) of the 96-base frame (w2 : w1 : w0), shifted to the top of o[0..2], the rest cleared
 __device__ __forceinline__ void sk_extract(u64 w2, u64 w1, u64 w0, int bs, int nb, u64 (&o)[3]) {
     const int sh = 2 * bs, ws = sh >> 6, b = sh & 63;
@@ -541,120 +566,6 @@ __global__ __launch_bounds__(SK_NT) void k_sk_scatter(const u64* __restrict__ pa
         for (u32 o = 0; o < sp.G; ++o) {                      // zero-length records up to the end of each of this block's slices
             const u64 beg = obw[o] + (u64)(cur[o] < lim[o] ? cur[o] : lim[o]) * R, end = obw[o] + (u64)lim[o] * R;
             for (u64 w = beg + threadIdx.x; w < end; w += SK_NT) send[w] = 0ull;
-        }
-    }
-}
-
-// ---------------------------------------------------------------- receiver: k-mers per chunk of records
-#define SKX_NT 256
-__global__ __launch_bounds__(SKX_NT) void k_sk_count(const u64* __restrict__ rec, u64 nrec, u32 R, u32 rpc, u32* __restrict__ sums) {
-    __shared__ u32 ws[SKX_NT / 64];
-    const u64 rbeg = (u64)blockIdx.x * rpc;
-    const u64 rend = rbeg + rpc < nrec ? rbeg + rpc : nrec;
-    u32 s = 0;
-    for (u64 r = rbeg + threadIdx.x; r < rend; r += SKX_NT) s += (u32)(rec[r * R + R - 1] & 0xFFu);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += __shfl_down(s, d);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) { u32 t = 0; for (int i = 0; i < SKX_NT / 64; ++i) t += ws[i]; sums[blockIdx.x] = t; }
-}
-
-// k-mer `j` of a staged record -> mixed key (same key as tile_keys_reads would give for that window)
-__device__ __forceinline__ u64 sk_key1(const u64* r, int j, int k) {
-    const u64 x = j ? (r[0] << (2 * j)) | (r[1] >> (64 - 2 * j)) : r[0];
-    const u64 kmask = (k == 32) ? ~0ull : ((1ull << (2 * k)) - 1);
-    const u64 fwd = x >> (64 - 2 * k);
-    const u64 rc = (rev_pairs(fwd) >> (64 - 2 * k)) ^ (0xAAAAAAAAAAAAAAAAull & kmask);
-    return kmix(fwd < rc ? fwd : rc);
-}
-__device__ __forceinline__ K2 sk_key2(const u64* r, int j, int k) {
-    const u64 y0 = j ? (r[0] << (2 * j)) | (r[1] >> (64 - 2 * j)) : r[0];
-    const u64 y1 = j ? (r[1] << (2 * j)) | (r[2] >> (64 - 2 * j)) : r[1];
-    const int sh = 128 - 2 * k;                                // 0..62
-    const int kh = 2 * k - 64;
-    const u64 hmask = (kh == 64) ? ~0ull : ((1ull << kh) - 1);
-    const u64 flo = sh ? (y1 >> sh) | (y0 << (64 - sh)) : y1;
-    const u64 fhi = sh ? (y0 >> sh) : y0;
-    u64 rhi = rev_pairs(flo), rlo = rev_pairs(fhi);
-    if (sh) { rlo = (rlo >> sh) | (rhi << (64 - sh)); rhi >>= sh; }
-    rlo ^= 0xAAAAAAAAAAAAAAAAull;
-    rhi ^= (0xAAAAAAAAAAAAAAAAull & hmask);
-    const bool fl = fhi < rhi || (fhi == rhi && flo < rlo);
-    K2 o; o.w[1] = fl ? fhi : rhi; o.w[0] = fl ? flo : rlo;
-    kmixN(o);
-    return o;
-}
-
-// ---------------------------------------------------------------- receiver: records -> dense mixed keys
-// One block per chunk of records.  A tile of SKX_NT records is staged in LDS together with a slot map
-// (output slot -> record, k-mer index), then every thread builds ONE k-mer per trip straight from the
-// staged bases (a funnel shift + rev_pairs; no rolling, no idle lanes) and stores it coalesced.
-template <int W>
-__global__ __launch_bounds__(SKX_NT) void k_sk_expand(const u64* __restrict__ rec, u64 nrec, u32 R, int k, u32 rpc,
-                                                      const u64* __restrict__ chunk_base, typename KeyT<W>::T* __restrict__ out) {
-    __shared__ u64 srec[SKX_NT * 3];
-    __shared__ unsigned short smap[SKX_NT * SK_MAXN];
-    __shared__ u32 wsum[SKX_NT / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const u64 rbeg = (u64)blockIdx.x * rpc;
-    const u64 rend = rbeg + rpc < nrec ? rbeg + rpc : nrec;
-    u64 obase = chunk_base[blockIdx.x];
-    for (u64 r0 = rbeg; r0 < rend; r0 += SKX_NT) {
-        const u64 r = r0 + tid;
-        u32 n = 0;
-        if (r < rend) {
-            const u64* p = rec + r * R;
-            const u64 a = p[0], b = p[1], c = (R == 3) ? p[2] : 0ull;
-            srec[tid * 3] = a; srec[tid * 3 + 1] = b; srec[tid * 3 + 2] = c;
-            n = (u32)((R == 3 ? c : b) & 0xFFu);
-        }
-        u32 inc = n;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const u32 v = __shfl_up(inc, d); if (lane >= d) inc += v; }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        u32 off = inc - n, total = 0;
-#pragma unroll
-        for (int x = 0; x < SKX_NT / 64; ++x) { const u32 v = wsum[x]; if (x < wave) off += v; total += v; }
-        for (u32 j = 0; j < n; ++j) smap[off + j] = (unsigned short)((tid << 5) | j);
-        __syncthreads();
-        for (u32 i = tid; i < total; i += SKX_NT) {
-            const u32 e = smap[i];
-            const u64* rr = srec + (e >> 5) * 3;
-            if (W == 1) reinterpret_cast<u64*>(out)[obase + i] = sk_key1(rr, (int)(e & 31u), k);
-            else reinterpret_cast<K2*>(out)[obase + i] = sk_key2(rr, (int)(e & 31u), k);
-        }
-        obase += total;
-        __syncthreads();
-    }
-}
-
-// ---------------------------------------------------------------- receiver: a positional SAMPLE of the records as a key array
-// Sample chunk c = the records [cbeg[c], cbeg[c] + nr) (nr candidates, as a level-1 tile takes them); every candidate gets 16 key
-// slots in out[(c * nr + i) * SK_MAXN ..], filled with its k-mers' mixed keys and, behind them (and for candidates past the end of the
-// records), the all-ones sentinel -- a key array with pads, which the histogram / heavy-k-mer kernels of the key-array source read
-// as it is (tile_keys_array masks the pads).  The level-1 slices of the receive side are sized from it, per bin.
-template <int W>
-__global__ __launch_bounds__(SKX_NT) void k_sk_sample_keys(const u64* __restrict__ rec, u64 nrec, u32 R, int k, const u64* __restrict__ cbeg, u32 nr,
-                                                           typename KeyT<W>::T* __restrict__ out) {
-    typedef typename KeyT<W>::T Key;
-    const u64 r0 = cbeg[blockIdx.x];
-    Key* o = out + (u64)blockIdx.x * nr * SK_MAXN;
-    for (u32 i = threadIdx.x; i < nr; i += SKX_NT) {
-        const u64 r = r0 + i;
-        u64 w[3] = {0ull, 0ull, 0ull};
-        u32 n = 0;
-        if (r < nrec) {
-            const u64* p = rec + r * R;
-            w[0] = p[0]; w[1] = p[1]; if (R == 3) w[2] = p[2];
-            n = (u32)(w[R - 1] & 0xFFu);
-            if (n > SK_MAXN) n = SK_MAXN;
-        }
-        for (u32 j = 0; j < SK_MAXN; ++j) {
-            Key key = empty_key<W>();
-            if (j < n) sk_key(w, (int)j, k, key);
-            o[(u64)i * SK_MAXN + j] = key;
         }
     }
 }

@@ -1729,9 +1729,10 @@ def test_partition_order_is_the_reference_contract(oracle, golden_dir, dev, monk
 
 
 def test_multi_pass_count_leaves_the_sender_state_alone(oracle, dev):
-    """the record-based level 0 of a multi-pass count borrows the context's multi-GPU sender state (owners =
-    passes, a repartition table for that many owners) -- and must give it back: a later dskgpu_mg_* call on the same world_size = 1
-    context sees ONE owner again (it used to loop over up to 64 owners into the caller's one-entry arrays)."""
+    """the record-based level 0 of a multi-pass count has a sender state of its own (owners = passes, a
+    repartition table for that many owners) and leaves the exchange's alone: a later dskgpu_mg_* call on the same world_size = 1
+    context sees ONE owner (when the level 0 borrowed the exchange's state, such a call once looped over up to 64 owners into the
+    caller's one-entry arrays)."""
     from dsk_amd import KmerCounter, synth
     from dsk_amd.multi import scatter_records
     reads = synth.make_reads(synth.make_genome(300_000, dev), 100_000, 150)
@@ -1752,6 +1753,33 @@ def test_multi_pass_count_leaves_the_sender_state_alone(oracle, dev):
         assert (kc.histogram() == ref.histogram(10000)).all()
         kc.count()                                                                    # ... and the multi-pass count again, afterwards
         assert kc.stats()["n_distinct"] == ref.distinct
+
+
+def test_multi_pass_count_keeps_the_callers_repartition_table(oracle, dev):
+    """The record-based level 0 builds a repartition table for its passes; the table the caller set for the exchange (mg_set_table) is
+    another one and survives the count: all buckets split -- every window a one-k-mer record -- sends the same records before and after,
+    and more of them than the default table does."""
+    from dsk_amd import KmerCounter, synth
+    from dsk_amd.engine import MG_BUCKETS
+    from dsk_amd.multi import scatter_records
+    reads = synth.make_reads(synth.make_genome(300_000, dev), 100_000, 150)
+    ref = oracle.count(reads.cpu().numpy(), 31)
+    with KmerCounter(kmer_size=31, abundance_min=1) as kc:                            # what the default table sends for these reads
+        kc.set_reads_device(reads.data_ptr(), reads.numel())
+        _, default_counts = scatter_records(kc, None, dev)
+    with KmerCounter(kmer_size=31, abundance_min=1, max_pass_mkeys=2) as kc:
+        kc.set_reads_device(reads.data_ptr(), reads.numel())
+        kc.mg_set_table(np.full(MG_BUCKETS, 255, dtype=np.uint8))
+        _, counts = scatter_records(kc, None, dev)
+        sent = kc.mg_sent_kmers()
+        assert sent == [ref.total]
+        kc.count()
+        st = kc.stats()
+        assert st["n_passes"] > 4 and st["n_read_sweeps"] < st["n_passes"]            # the record-based level 0 ran
+        assert st["n_kmers"] == ref.total and st["n_distinct"] == ref.distinct
+        _, counts2 = scatter_records(kc, None, dev)
+        assert counts2 == counts and kc.mg_sent_kmers() == sent
+        assert counts[0] > default_counts[0]
 
 
 @pytest.mark.parametrize("k", [40, 63, 70, 100])

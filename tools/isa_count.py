@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
-"""Static instruction counts of device kernels (no GPU needed): compiles dskgpu.hip to gfx950 assembly and prints, per kernel whose
-mangled name contains <pattern>, the VGPR count / occupancy and the instructions per basic block by class.
-   python tools/isa_count.py <pattern> [min block size]"""
+"""Static instruction counts of device kernels (no GPU needed): compiles one translation unit of dsk_amd/csrc (dskgpu.hip unless named:
+the sender kernels are in sender.hip) to gfx950 assembly and prints, per kernel whose mangled name contains <pattern>, the VGPR count /
+occupancy and the instructions per basic block by class.
+   python tools/isa_count.py <pattern> [min block size [unit.hip]]"""
 import os, re, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pat = sys.argv[1]
 minb = int(sys.argv[2]) if len(sys.argv) > 2 else 12
-out = "/tmp/isa_dskgpu.s"
+unit = sys.argv[3] if len(sys.argv) > 3 else "dskgpu.hip"
+out = "/tmp/isa_%s.s" % os.path.splitext(unit)[0]
 cs = os.path.join(root, "dsk_amd", "csrc")
-src = os.path.join(cs, "dskgpu.hip")
+src = os.path.join(cs, unit)
 if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(os.path.join(cs, f)) for f in os.listdir(cs) if not f.endswith(".so")):
     subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-Wno-unused-function", "-ffp-contract=off", "-w",
                            "-S", "--cuda-device-only", "-o", out, src])
