@@ -1863,6 +1863,7 @@ void dskgpu_destroy(dskgpu_ctx* ctx) {
     ctx->sender.release(); ctx->l0_sender.release();
     ctx->query.release();
     ctx->unitigs.release();
+    ctx->filtered.release();
     if (ctx->land) (void)hipHostFree(ctx->land);
     for (DevBuf* b : bufs) b->release();
     for (int i = 0; i < 4; ++i) { ctx->out_w[i].release(); ctx->srt_w[i].release(); ctx->acc_w[i].release(); ctx->u_w[i].release(); ctx->s_w[i].release(); }

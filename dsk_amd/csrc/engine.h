@@ -4,7 +4,8 @@
 // the record-based level 0 of a multi-pass count (rec_l0_*) -- and owns the two Sender states (dskgpu_ctx::sender, ::l0_sender);
 // rowsort.hip orders the solid rows (order_rows) and owns the row sort's state (dskgpu_ctx::rs); query.hip answers lookups in the
 // last result (dskgpu_query_*) and owns dskgpu_ctx::query; graph.hip answers the de Bruijn neighbourhood of k-mers from the same index
-// (dskgpu_graph_*); unitigs.hip compacts the rows' graph into unitigs and links them (dskgpu_unitigs*, dskgpu_unitig_edges*) and owns dskgpu_ctx::unitigs.  Private to the library.
+// (dskgpu_graph_*); unitigs.hip compacts the rows' graph into unitigs and links them (dskgpu_unitigs*, dskgpu_unitig_edges*) and owns dskgpu_ctx::unitigs;
+// tips.hip takes rows out of a result (dskgpu_filter_rows) and finds and clips the tips of the compacted graph (dskgpu_graph_tips, dskgpu_clip_tips) and owns dskgpu_ctx::filtered.  Private to the library.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -145,6 +146,7 @@ struct Query {
     u64 cap = 0;
     bool valid = false;            // the table indexes the current result (dskgpu_ctx::drop_result clears it)
     void release() { table.release(); packed.release(); inval.release(); deg.release(); cap = 0; valid = false; }
+    void invalidate() { valid = false; }      // the rows changed under it (dskgpu_filter_rows): built again on the next use, in the memory it has
 };
 
 // The rows' de Bruijn graph compacted into unitigs (unitigs.hip), built on the first dskgpu_unitigs* call after a count: per row the unitig
@@ -160,6 +162,26 @@ struct Unitigs {
     bool e_valid = false;          // ... and the edges are those of that compaction
     void release_edges() { for (DevBuf* b : {&ends, &e_offsets, &e_targets}) b->release(); e_stats = dskgpu_unitig_edge_stats{}; e_valid = false; }
     void release() { for (DevBuf* b : {&unitig, &pos, &offsets, &ab_sum, &kind}) b->release(); stats = dskgpu_unitig_stats{}; valid = false; release_edges(); }
+    void invalidate() { stats = dskgpu_unitig_stats{}; e_stats = dskgpu_unitig_edge_stats{}; valid = false; e_valid = false; }      // as Query::invalidate
+};
+
+// The rows that dskgpu_filter_rows kept (tips.hip): two sets of row arrays, so that a filter of filtered rows reads one set and writes the
+// other; cur = the set res_w / res_ab point into, -1 = the result is still the count's own.  part_off: DSKGPU_F_PARTITION_ORDER, the first
+// kept row of every partition (n_parts + 1 entries) -- rows_partition_range reads them instead of the row sort's while cur >= 0.
+// The rest is scratch: scan = the exclusive scan of the keep flags, rec = the record a round reads back ([TS_COUNT counters | new
+// partition offsets]), off_in = the old partition offsets on the device; info / len / bits / keep = the tip rule's per-unitig and per-row
+// bytes.  Like the index and the compaction it is kept between calls (9 bytes per row + 6 per unitig of the largest call), so that a caller
+// who drives the rounds pays no allocation per round, and goes with the result (dskgpu_ctx::drop_result).
+struct Filtered {
+    DevBuf w[2][4], ab[2];
+    int cur = -1;
+    std::vector<u64> part_off;
+    DevBuf scan, tmp, rec, off_in, info, len, bits, keep;
+    void release() {
+        for (int s = 0; s < 2; ++s) { for (int x = 0; x < 4; ++x) w[s][x].release(); ab[s].release(); }
+        for (DevBuf* b : {&scan, &tmp, &rec, &off_in, &info, &len, &bits, &keep}) b->release();
+        cur = -1; part_off.clear();
+    }
 };
 
 // The super-k-mer sender's state (sender.hip): what k_sk_sample / k_sk_hist / k_sk_scatter are launched with and what they leave behind.
@@ -274,9 +296,10 @@ struct dskgpu_ctx {
     std::vector<u64> hist;
     Query query;
     Unitigs unitigs;
+    Filtered filtered;
     // a count starts, or its result is not to be read: the index of the old rows and their unitigs go with them, and so does their memory
     // -- up to 32 + 8 bytes per row that the count about to run may need (a no-op for a context that was never queried)
-    void drop_result() { have_result = false; query.release(); unitigs.release(); }
+    void drop_result() { have_result = false; query.release(); unitigs.release(); filtered.release(); }
     // the read stream changed: what was learnt about the old reads -- their kept encoding apart (enc_keep: the caller's to clear) -- goes
     void reads_changed() { enc_fresh = false; sender.prepared = false; sender.exact = false; opt2_off = false; opt1_off = false; mw_v3_off = false; rec_l0_off = false; last_rows = 0; }
 
@@ -356,3 +379,6 @@ QTable query_table(const dskgpu_ctx* ctx);               // what a kernel takes 
 int query_ensure(dskgpu_ctx* ctx, DevBuf& b, size_t bytes, const char* what);
 void query_begin(dskgpu_ctx* ctx);                       // stage marks of a call from "query start" on ...
 int query_finish(dskgpu_ctx* ctx);                       // ... and the wait for the stream that resolves them
+
+// unitigs.hip
+int ensure_edges(dskgpu_ctx* ctx, const char* who);      // the edges of the current result's compaction: there already, or built now (opens the call's stage marks)

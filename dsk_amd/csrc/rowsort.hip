@@ -927,6 +927,7 @@ u32 rows_partitions(const dskgpu_ctx* ctx) {
 void rows_partition_range(const dskgpu_ctx* ctx, u32 p, u64* b, u64* e) {
     const RowSort& rs = ctx->rs;
     if (rs.part_mode) {
+        if (ctx->filtered.cur >= 0) { *b = ctx->filtered.part_off[p]; *e = ctx->filtered.part_off[p + 1]; return; }      // (dskgpu_filter_rows: the kept rows of every partition)
         if (!rs.h_part_off64.empty()) { *b = rs.h_part_off64[p]; *e = rs.h_part_off64[p + 1]; }      // (several passes: 64-bit row numbers)
         else { *b = rs.h_part_off[p]; *e = rs.h_part_off[p + 1]; }
         return;

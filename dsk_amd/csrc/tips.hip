@@ -1,0 +1,210 @@
+// tips.hip -- rows taken out of a result on the device, and the tips of the compacted de Bruijn graph found and clipped with it:
+// dskgpu_filter_rows / dskgpu_graph_tips / dskgpu_clip_tips (include/dskgpu.h).  Host side of tips.h; owns dskgpu_ctx::filtered.
+// The filter reads the result (res_w / res_ab / n_rows) and the partition layout (rows_partition_range) and leaves both describing the
+// kept rows, in buffers of its own; the lookup index, the compaction and the edges are marked stale and built again, in the memory they
+// have, by whoever asks next.  The tip rule reads the tables of unitigs.hip (ensure_edges builds them) and nothing else.  A round of
+// dskgpu_clip_tips reads back ONE record: the four counters of the rule and the new partition offsets, the last of which is the kept total.
+#include <hip/hip_runtime.h>
+#include <rocprim/device/device_scan.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
+
+#include "engine.h"
+#include "tips.h"
+
+namespace {
+
+unsigned blocks(u64 items, u64 per_block) { return (unsigned)((items + per_block - 1) / per_block); }
+
+int abandon(dskgpu_ctx* ctx, int rc) {
+    (void)hipStreamSynchronize(ctx->stream);
+    ctx->marks.clear(); ctx->ev_used = 0;
+    return rc;
+}
+
+// the record of a round: [TS_COUNT counters, zeroed | one new offset per entry of old_off].  old_off = the first row of every partition
+// (DSKGPU_F_PARTITION_ORDER only) and, last, n_rows: its new offset is the kept total
+int begin_record(dskgpu_ctx* ctx, bool with_offsets, std::vector<u64>& old_off) {
+    Filtered& F = ctx->filtered;
+    old_off.clear();
+    if (with_offsets) {
+        if (ctx->rs.part_mode) {
+            const u32 P = rows_partitions(ctx);
+            for (u32 p = 0; p < P; ++p) { u64 b, e; rows_partition_range(ctx, p, &b, &e); old_off.push_back(b); if (p + 1 == P) old_off.push_back(e); }
+            if (P == 0) old_off.push_back(0);
+        }
+        old_off.push_back(ctx->n_rows);
+    }
+    if (const int rc = query_ensure(ctx, F.rec, (TS_COUNT + old_off.size()) * 8, "tip record")) return rc;
+    CK(hipMemsetAsync(F.rec.p, 0, TS_COUNT * 8, ctx->stream));
+    return DSKGPU_OK;
+}
+
+// enqueue: the exclusive scan of the keep flags and, from it, the new offsets into the record.  n_rows > 0; old_off lives until the read-back
+int filter_scan(dskgpu_ctx* ctx, const unsigned char* keep, const std::vector<u64>& old_off) {
+    Filtered& F = ctx->filtered;
+    const u64 n = ctx->n_rows, n_off = old_off.size();
+    if (const int rc = query_ensure(ctx, F.scan, n * 8, "keep scan")) return rc;
+    if (const int rc = query_ensure(ctx, F.off_in, n_off * 8, "partition offsets")) return rc;
+    u64* scan = F.scan.as<u64>();
+    auto flags = rocprim::make_transform_iterator(keep, TKeepFlag());
+    size_t tmp_bytes = 0;
+    CK(rocprim::exclusive_scan(nullptr, tmp_bytes, flags, scan, 0ull, (size_t)n, rocprim::plus<u64>(), ctx->stream));      // LIBRARY SCAN (rocprim): plumbing, one pass over a byte per row
+    if (const int rc = query_ensure(ctx, F.tmp, tmp_bytes ? tmp_bytes : 8, "keep scan")) return rc;
+    CK(rocprim::exclusive_scan(F.tmp.p, tmp_bytes, flags, scan, 0ull, (size_t)n, rocprim::plus<u64>(), ctx->stream));
+    CK(hipMemcpyAsync(F.off_in.p, old_off.data(), n_off * 8, hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_filter_offsets, dim3(blocks(n_off, 256)), dim3(256), 0, ctx->stream, F.off_in.as<u64>(), n_off, scan, keep, n, F.rec.as<u64>() + TS_COUNT);
+    CKL("k_filter_offsets");
+    return DSKGPU_OK;
+}
+
+template <int W>
+void launch_compact(dskgpu_ctx* ctx, const unsigned char* keep, u64 n_kept, int dst) {
+    Filtered& F = ctx->filtered;
+    RowsIn in; RowsOut out;
+    for (int x = 0; x < 4; ++x) { in.w[x] = ctx->res_w[x]; out.w[x] = x < W ? F.w[dst][x].as<u64>() : nullptr; }
+    hipLaunchKernelGGL(k_rows_compact<W>, dim3(blocks(ctx->n_rows, 256)), dim3(256), 0, ctx->stream, in, ctx->res_ab, keep, F.scan.as<u64>(), ctx->n_rows, n_kept,
+                       out, F.ab[dst].as<u32>());
+}
+
+// the kept rows into the set that does not hold the result, then the result is that set.  new_off: the record's offsets on the host.
+// Nothing of the context changes before every buffer is there and the kernel is enqueued
+int filter_apply(dskgpu_ctx* ctx, const unsigned char* keep, const u64* new_off, u64 n_off) {
+    Filtered& F = ctx->filtered;
+    const u64 n = ctx->n_rows, n_kept = new_off[n_off - 1];
+    const int W = ctx->W, dst = F.cur == 0 ? 1 : 0;
+    if (n_kept > n) return fail(ctx, DSKGPU_E_DEVICE, "dskgpu_filter_rows: more rows kept than there are (internal error)");
+    for (u64 i = 0; i + 1 < n_off; ++i)
+        if (new_off[i] > new_off[i + 1]) return fail(ctx, DSKGPU_E_DEVICE, "dskgpu_filter_rows: the kept partitions do not ascend (internal error)");
+    for (int x = 0; x < W; ++x)
+        if (const int rc = query_ensure(ctx, F.w[dst][x], (n_kept + 1) * 8, "kept rows")) return rc;
+    if (const int rc = query_ensure(ctx, F.ab[dst], (n_kept + 1) * 4, "kept rows")) return rc;
+    if (W == 1) launch_compact<1>(ctx, keep, n_kept, dst); else if (W == 2) launch_compact<2>(ctx, keep, n_kept, dst); else launch_compact<4>(ctx, keep, n_kept, dst);
+    CKL("k_rows_compact");
+    for (int x = 0; x < 4; ++x) ctx->res_w[x] = x < W ? F.w[dst][x].as<u64>() : nullptr;
+    ctx->res_ab = F.ab[dst].as<u32>();
+    ctx->n_rows = n_kept;
+    F.cur = dst;
+    if (ctx->rs.part_mode) F.part_off.assign(new_off, new_off + (n_off - 1)); else F.part_off.clear();
+    ctx->query.invalidate(); ctx->unitigs.invalidate();
+    return DSKGPU_OK;
+}
+
+int read_record(dskgpu_ctx* ctx, std::vector<u64>& h, u64 n_off) {
+    h.assign(TS_COUNT + n_off, 0);
+    CK(hipMemcpyAsync(h.data(), ctx->filtered.rec.p, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    CK(hipStreamSynchronize(ctx->stream));
+    return DSKGPU_OK;
+}
+
+// enqueue one round of the rule on the current result, whose edges are there: bits per unitig (F.bits), the counters into the record,
+// d_row_tip (may be null) and, with want_keep, the keep flags of the rows (F.keep).  n_rows > 0
+int tips_enqueue(dskgpu_ctx* ctx, const dskgpu_tip_params& p, unsigned char* d_row_tip, bool want_keep) {
+    Filtered& F = ctx->filtered;
+    const Unitigs& U = ctx->unitigs;
+    const u64 n = ctx->n_rows, nu = U.stats.n_unitigs;
+    if (const int rc = query_ensure(ctx, F.info, nu, "tip candidates")) return rc;
+    if (const int rc = query_ensure(ctx, F.len, nu * 4, "tip lengths")) return rc;
+    if (const int rc = query_ensure(ctx, F.bits, nu, "tip bits")) return rc;
+    if (want_keep) if (const int rc = query_ensure(ctx, F.keep, n, "keep flags")) return rc;
+    const dim3 ugrid(blocks(nu, 256));
+    hipLaunchKernelGGL(k_tip_candidates, ugrid, dim3(256), 0, ctx->stream, U.offsets.as<u64>(), U.kind.as<unsigned char>(), U.ab_sum.as<u64>(), U.e_offsets.as<u64>(), nu,
+                       (int)ctx->cfg.kmer_size, p.max_nodes, p.max_abundance, F.info.as<unsigned char>(), F.len.as<u32>());
+    CKL("k_tip_candidates");
+    hipLaunchKernelGGL(k_tip_decide, ugrid, dim3(256), 0, ctx->stream, F.info.as<unsigned char>(), F.len.as<u32>(), U.ab_sum.as<u64>(), U.e_offsets.as<u64>(),
+                       U.e_targets.as<u32>(), nu, U.e_stats.n_edges, F.bits.as<unsigned char>(), F.rec.as<u64>());
+    CKL("k_tip_decide");
+    if (d_row_tip || want_keep) {
+        hipLaunchKernelGGL(k_tip_rows, dim3(blocks(n, 256)), dim3(256), 0, ctx->stream, U.unitig.as<u32>(), F.bits.as<unsigned char>(), n, nu, d_row_tip,
+                           want_keep ? F.keep.as<unsigned char>() : (unsigned char*)nullptr);
+        CKL("k_tip_rows");
+    }
+    return DSKGPU_OK;
+}
+
+int check_params(dskgpu_ctx* ctx, const dskgpu_tip_params* p, const char* who) {
+    if (!p) return fail(ctx, DSKGPU_E_ARG, std::string(who) + ": null params");
+    if (p->max_nodes == 0 || p->max_nodes > T_MAX_NODES) return fail(ctx, DSKGPU_E_ARG, std::string(who) + ": max_nodes must be in 1..65535");
+    return DSKGPU_OK;
+}
+
+void add_round(dskgpu_tip_stats& t, const u64* h) {
+    t.n_candidates += h[TS_CAND]; t.n_tips += h[TS_TIPS]; t.n_outranked += h[TS_OUTRANKED]; t.n_rows_clipped += h[TS_ROWS];
+}
+
+}  // namespace
+
+extern "C" {
+
+int dskgpu_filter_rows(dskgpu_ctx* ctx, const void* d_keep, uint64_t* n_kept) {
+    if (!ctx) return DSKGPU_E_ARG;
+    if (!ctx->have_result) return fail(ctx, DSKGPU_E_STATE, "no result to filter: count first");
+    if (ctx->n_rows == 0) { if (n_kept) *n_kept = 0; return DSKGPU_OK; }
+    if (!d_keep) return fail(ctx, DSKGPU_E_ARG, "dskgpu_filter_rows: null d_keep");
+    CK(hipSetDevice(ctx->cfg.device));
+    query_begin(ctx);
+    const unsigned char* keep = static_cast<const unsigned char*>(d_keep);
+    std::vector<u64> old_off, h;
+    if (const int rc = begin_record(ctx, true, old_off)) return abandon(ctx, rc);
+    if (const int rc = filter_scan(ctx, keep, old_off)) return abandon(ctx, rc);
+    if (const int rc = read_record(ctx, h, old_off.size())) return abandon(ctx, rc);
+    if (const int rc = filter_apply(ctx, keep, h.data() + TS_COUNT, old_off.size())) return abandon(ctx, rc);
+    ctx->mark("filter rows");
+    if (const int rc = query_finish(ctx)) return rc;
+    if (n_kept) *n_kept = ctx->n_rows;
+    return DSKGPU_OK;
+}
+
+int dskgpu_graph_tips(dskgpu_ctx* ctx, const dskgpu_tip_params* params, void* d_row_tip, void* d_unitig_tip, dskgpu_tip_stats* stats) {
+    if (!ctx) return DSKGPU_E_ARG;
+    if (!d_row_tip && !d_unitig_tip && !stats) return fail(ctx, DSKGPU_E_ARG, "dskgpu_graph_tips: no output pointer");
+    if (const int rc = check_params(ctx, params, "dskgpu_graph_tips")) return rc;
+    if (const int rc = ensure_edges(ctx, "dskgpu_graph_tips")) return rc;
+    dskgpu_tip_stats t{};
+    if (ctx->n_rows == 0) {
+        if (const int rc = query_finish(ctx)) return rc;
+        if (stats) *stats = t;
+        return DSKGPU_OK;
+    }
+    std::vector<u64> old_off, h;
+    if (const int rc = begin_record(ctx, false, old_off)) return abandon(ctx, rc);
+    if (const int rc = tips_enqueue(ctx, *params, static_cast<unsigned char*>(d_row_tip), false)) return abandon(ctx, rc);
+    if (d_unitig_tip) CK(hipMemcpyAsync(d_unitig_tip, ctx->filtered.bits.p, ctx->unitigs.stats.n_unitigs, hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->mark("tips");
+    if (const int rc = read_record(ctx, h, 0)) return abandon(ctx, rc);
+    if (const int rc = query_finish(ctx)) return rc;
+    add_round(t, h.data());
+    t.n_rounds = 1; t.n_rows_left = ctx->n_rows - t.n_rows_clipped;
+    if (stats) *stats = t;
+    return DSKGPU_OK;
+}
+
+int dskgpu_clip_tips(dskgpu_ctx* ctx, const dskgpu_tip_params* params, dskgpu_tip_stats* stats) {
+    if (!ctx) return DSKGPU_E_ARG;
+    if (const int rc = check_params(ctx, params, "dskgpu_clip_tips")) return rc;
+    if (params->max_rounds > 64) return fail(ctx, DSKGPU_E_ARG, "dskgpu_clip_tips: max_rounds must be in 0..64");
+    const u64 max_rounds = params->max_rounds ? params->max_rounds : 64;
+    dskgpu_tip_stats t{};
+    std::vector<u64> old_off, h;
+    int rc = DSKGPU_OK;
+    for (;;) {
+        if ((rc = ensure_edges(ctx, "dskgpu_clip_tips"))) break;              // (of the final rows too: the graph is ready when the call returns)
+        if (ctx->n_rows == 0 || t.n_rounds == max_rounds) { rc = query_finish(ctx); break; }
+        const u64 n = ctx->n_rows;
+        if ((rc = begin_record(ctx, true, old_off)) || (rc = tips_enqueue(ctx, *params, nullptr, true))) { abandon(ctx, rc); break; }
+        ctx->mark("tips");
+        const unsigned char* keep = ctx->filtered.keep.as<unsigned char>();
+        if ((rc = filter_scan(ctx, keep, old_off)) || (rc = read_record(ctx, h, old_off.size()))) { abandon(ctx, rc); break; }
+        if (h[TS_TIPS] == 0) { add_round(t, h.data()); rc = query_finish(ctx); break; }
+        if (h[TS_ROWS] + h.back() != n) { rc = abandon(ctx, fail(ctx, DSKGPU_E_DEVICE, "dskgpu_clip_tips: the tips' rows and the kept rows do not add up (internal error)")); break; }
+        if ((rc = filter_apply(ctx, keep, h.data() + TS_COUNT, old_off.size()))) { abandon(ctx, rc); break; }
+        ctx->mark("filter rows");
+        add_round(t, h.data());
+        ++t.n_rounds;
+        if ((rc = query_finish(ctx))) break;
+    }
+    t.n_rows_left = ctx->n_rows;
+    if (stats) *stats = t;
+    return rc;
+}
+
+}  // extern "C"

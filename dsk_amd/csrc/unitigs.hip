@@ -233,7 +233,9 @@ int build_edges(dskgpu_ctx* ctx) {
     return DSKGPU_OK;
 }
 
-// the edges of the current result's compaction: there already, or built now (the compaction and the index below them too)
+}  // namespace
+
+// the edges of the current result's compaction: there already, or built now (the compaction and the index below them too).  tips.hip calls it.
 int ensure_edges(dskgpu_ctx* ctx, const char* who) {
     if (const int rc = ensure_unitigs(ctx, who)) return rc;
     if (ctx->unitigs.e_valid) return DSKGPU_OK;
@@ -246,8 +248,6 @@ int ensure_edges(dskgpu_ctx* ctx, const char* who) {
     ctx->unitigs.e_valid = true;
     return DSKGPU_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

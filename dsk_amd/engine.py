@@ -81,6 +81,27 @@ class _UnitigEdgeStats(C.Structure):
     ]
 
 
+class _TipParams(C.Structure):
+    _fields_ = [
+        ("max_nodes", C.c_uint32),
+        ("max_abundance", C.c_uint32),
+        ("max_rounds", C.c_uint32),
+        ("reserved", C.c_uint32 * 5),
+    ]
+
+
+class _TipStats(C.Structure):
+    _fields_ = [
+        ("n_candidates", C.c_uint64),
+        ("n_tips", C.c_uint64),
+        ("n_outranked", C.c_uint64),
+        ("n_rows_clipped", C.c_uint64),
+        ("n_rounds", C.c_uint64),
+        ("n_rows_left", C.c_uint64),
+        ("reserved", C.c_uint64 * 2),
+    ]
+
+
 MG_BUCKETS = 4096      # DSKGPU_MG_BUCKETS
 MG_SPLIT = 255         # DSKGPU_MG_SPLIT
 
@@ -112,6 +133,7 @@ EXPORTS = [
     "dskgpu_set_row_order", "dskgpu_num_partitions", "dskgpu_partition_size", "dskgpu_partition_offsets", "dskgpu_partition_copy", "dskgpu_result_device",
     "dskgpu_stage_times", "dskgpu_query_prepare", "dskgpu_query_kmers", "dskgpu_query_reads", "dskgpu_graph_adjacency", "dskgpu_graph_neighbors",
     "dskgpu_unitigs", "dskgpu_unitigs_rows", "dskgpu_unitigs_table", "dskgpu_unitigs_stream", "dskgpu_unitig_edges", "dskgpu_unitig_edges_table",
+    "dskgpu_filter_rows", "dskgpu_graph_tips", "dskgpu_clip_tips",
     "dskgpu_k_encode", "dskgpu_k_enumerate", "dskgpu_k_minimizers",
     "dskgpu_group_create", "dskgpu_group_destroy", "dskgpu_group_last_error", "dskgpu_group_size", "dskgpu_group_ctx",
     "dskgpu_group_transport", "dskgpu_group_count", "dskgpu_group_exchanged_words", "dskgpu_group_sliced_steps", "dskgpu_group_histogram", "dskgpu_group_histogram2d",
@@ -209,6 +231,12 @@ def load_library():
     lib.dskgpu_unitig_edges.restype = C.c_int
     lib.dskgpu_unitig_edges_table.argtypes = [vp, vp, vp, vp]
     lib.dskgpu_unitig_edges_table.restype = C.c_int
+    lib.dskgpu_filter_rows.argtypes = [vp, vp, C.POINTER(u64)]
+    lib.dskgpu_filter_rows.restype = C.c_int
+    lib.dskgpu_graph_tips.argtypes = [vp, C.POINTER(_TipParams), vp, vp, C.POINTER(_TipStats)]
+    lib.dskgpu_graph_tips.restype = C.c_int
+    lib.dskgpu_clip_tips.argtypes = [vp, C.POINTER(_TipParams), C.POINTER(_TipStats)]
+    lib.dskgpu_clip_tips.restype = C.c_int
     lib.dskgpu_k_encode.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_enumerate.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_minimizers.argtypes = [vp, vp, u64, vp, vp]
@@ -700,6 +728,59 @@ class KmerCounter:
                 for V in targets[off[U]: off[U + 1]]:
                     f.write("L\t%d\t%s\t%d\t%s\t%s\n" % (U >> 1, "-" if U & 1 else "+", int(V) >> 1, "-" if int(V) & 1 else "+", overlap))
         return {"n_segments": len(seqs), "n_links": int(len(targets))}
+
+    # -- rows out of a result, and the tips of the compacted graph (include/dskgpu.h: dskgpu_filter_rows / _graph_tips / _clip_tips)
+    def filter_rows(self, d_keep: int) -> int:
+        """d_keep: n_rows bytes on the device (result order), non-zero = keep the row.  The result, its partitions and every lookup and
+        graph call describe the kept rows from now on; stats() and histogram() stay the count's.  -> the rows left."""
+        n = C.c_uint64(0)
+        self._ck(self._lib.dskgpu_filter_rows(self._h, C.c_void_p(d_keep) if d_keep else None, C.byref(n)))
+        return int(n.value)
+
+    def filter_rows_tensor(self, keep) -> int:
+        """keep: CUDA bool or uint8 tensor of n_rows flags.  -> the rows left."""
+        import torch
+        if not keep.is_cuda or keep.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("filter_rows_tensor: a CUDA bool or uint8 tensor is needed")
+        n = self.result_device()[2]
+        if keep.numel() != n:
+            raise ValueError("filter_rows_tensor: %d flags for %d rows" % (keep.numel(), n))
+        keep = keep.contiguous().view(torch.uint8)
+        torch.cuda.current_stream(keep.device).synchronize()      # the context's stream is not torch's: the flags are written before the filter reads them
+        return self.filter_rows(keep.data_ptr() if n else 0)
+
+    @staticmethod
+    def _tip_stats(st) -> dict:
+        return {name: int(getattr(st, name)) for name, _ in _TipStats._fields_ if name != "reserved"}
+
+    def graph_tips(self, max_nodes: int, max_abundance: int = 0, d_row_tip: int = 0, d_unitig_tip: int = 0) -> dict:
+        """One round of the tip rule on the last result, which stays as it is.  d_row_tip: n_rows bytes on the device <- 1 = the row's unitig
+        is a tip; d_unitig_tip: n_unitigs bytes <- bit 0 candidate, bit 1 tip, bit 2 outranked; either may be 0.  -> the round's counts:
+        n_candidates, n_tips, n_outranked, n_rows_clipped, n_rounds (1), n_rows_left."""
+        par, st = _TipParams(max_nodes=max_nodes, max_abundance=max_abundance), _TipStats()
+        self._ck(self._lib.dskgpu_graph_tips(self._h, C.byref(par), C.c_void_p(d_row_tip) if d_row_tip else None,
+                                             C.c_void_p(d_unitig_tip) if d_unitig_tip else None, C.byref(st)))
+        return self._tip_stats(st)
+
+    def graph_tips_tensor(self, max_nodes: int, max_abundance: int = 0):
+        """-> (uint8[n_rows] row is on a tip, uint8[n_unitigs] candidate | tip << 1 | outranked << 2, the stats of graph_tips), CUDA tensors."""
+        import torch
+        nu = self.unitigs()["n_unitigs"]
+        n = self.result_device()[2]
+        dev = torch.device("cuda", self.device)
+        row_tip, unitig_tip = torch.zeros(n, dtype=torch.uint8, device=dev), torch.zeros(nu, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()              # the context's stream is not torch's: the zero fill is done before the kernels write
+        st = self.graph_tips(max_nodes, max_abundance, row_tip.data_ptr() if n else 0, unitig_tip.data_ptr() if nu else 0)
+        return row_tip, unitig_tip, st
+
+    def clip_tips(self, max_nodes: Optional[int] = None, max_abundance: int = 0, max_rounds: int = 0) -> dict:
+        """Rounds of (tips -> filter_rows) until a round finds no tip or max_rounds (0 = 64) rounds have clipped; max_nodes None = kmer_size.
+        On return the unitigs and the edges of the rows left are built: write_gfa writes the cleaned graph.  -> the sums over the rounds,
+        n_rounds = rounds that clipped, n_rows_left = the rows of the result now."""
+        par = _TipParams(max_nodes=self.kmer_size if max_nodes is None else max_nodes, max_abundance=max_abundance, max_rounds=max_rounds)
+        st = _TipStats()
+        self._ck(self._lib.dskgpu_clip_tips(self._h, C.byref(par), C.byref(st)))
+        return self._tip_stats(st)
 
     # -- kernel-level entry points (parity tests)
     def k_encode(self, d_bytes: int, nbytes: int, d_packed: int, d_invalid: int) -> None:

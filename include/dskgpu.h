@@ -259,6 +259,7 @@ typedef struct dskgpu_stats {
                                 count materialises the keys of up to 16 passes per sweep -- this is what DSK calls a pass
                                 (each one re-reads the input; README.md:126-130 "below 10")                             */
 } dskgpu_stats;
+/* The record of the last COUNT: dskgpu_filter_rows / dskgpu_clip_tips change neither it nor the histogram (n_solid stays what the count found). */
 int dskgpu_get_stats(const dskgpu_ctx* ctx, dskgpu_stats* out);
 
 /* out[0..nbins-1]; out[i] = number of distinct k-mers whose
@@ -425,6 +426,63 @@ int dskgpu_unitig_edges(dskgpu_ctx* ctx, dskgpu_unitig_edge_stats* stats);
  * d_offsets[2 * n_unitigs] = n_edges); d_targets u32[n_edges] the oriented unitigs V; d_ends u32[2 * n_unitigs], ends[U] = last(U) as an
  * oriented node number 2 r + s -- the way back from a unitig to its rows.  Any may be NULL; all NULL: DSKGPU_E_ARG. */
 int dskgpu_unitig_edges_table(dskgpu_ctx* ctx, void* d_offsets, void* d_targets, void* d_ends);
+
+/* ---- tip clipping: the first call that CHANGES a graph -- what Minia, BCALM's tip removal and gatb-core's `Graph` simplifications do
+ * before anything else, because on real reads the compacted graph is dominated by the short dead ends that sequencing errors leave.
+ * Two pieces: a way to take rows out of a result (dskgpu_filter_rows), after which every call above serves the graph of the kept rows with
+ * the code it has, and the tip rule on the tables of the compaction and the edges (dskgpu_graph_tips; dskgpu_clip_tips runs rounds of both).
+ * Everything is exact integer arithmetic; nothing depends on the row order except the numbering.
+ * With unitig u of L[u] = (offsets[u + 1] - offsets[u]) - k rows, S[u] = ab_sum[u], kind[u], its readings U = 2u + t, E(U) = the targets of U in
+ * the table of dskgpu_unitig_edges_table and deg(U) = |E(U)|:
+ *   CANDIDATE  cand[u] <=> kind[u] == 0, L[u] <= max_nodes, exactly one of deg(2u), deg(2u + 1) is 0, and max_abundance == 0 or
+ *              S[u] <= max_abundance * L[u].  The ATTACHED END A(u) is the one of 2u, 2u + 1 that has edges.
+ *   SIBLINGS   of u: the unitigs w = X >> 1 with X in E(V ^ 1) for some V in E(A(u)), w != u -- what else hangs on the nodes u hangs on;
+ *              read off the tables as they are (palindromes need no special case), at most 4 x 4 entries.
+ *   STRONGER   stronger(w, u) <=> S[w] * L[u] > S[u] * L[w], or the products are equal and L[w] > L[u] (max_nodes <= 65535 keeps the
+ *              products of two candidates inside 64 bits).
+ *   TIP        tip[u] <=> cand[u] and some sibling w has !cand[w] or stronger(w, u); OUTRANKED when no sibling has !cand[w], so that only
+ *              stronger candidates clipped it.
+ * So a dead start that forks is never clipped (it has no sibling), two equally strong short ends of a fork both stay, and an isolated
+ * unitig is never clipped.  A ROUND removes the rows of all tips; the graph of the remaining rows is compacted again, and a round that
+ * finds no tip ends the loop.  Bubble popping is not done, and a rank of a group (world_size > 1) has no compaction to clip. */
+typedef struct dskgpu_tip_params {
+    uint32_t max_nodes, max_abundance, max_rounds, reserved[5];
+} dskgpu_tip_params;                                     /* 32 bytes; max_nodes 1..65535, max_abundance 0 = no limit, max_rounds: dskgpu_clip_tips only */
+typedef struct dskgpu_tip_stats {
+    uint64_t n_candidates, n_tips, n_outranked, n_rows_clipped, n_rounds, n_rows_left, reserved[2];
+} dskgpu_tip_stats;                                      /* 64 bytes */
+/* Keep the rows r of the current result with d_keep[r] != 0 (d_keep: n_rows bytes on the device, result order) and drop the others.
+ * The kept rows stay in their order, word arrays and abundance; dskgpu_result_device and every partition accessor describe them from now
+ * on.  The number of partitions is unchanged: in the global order (and with DSKGPU_F_NO_SORT) they are the usual n * p / P ranges of the new
+ * n_rows; with DSKGPU_F_PARTITION_ORDER partition p holds exactly the kept rows of the old partition p -- one pass or several --, still ascending.
+ * For every k and every result a context can hold, a rank's rows (world_size > 1) included.
+ * The lookup index, the compaction and the edges are dropped: the next call that needs them builds them over the kept rows.
+ * dskgpu_get_stats and dskgpu_histogram stay the COUNT's record -- n_solid is what the count found, not what is left; the rows left are
+ * dskgpu_result_device's n_rows.  The reads, a kept encoding and the sender state are untouched.  The kept rows live in buffers of the
+ * context's own (a second filter reads one set and writes another), freed, with the scratch of these calls (9 bytes per row), when the next count starts and by dskgpu_destroy; when they do
+ * not fit: DSKGPU_E_NOMEM and the result is unchanged.  *n_kept (may be NULL) = the rows left.  Runs on the context's stream, synchronous
+ * on return.  Stage time: "filter rows".
+ * Errors: a null ctx, or a null d_keep while there are rows, DSKGPU_E_ARG; no result DSKGPU_E_STATE.  A result with zero rows: DSKGPU_OK,
+ * n_kept = 0, nothing is done. */
+int dskgpu_filter_rows(dskgpu_ctx* ctx, const void* d_keep, uint64_t* n_kept);
+/* One round of the rule on the current result; no row changes.  d_row_tip u8[n_rows]: 1 = the row's unitig is a tip; d_unitig_tip
+ * u8[n_unitigs]: bit 0 = candidate, bit 1 = tip, bit 2 = outranked; stats: the counts of this round with n_rounds = 1 and n_rows_left =
+ * n_rows - n_rows_clipped.  Any may be NULL; all three NULL: DSKGPU_E_ARG.  Builds the edges (and the compaction and the index below them)
+ * when they are not there, and changes nothing else in the context: the reads (a kept encoding included), the result, the stats and the
+ * sender state stay as they are.  Stage time: "tips" (and those of what the call built).
+ * Errors: a null ctx or params, max_nodes 0 or > 65535: DSKGPU_E_ARG; no result DSKGPU_E_STATE; a context with world_size > 1
+ * DSKGPU_E_STATE (the text names world_size); the limits and DSKGPU_E_NOMEM of dskgpu_unitig_edges.  A result with zero rows: all-zero
+ * stats, nothing is written. */
+int dskgpu_graph_tips(dskgpu_ctx* ctx, const dskgpu_tip_params* params, void* d_row_tip, void* d_unitig_tip, dskgpu_tip_stats* stats);
+/* Rounds of (dskgpu_graph_tips -> dskgpu_filter_rows of the rows that are on no tip) until a round finds no tip or max_rounds rounds
+ * have clipped (1..64; 0 = 64; more: DSKGPU_E_ARG).  stats (may be NULL): the sums over the rounds that ran, the last one that found no
+ * tip included -- a stop by max_rounds evaluates no further round, so n_candidates then holds the clipping rounds only --; n_rounds = the rounds that clipped something, n_rows_left = the final n_rows.  On return the compaction and the edges of
+ * the FINAL rows are built: dskgpu_unitigs_stream, dskgpu_unitig_edges_table (and a GFA written from them) give the cleaned graph at once.
+ * What dskgpu_filter_rows says about the rest of the context holds here.  A round reads back one small record; an error in a later round
+ * (DSKGPU_E_NOMEM, say) leaves the result of the rounds already done, which is a consistent result like any other, and stats says
+ * how far the call came.  Stage times: "tips", "filter rows", and "query index" / "graph" / "unitigs" / "unitig edges" of every rebuild.
+ * Errors: those of dskgpu_graph_tips. */
+int dskgpu_clip_tips(dskgpu_ctx* ctx, const dskgpu_tip_params* params, dskgpu_tip_stats* stats);
 
 /* ---- the same call on N GPUs of one node, inside ONE process (what `dsk -nb-gpus N` runs): the reference's
  * single `execute()` (src/DSK.cpp:55-60) still leaves ONE storage with a flat list of solid partitions
