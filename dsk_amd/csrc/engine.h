@@ -5,7 +5,8 @@
 // rowsort.hip orders the solid rows (order_rows) and owns the row sort's state (dskgpu_ctx::rs); query.hip answers lookups in the
 // last result (dskgpu_query_*) and owns dskgpu_ctx::query; graph.hip answers the de Bruijn neighbourhood of k-mers from the same index
 // (dskgpu_graph_*); unitigs.hip compacts the rows' graph into unitigs and links them (dskgpu_unitigs*, dskgpu_unitig_edges*) and owns dskgpu_ctx::unitigs;
-// tips.hip takes rows out of a result (dskgpu_filter_rows) and finds and clips the tips of the compacted graph (dskgpu_graph_tips, dskgpu_clip_tips) and owns dskgpu_ctx::filtered.  Private to the library.
+// tips.hip takes rows out of a result (dskgpu_filter_rows) and finds and clips the tips of the compacted graph (dskgpu_graph_tips, dskgpu_clip_tips) and owns dskgpu_ctx::filtered;
+// bubbles.hip finds and pops the simple bubbles with the same rounds (dskgpu_graph_bubbles, dskgpu_pop_bubbles, dskgpu_simplify).  Private to the library.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -168,18 +169,19 @@ struct Unitigs {
 // The rows that dskgpu_filter_rows kept (tips.hip): two sets of row arrays, so that a filter of filtered rows reads one set and writes the
 // other; cur = the set res_w / res_ab point into, -1 = the result is still the count's own.  part_off: DSKGPU_F_PARTITION_ORDER, the first
 // kept row of every partition (n_parts + 1 entries) -- rows_partition_range reads them instead of the row sort's while cur >= 0.
-// The rest is scratch: scan = the exclusive scan of the keep flags, rec = the record a round reads back ([TS_COUNT counters | new
+// The rest is scratch: scan = the exclusive scan of the keep flags, rec = the record a round reads back ([REC_COUNTERS counters | new
 // partition offsets]), off_in = the old partition offsets on the device; info / len / bits / keep = the tip rule's per-unitig and per-row
-// bytes.  Like the index and the compaction it is kept between calls (9 bytes per row + 6 per unitig of the largest call), so that a caller
+// bytes; the bubble rule (bubbles.hip) uses len / bits / keep too and ends = the two ends of every candidate, one word per unitig.
+// Like the index and the compaction it is kept between calls (9 bytes per row + 14 per unitig of the largest call), so that a caller
 // who drives the rounds pays no allocation per round, and goes with the result (dskgpu_ctx::drop_result).
 struct Filtered {
     DevBuf w[2][4], ab[2];
     int cur = -1;
     std::vector<u64> part_off;
-    DevBuf scan, tmp, rec, off_in, info, len, bits, keep;
+    DevBuf scan, tmp, rec, off_in, info, len, bits, keep, ends;
     void release() {
         for (int s = 0; s < 2; ++s) { for (int x = 0; x < 4; ++x) w[s][x].release(); ab[s].release(); }
-        for (DevBuf* b : {&scan, &tmp, &rec, &off_in, &info, &len, &bits, &keep}) b->release();
+        for (DevBuf* b : {&scan, &tmp, &rec, &off_in, &info, &len, &bits, &keep, &ends}) b->release();
         cur = -1; part_off.clear();
     }
 };
@@ -382,3 +384,14 @@ int query_finish(dskgpu_ctx* ctx);                       // ... and the wait for
 
 // unitigs.hip
 int ensure_edges(dskgpu_ctx* ctx, const char* who);      // the edges of the current result's compaction: there already, or built now (opens the call's stage marks)
+
+// tips.hip: the machinery of a round that takes rows out, shared by the tip and the bubble rule.  The record of a round (Filtered::rec) is
+// [REC_COUNTERS counters of the rule, zeroed | one new offset per entry of old_off]; the last new offset is the kept total
+enum { REC_COUNTERS = 4 };
+int abandon(dskgpu_ctx* ctx, int rc);                    // a call gives up: wait for the stream, forget its stage marks, -> rc
+int begin_record(dskgpu_ctx* ctx, bool with_offsets, std::vector<u64>& old_off);      // the record, its counters zeroed; with_offsets: old_off = the partitions' first rows and n_rows
+int filter_scan(dskgpu_ctx* ctx, const unsigned char* keep, const std::vector<u64>& old_off);      // enqueue the scan of the keep flags and the new offsets into the record
+int read_record(dskgpu_ctx* ctx, std::vector<u64>& h, u64 n_off);      // the round's ONE read-back: REC_COUNTERS + n_off words
+int filter_apply(dskgpu_ctx* ctx, const unsigned char* keep, const u64* new_off, u64 n_off);      // the kept rows become the result
+// per row, bit 1 of Filtered::bits of its unitig -> d_row_flag (may be null) and, with want_keep, its complement -> Filtered::keep
+int flag_rows(dskgpu_ctx* ctx, unsigned char* d_row_flag, bool want_keep);

@@ -11,17 +11,22 @@
 #include "engine.h"
 #include "tips.h"
 
+static_assert(TS_COUNT == REC_COUNTERS, "the tip rule's counters are the record's");
+
 namespace {
 
 unsigned blocks(u64 items, u64 per_block) { return (unsigned)((items + per_block - 1) / per_block); }
 
+}  // namespace
+
+// ---- the machinery of a round (engine.h), shared with bubbles.hip
 int abandon(dskgpu_ctx* ctx, int rc) {
     (void)hipStreamSynchronize(ctx->stream);
     ctx->marks.clear(); ctx->ev_used = 0;
     return rc;
 }
 
-// the record of a round: [TS_COUNT counters, zeroed | one new offset per entry of old_off].  old_off = the first row of every partition
+// the record of a round: [REC_COUNTERS counters, zeroed | one new offset per entry of old_off].  old_off = the first row of every partition
 // (DSKGPU_F_PARTITION_ORDER only) and, last, n_rows: its new offset is the kept total
 int begin_record(dskgpu_ctx* ctx, bool with_offsets, std::vector<u64>& old_off) {
     Filtered& F = ctx->filtered;
@@ -34,8 +39,8 @@ int begin_record(dskgpu_ctx* ctx, bool with_offsets, std::vector<u64>& old_off) 
         }
         old_off.push_back(ctx->n_rows);
     }
-    if (const int rc = query_ensure(ctx, F.rec, (TS_COUNT + old_off.size()) * 8, "tip record")) return rc;
-    CK(hipMemsetAsync(F.rec.p, 0, TS_COUNT * 8, ctx->stream));
+    if (const int rc = query_ensure(ctx, F.rec, (REC_COUNTERS + old_off.size()) * 8, "tip record")) return rc;
+    CK(hipMemsetAsync(F.rec.p, 0, REC_COUNTERS * 8, ctx->stream));
     return DSKGPU_OK;
 }
 
@@ -52,10 +57,12 @@ int filter_scan(dskgpu_ctx* ctx, const unsigned char* keep, const std::vector<u6
     if (const int rc = query_ensure(ctx, F.tmp, tmp_bytes ? tmp_bytes : 8, "keep scan")) return rc;
     CK(rocprim::exclusive_scan(F.tmp.p, tmp_bytes, flags, scan, 0ull, (size_t)n, rocprim::plus<u64>(), ctx->stream));
     CK(hipMemcpyAsync(F.off_in.p, old_off.data(), n_off * 8, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_filter_offsets, dim3(blocks(n_off, 256)), dim3(256), 0, ctx->stream, F.off_in.as<u64>(), n_off, scan, keep, n, F.rec.as<u64>() + TS_COUNT);
+    hipLaunchKernelGGL(k_filter_offsets, dim3(blocks(n_off, 256)), dim3(256), 0, ctx->stream, F.off_in.as<u64>(), n_off, scan, keep, n, F.rec.as<u64>() + REC_COUNTERS);
     CKL("k_filter_offsets");
     return DSKGPU_OK;
 }
+
+namespace {
 
 template <int W>
 void launch_compact(dskgpu_ctx* ctx, const unsigned char* keep, u64 n_kept, int dst) {
@@ -65,6 +72,8 @@ void launch_compact(dskgpu_ctx* ctx, const unsigned char* keep, u64 n_kept, int 
     hipLaunchKernelGGL(k_rows_compact<W>, dim3(blocks(ctx->n_rows, 256)), dim3(256), 0, ctx->stream, in, ctx->res_ab, keep, F.scan.as<u64>(), ctx->n_rows, n_kept,
                        out, F.ab[dst].as<u32>());
 }
+
+}  // namespace
 
 // the kept rows into the set that does not hold the result, then the result is that set.  new_off: the record's offsets on the host.
 // Nothing of the context changes before every buffer is there and the kernel is enqueued
@@ -90,22 +99,35 @@ int filter_apply(dskgpu_ctx* ctx, const unsigned char* keep, const u64* new_off,
 }
 
 int read_record(dskgpu_ctx* ctx, std::vector<u64>& h, u64 n_off) {
-    h.assign(TS_COUNT + n_off, 0);
+    h.assign(REC_COUNTERS + n_off, 0);
     CK(hipMemcpyAsync(h.data(), ctx->filtered.rec.p, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
     return DSKGPU_OK;
 }
+
+int flag_rows(dskgpu_ctx* ctx, unsigned char* d_row_flag, bool want_keep) {
+    Filtered& F = ctx->filtered;
+    const Unitigs& U = ctx->unitigs;
+    const u64 n = ctx->n_rows;
+    if (!d_row_flag && !want_keep) return DSKGPU_OK;
+    if (want_keep) if (const int rc = query_ensure(ctx, F.keep, n, "keep flags")) return rc;
+    hipLaunchKernelGGL(k_tip_rows, dim3(blocks(n, 256)), dim3(256), 0, ctx->stream, U.unitig.as<u32>(), F.bits.as<unsigned char>(), n, U.stats.n_unitigs, d_row_flag,
+                       want_keep ? F.keep.as<unsigned char>() : (unsigned char*)nullptr);
+    CKL("k_tip_rows");
+    return DSKGPU_OK;
+}
+
+namespace {
 
 // enqueue one round of the rule on the current result, whose edges are there: bits per unitig (F.bits), the counters into the record,
 // d_row_tip (may be null) and, with want_keep, the keep flags of the rows (F.keep).  n_rows > 0
 int tips_enqueue(dskgpu_ctx* ctx, const dskgpu_tip_params& p, unsigned char* d_row_tip, bool want_keep) {
     Filtered& F = ctx->filtered;
     const Unitigs& U = ctx->unitigs;
-    const u64 n = ctx->n_rows, nu = U.stats.n_unitigs;
+    const u64 nu = U.stats.n_unitigs;
     if (const int rc = query_ensure(ctx, F.info, nu, "tip candidates")) return rc;
     if (const int rc = query_ensure(ctx, F.len, nu * 4, "tip lengths")) return rc;
     if (const int rc = query_ensure(ctx, F.bits, nu, "tip bits")) return rc;
-    if (want_keep) if (const int rc = query_ensure(ctx, F.keep, n, "keep flags")) return rc;
     const dim3 ugrid(blocks(nu, 256));
     hipLaunchKernelGGL(k_tip_candidates, ugrid, dim3(256), 0, ctx->stream, U.offsets.as<u64>(), U.kind.as<unsigned char>(), U.ab_sum.as<u64>(), U.e_offsets.as<u64>(), nu,
                        (int)ctx->cfg.kmer_size, p.max_nodes, p.max_abundance, F.info.as<unsigned char>(), F.len.as<u32>());
@@ -113,12 +135,7 @@ int tips_enqueue(dskgpu_ctx* ctx, const dskgpu_tip_params& p, unsigned char* d_r
     hipLaunchKernelGGL(k_tip_decide, ugrid, dim3(256), 0, ctx->stream, F.info.as<unsigned char>(), F.len.as<u32>(), U.ab_sum.as<u64>(), U.e_offsets.as<u64>(),
                        U.e_targets.as<u32>(), nu, U.e_stats.n_edges, F.bits.as<unsigned char>(), F.rec.as<u64>());
     CKL("k_tip_decide");
-    if (d_row_tip || want_keep) {
-        hipLaunchKernelGGL(k_tip_rows, dim3(blocks(n, 256)), dim3(256), 0, ctx->stream, U.unitig.as<u32>(), F.bits.as<unsigned char>(), n, nu, d_row_tip,
-                           want_keep ? F.keep.as<unsigned char>() : (unsigned char*)nullptr);
-        CKL("k_tip_rows");
-    }
-    return DSKGPU_OK;
+    return flag_rows(ctx, d_row_tip, want_keep);
 }
 
 int check_params(dskgpu_ctx* ctx, const dskgpu_tip_params* p, const char* who) {

@@ -102,6 +102,37 @@ class _TipStats(C.Structure):
     ]
 
 
+class _BubbleParams(C.Structure):
+    _fields_ = [
+        ("max_nodes", C.c_uint32),
+        ("max_diff", C.c_uint32),
+        ("max_rounds", C.c_uint32),
+        ("reserved", C.c_uint32 * 5),
+    ]
+
+
+class _BubbleStats(C.Structure):
+    _fields_ = [
+        ("n_candidates", C.c_uint64),
+        ("n_in_bubbles", C.c_uint64),
+        ("n_popped", C.c_uint64),
+        ("n_rows_popped", C.c_uint64),
+        ("n_rounds", C.c_uint64),
+        ("n_rows_left", C.c_uint64),
+        ("reserved", C.c_uint64 * 2),
+    ]
+
+
+class _SimplifyStats(C.Structure):
+    _fields_ = [
+        ("n_passes", C.c_uint64),
+        ("n_rows_left", C.c_uint64),
+        ("reserved", C.c_uint64 * 6),
+        ("tips", _TipStats),
+        ("bubbles", _BubbleStats),
+    ]
+
+
 MG_BUCKETS = 4096      # DSKGPU_MG_BUCKETS
 MG_SPLIT = 255         # DSKGPU_MG_SPLIT
 
@@ -134,6 +165,7 @@ EXPORTS = [
     "dskgpu_stage_times", "dskgpu_query_prepare", "dskgpu_query_kmers", "dskgpu_query_reads", "dskgpu_graph_adjacency", "dskgpu_graph_neighbors",
     "dskgpu_unitigs", "dskgpu_unitigs_rows", "dskgpu_unitigs_table", "dskgpu_unitigs_stream", "dskgpu_unitig_edges", "dskgpu_unitig_edges_table",
     "dskgpu_filter_rows", "dskgpu_graph_tips", "dskgpu_clip_tips",
+    "dskgpu_graph_bubbles", "dskgpu_pop_bubbles", "dskgpu_simplify",
     "dskgpu_k_encode", "dskgpu_k_enumerate", "dskgpu_k_minimizers",
     "dskgpu_group_create", "dskgpu_group_destroy", "dskgpu_group_last_error", "dskgpu_group_size", "dskgpu_group_ctx",
     "dskgpu_group_transport", "dskgpu_group_count", "dskgpu_group_exchanged_words", "dskgpu_group_sliced_steps", "dskgpu_group_histogram", "dskgpu_group_histogram2d",
@@ -237,6 +269,12 @@ def load_library():
     lib.dskgpu_graph_tips.restype = C.c_int
     lib.dskgpu_clip_tips.argtypes = [vp, C.POINTER(_TipParams), C.POINTER(_TipStats)]
     lib.dskgpu_clip_tips.restype = C.c_int
+    lib.dskgpu_graph_bubbles.argtypes = [vp, C.POINTER(_BubbleParams), vp, vp, C.POINTER(_BubbleStats)]
+    lib.dskgpu_graph_bubbles.restype = C.c_int
+    lib.dskgpu_pop_bubbles.argtypes = [vp, C.POINTER(_BubbleParams), C.POINTER(_BubbleStats)]
+    lib.dskgpu_pop_bubbles.restype = C.c_int
+    lib.dskgpu_simplify.argtypes = [vp, C.POINTER(_TipParams), C.POINTER(_BubbleParams), C.c_uint32, C.POINTER(_SimplifyStats)]
+    lib.dskgpu_simplify.restype = C.c_int
     lib.dskgpu_k_encode.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_enumerate.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_minimizers.argtypes = [vp, vp, u64, vp, vp]
@@ -781,6 +819,62 @@ class KmerCounter:
         st = _TipStats()
         self._ck(self._lib.dskgpu_clip_tips(self._h, C.byref(par), C.byref(st)))
         return self._tip_stats(st)
+
+    # -- the simple bubbles of the compacted graph, and tips and bubbles in turn (include/dskgpu.h: dskgpu_graph_bubbles / _pop_bubbles / _simplify)
+    @staticmethod
+    def _bubble_stats(st) -> dict:
+        return {name: int(getattr(st, name)) for name, _ in _BubbleStats._fields_ if name != "reserved"}
+
+    def graph_bubbles(self, max_nodes: int, max_diff: int = 4, d_row_pop: int = 0, d_unitig_bits: int = 0) -> dict:
+        """One round of the bubble rule on the last result, which stays as it is.  d_row_pop: n_rows bytes on the device <- 1 = the row's
+        unitig is popped; d_unitig_bits: n_unitigs bytes <- bit 0 candidate, bit 1 popped, bit 2 in a bubble; either may be 0.  -> the
+        round's counts: n_candidates, n_in_bubbles, n_popped, n_rows_popped, n_rounds (1), n_rows_left."""
+        par, st = _BubbleParams(max_nodes=max_nodes, max_diff=max_diff), _BubbleStats()
+        self._ck(self._lib.dskgpu_graph_bubbles(self._h, C.byref(par), C.c_void_p(d_row_pop) if d_row_pop else None,
+                                                C.c_void_p(d_unitig_bits) if d_unitig_bits else None, C.byref(st)))
+        return self._bubble_stats(st)
+
+    def graph_bubbles_tensor(self, max_nodes: int, max_diff: int = 4):
+        """-> (uint8[n_rows] row is popped, uint8[n_unitigs] candidate | popped << 1 | in a bubble << 2, the stats of graph_bubbles), CUDA tensors."""
+        import torch
+        nu = self.unitigs()["n_unitigs"]
+        n = self.result_device()[2]
+        dev = torch.device("cuda", self.device)
+        row_pop, unitig_bits = torch.zeros(n, dtype=torch.uint8, device=dev), torch.zeros(nu, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()              # the context's stream is not torch's: the zero fill is done before the kernels write
+        st = self.graph_bubbles(max_nodes, max_diff, row_pop.data_ptr() if n else 0, unitig_bits.data_ptr() if nu else 0)
+        return row_pop, unitig_bits, st
+
+    def pop_bubbles(self, max_nodes: Optional[int] = None, max_diff: int = 4, max_rounds: int = 0) -> dict:
+        """Rounds of (bubbles -> filter_rows) until a round pops nothing or max_rounds (0 = 64) rounds have popped; max_nodes None =
+        2 * kmer_size.  On return the unitigs and the edges of the rows left are built.  -> the sums over the rounds, n_rounds = rounds that
+        popped, n_rows_left = the rows of the result now."""
+        par = _BubbleParams(max_nodes=2 * self.kmer_size if max_nodes is None else max_nodes, max_diff=max_diff, max_rounds=max_rounds)
+        st = _BubbleStats()
+        self._ck(self._lib.dskgpu_pop_bubbles(self._h, C.byref(par), C.byref(st)))
+        return self._bubble_stats(st)
+
+    def simplify(self, tips: Optional[dict] = None, bubbles: Optional[dict] = None, max_passes: int = 0) -> dict:
+        """Passes of (clip_tips, then pop_bubbles) until a pass removes no row or max_passes (0 = 16) passes have run.  tips / bubbles: the
+        keyword arguments of clip_tips / pop_bubbles (None = their defaults), or False to skip that half.  On return the unitigs and the
+        edges of the rows left are built: write_gfa writes the cleaned graph.  -> {n_passes, n_rows_left, tips: the sums of clip_tips'
+        dicts, bubbles: those of pop_bubbles'}."""
+        tp = bp = None
+        if tips is not False:
+            a = dict(tips or {})
+            mn = a.pop("max_nodes", None)
+            tp = _TipParams(max_nodes=self.kmer_size if mn is None else mn, max_abundance=a.pop("max_abundance", 0), max_rounds=a.pop("max_rounds", 0))
+            if a:
+                raise TypeError("simplify: unknown tip arguments %s" % sorted(a))
+        if bubbles is not False:
+            a = dict(bubbles or {})
+            mn = a.pop("max_nodes", None)
+            bp = _BubbleParams(max_nodes=2 * self.kmer_size if mn is None else mn, max_diff=a.pop("max_diff", 4), max_rounds=a.pop("max_rounds", 0))
+            if a:
+                raise TypeError("simplify: unknown bubble arguments %s" % sorted(a))
+        st = _SimplifyStats()
+        self._ck(self._lib.dskgpu_simplify(self._h, C.byref(tp) if tp is not None else None, C.byref(bp) if bp is not None else None, max_passes, C.byref(st)))
+        return {"n_passes": int(st.n_passes), "n_rows_left": int(st.n_rows_left), "tips": self._tip_stats(st.tips), "bubbles": self._bubble_stats(st.bubbles)}
 
     # -- kernel-level entry points (parity tests)
     def k_encode(self, d_bytes: int, nbytes: int, d_packed: int, d_invalid: int) -> None:

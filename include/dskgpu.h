@@ -444,7 +444,8 @@ int dskgpu_unitig_edges_table(dskgpu_ctx* ctx, void* d_offsets, void* d_targets,
  *              stronger candidates clipped it.
  * So a dead start that forks is never clipped (it has no sibling), two equally strong short ends of a fork both stay, and an isolated
  * unitig is never clipped.  A ROUND removes the rows of all tips; the graph of the remaining rows is compacted again, and a round that
- * finds no tip ends the loop.  Bubble popping is not done, and a rank of a group (world_size > 1) has no compaction to clip. */
+ * finds no tip ends the loop.  Bubbles are popped by the calls of the next section, and a rank of a group (world_size > 1) has no
+ * compaction to clip. */
 typedef struct dskgpu_tip_params {
     uint32_t max_nodes, max_abundance, max_rounds, reserved[5];
 } dskgpu_tip_params;                                     /* 32 bytes; max_nodes 1..65535, max_abundance 0 = no limit, max_rounds: dskgpu_clip_tips only */
@@ -483,6 +484,51 @@ int dskgpu_graph_tips(dskgpu_ctx* ctx, const dskgpu_tip_params* params, void* d_
  * how far the call came.  Stage times: "tips", "filter rows", and "query index" / "graph" / "unitigs" / "unitig edges" of every rebuild.
  * Errors: those of dskgpu_graph_tips. */
 int dskgpu_clip_tips(dskgpu_ctx* ctx, const dskgpu_tip_params* params, dskgpu_tip_stats* stats);
+
+/* ---- bubble popping: the other half of what an assembler does before it reads a contig off the graph.  Tips are the errors near a read's
+ * end; bubbles are the errors, and the SNPs, in its middle: two or more parallel unitigs between the same two ends, one of them weak.
+ * The rule reads the same tables as the tip rule and a round takes rows out the same way (dskgpu_filter_rows); exact integer arithmetic,
+ * nothing depends on the row order except the numbering.  In the notation of the tip section:
+ *   CANDIDATE  cand[u] <=> kind[u] == 0, L[u] <= max_nodes, deg(2u) == 1 and deg(2u + 1) == 1, and with out(u) = E(2u)[0] and in(u) =
+ *              E(2u + 1)[0] neither out(u) >> 1 nor in(u) >> 1 is u.  So u is a simple path from P = in(u) ^ 1 to out(u).
+ *   SIBLINGS   of a candidate u: the unitigs w = X >> 1 for X in E(in(u) ^ 1) (at most 4) with w != u, cand[w], E(X)[0] == out(u),
+ *              E(X ^ 1)[0] == in(u) and |L[w] - L[u]| <= max_diff -- the same two ends, read in the orientation in which P reaches w
+ *              (X even: out(w) == out(u) and in(w) == in(u); X odd: in(w) == out(u) and out(w) == in(u)).  The tables are read as they
+ *              are; palindromes get no special case.
+ *   STRONGER   as for tips: S[w] * L[u] > S[u] * L[w], or the products are equal and L[w] > L[u].
+ *   POPPED     pop[u] <=> cand[u] and some sibling is stronger than u.  IN A BUBBLE <=> cand[u] and u has at least one sibling.
+ * So equally strong branches all stay, of a three-way bubble the two weaker go in one round, and a unitig with more than one edge at an
+ * end is never popped.  A ROUND removes the rows of all popped unitigs; the graph of the remaining rows is compacted again, and a round
+ * that pops nothing ends the loop.  A dead-end branch that carries a bubble is no tip before the bubble is popped, and a popped bubble can
+ * leave a new tip: dskgpu_simplify runs both in turn until the graph stops changing. */
+typedef struct dskgpu_bubble_params {
+    uint32_t max_nodes, max_diff, max_rounds, reserved[5];
+} dskgpu_bubble_params;                                  /* 32 bytes; max_nodes 1..65535, max_diff 0 = equal lengths only, max_rounds: dskgpu_pop_bubbles / dskgpu_simplify only */
+typedef struct dskgpu_bubble_stats {
+    uint64_t n_candidates, n_in_bubbles, n_popped, n_rows_popped, n_rounds, n_rows_left, reserved[2];
+} dskgpu_bubble_stats;                                   /* 64 bytes */
+typedef struct dskgpu_simplify_stats {
+    uint64_t n_passes, n_rows_left, reserved[6];
+    dskgpu_tip_stats tips;
+    dskgpu_bubble_stats bubbles;
+} dskgpu_simplify_stats;                                 /* 192 bytes */
+/* One round of the rule on the current result; no row changes.  d_row_pop u8[n_rows]: 1 = the row's unitig is popped; d_unitig_bits
+ * u8[n_unitigs]: bit 0 = candidate, bit 1 = popped, bit 2 = in a bubble; stats: the counts of this round with n_rounds = 1 and
+ * n_rows_left = n_rows - n_rows_popped.  The outputs, their NULL rules, what the call builds, what it leaves alone and its errors are
+ * those of dskgpu_graph_tips.  Stage time: "bubbles" (and those of what the call built). */
+int dskgpu_graph_bubbles(dskgpu_ctx* ctx, const dskgpu_bubble_params* params, void* d_row_pop, void* d_unitig_bits, dskgpu_bubble_stats* stats);
+/* Rounds of (dskgpu_graph_bubbles -> dskgpu_filter_rows of the rows that are on no popped unitig) until a round pops nothing or max_rounds
+ * rounds have popped (1..64; 0 = 64; more: DSKGPU_E_ARG), with the contract of dskgpu_clip_tips: stats (may be NULL) holds the sums over the
+ * rounds that ran, n_rounds = the rounds that popped something, n_rows_left = the final n_rows; a round reads back one small record; an
+ * error in a later round leaves the consistent result of the rounds already done; on return the compaction and the edges of the FINAL rows
+ * are built.  Stage times: "bubbles", "filter rows", and those of every rebuild.  Errors: those of dskgpu_graph_tips. */
+int dskgpu_pop_bubbles(dskgpu_ctx* ctx, const dskgpu_bubble_params* params, dskgpu_bubble_stats* stats);
+/* Passes of (dskgpu_clip_tips, then dskgpu_pop_bubbles) until a pass removes no row or max_passes passes have run (1..16; 0 = 16; more:
+ * DSKGPU_E_ARG).  A NULL tip_params or bubble_params skips that half; both NULL: DSKGPU_E_ARG.  stats (may be NULL): n_passes = the passes
+ * that removed a row, tips / bubbles = the sums of the two calls' stats over the passes that ran (n_rounds summed too), n_rows_left = the
+ * final n_rows, in all three places.  An error ends the call with the result of what was done, as for dskgpu_clip_tips.
+ * Errors: those of the two calls, checked for both sets of parameters before anything runs. */
+int dskgpu_simplify(dskgpu_ctx* ctx, const dskgpu_tip_params* tip_params, const dskgpu_bubble_params* bubble_params, uint32_t max_passes, dskgpu_simplify_stats* stats);
 
 /* ---- the same call on N GPUs of one node, inside ONE process (what `dsk -nb-gpus N` runs): the reference's
  * single `execute()` (src/DSK.cpp:55-60) still leaves ONE storage with a flat list of solid partitions
