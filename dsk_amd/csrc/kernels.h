@@ -1456,16 +1456,24 @@ __global__ __launch_bounds__(CNT_NT) void k_count1(u64* keys, u64* solid_keys, c
     if (tid == 0 && ndist_acc) atomicAdd(&gstats[0], ndist_acc);
 }
 
-// ---- k_count1v3 (fixed-capacity regions only: the kernel of the histogram-free path): the same table WITHOUT the slot list.  The
-// lane whose CAS claims a slot remembers the slot in a register and sweeps it itself after the barrier: the insert chain loses the
-// list index (a returning LDS add and its wait) and the list write, the sweep loses the list read (by itself: 4.01 -> 3.98 ms --
-// the kernel is bound by dependent LDS round trips and its barriers at 44 % LDS busy, not by the LDS instruction count).  A region
-// holds at most cap <= CNT_V3_KEYS * CNT_NT keys, so a lane has at most CNT_V3_KEYS claims.  (Tried on the way, same results, both
+// ---- k_count1v3 (fixed-capacity regions only: the kernel of the histogram-free path): the same table WITHOUT the block-wide slot
+// list.  The lane whose CAS claims a slot remembers the slot in a register: the insert chain loses the list index (a returning LDS
+// add on a shared counter and its wait).  A region holds at most cap <= CNT_V3_KEYS * CNT_NT keys, so a lane has at most
+// CNT_V3_KEYS claims and a wave at most 64 * CNT_V3_KEYS.  After its inserts a wave ranks its claims -- one ballot per key slot j,
+// rank = claims of the slots before j + claiming lanes below this one, all scalar work plus mbcnt, no atomic -- and writes the slot
+// indices at their ranks into a list of its own (s_wl: 16 bits per claim, 10 KB per block, touched by the owning wave alone, so no
+// barrier is added).  After the barrier the wave sweeps the list 64 claims at a time: ceil(T / 64) passes with full lanes instead
+// of one quarter-filled pass per key slot (a mean sub-partition: ~51 claims per wave, one pass instead of three).  Measured in
+// profiles/count_dense_sweep.md.  The block-uniform nd and bad stay per-lane values: read through readfirstlane (scalar branch,
+// scalar ndist_acc) the same kernel took 5.1-5.4 ms instead of 3.6-3.8, with the old sweep as with this one -- one more of this
+// kernel's schedule cliffs.  (Tried on the way, same results, both
 // slower: a round that handles a lane's three keys together -- three reads, then three CASes in flight, a wave-private slot list,
 // every step behind a wave-uniform ballot -- 6.2 ms; the same round one key at a time 5.0 ms; three blocks of 640 threads per CU
 // -- this kernel needs 50 KB of LDS -- 4.9 ms: 64 VGPRs are not enough for five keys per lane in two register sets.)
 #define CNT_V3_KEYS 5
 #define CNT_NONE 0xFFFFFFFFu
+// set bits of a ballot below this lane
+__device__ __forceinline__ u32 lanes_below(u64 m) { return __builtin_amdgcn_mbcnt_hi((u32)(m >> 32), __builtin_amdgcn_mbcnt_lo((u32)m, 0u)); }
 // The probe loop is written for the WAVE -- one exit test per round (a ballot), no per-lane loop state: ~30 instructions per round
 // against ~65 of the per-lane loop of table_insert1 (3.98 -> 3.8 ms).  Called under the lanes' own condition: the ballot sees
 // the active ones.  -> the slot if this lane claimed it, else CNT_NONE
@@ -1495,11 +1503,13 @@ __global__ __launch_bounds__(NT) void k_count1v3(u64* keys, u64* solid_keys, u32
     __shared__ u32 tc[CNT_SLOTS];
     __shared__ u32 lh[CNT_LH];
     __shared__ u32 s_ctr[2][4];                 // [parity][ndist, out, ovf]
+    __shared__ unsigned short s_wl[NT / 64][NKEYS * 64];      // per wave: the slots its lanes claimed, dense by rank (the owning wave alone touches it)
     const int tid = threadIdx.x, lane = tid & 63;
+    unsigned short* const wl = s_wl[__builtin_amdgcn_readfirstlane(tid >> 6)];
     for (int s = tid; s < CNT_SLOTS; s += NT) { tk[s] = DSK_EMPTY; tc[s] = 0; }
     for (int b = tid; b < CNT_LH; b += NT) lh[b] = 0;
     if (tid < 8) s_ctr[tid >> 2][tid & 3] = 0;
-    u32 ones = 0;          // lane 0 of each wave: abundance-1 keys seen (flushed at the end)
+    u32 ones = 0;          // abundance-1 keys this wave has seen (wave-uniform; flushed at the end)
     u64 ndist_acc = 0;
     auto range_lo = [&](u32 qq) { const u32 c = qq < cp.F ? qq : cp.F - 1; return subcnt[c]; };
     auto count_of = [&](u32 qq, u32 lo) { return qq < cp.F ? ((int)lo < 0 ? 0u : lo) : 0u; };      // (chained: counted by k_count_chained)
@@ -1531,12 +1541,15 @@ __global__ __launch_bounds__(NT) void k_count1v3(u64* keys, u64* solid_keys, u32
 #pragma unroll
         for (int j = KPT; j < NKEYS; ++j)                // keys past the prefetched ones (n <= cap <= NKEYS * NT)
             if ((u32)(tid + j * NT) < n) cl[j] = table_insert3(tk, tc, &ctr[2], keys[begin + tid + j * NT]);
-        {
-            u32 mine = 0;
+        u32 T = 0;                                           // claims of this wave (wave-uniform); a claim's rank is T so far + the claiming lanes below it
 #pragma unroll
-            for (int j = 0; j < NKEYS; ++j) mine += (u32)__popcll(__ballot(cl[j] != CNT_NONE));
-            if (lane == 0 && mine) atomicAdd(&ctr[0], mine);
+        for (int j = 0; j < NKEYS; ++j) {
+            const bool claim = cl[j] != CNT_NONE;
+            const u64 m = __ballot(claim);
+            if (claim) wl[T + lanes_below(m)] = (unsigned short)cl[j];
+            T += (u32)__popcll(m);
         }
+        if (lane == 0 && T) atomicAdd(&ctr[0], T);
         cur = sub_of(rq, rlo);
         load_keys(cur, pk);
         rq += G; rlo = range_lo(rq);
@@ -1547,18 +1560,16 @@ __global__ __launch_bounds__(NT) void k_count1v3(u64* keys, u64* solid_keys, u32
             for (int s = tid; s < CNT_SLOTS; s += NT) { tk[s] = DSK_EMPTY; tc[s] = 0; }
             if (tid == 0) *overflow = 1;
         } else {
-#pragma unroll
-            for (int j = 0; j < NKEYS; ++j) {
-                const bool act = cl[j] != CNT_NONE;
-                if (!__ballot(act)) continue;                      // (wave-uniform)
+            for (u32 r0 = 0; r0 < T; r0 += 64) {                   // ceil(T / 64) dense passes: lane l sweeps the claim of rank r0 + l
+                const bool act = r0 + lane < T;
                 u64 key = 0; u32 c = 0;
                 if (act) {
-                    const u32 slot = cl[j];
+                    const u32 slot = wl[r0 + lane];
                     key = tk[slot]; c = tc[slot];
                     tk[slot] = DSK_EMPTY; tc[slot] = 0;
                 }
                 const u64 m1 = __ballot(act && c == 1);
-                if (lane == 0) ones += __popcll(m1);
+                ones += __popcll(m1);
                 if (act && c > 1) {
                     const u32 bin = c < cp.histo_max ? c : cp.histo_max;
                     if (bin < CNT_LH) atomicAdd(&lh[bin], 1u);
@@ -1569,7 +1580,7 @@ __global__ __launch_bounds__(NT) void k_count1v3(u64* keys, u64* solid_keys, u32
                 if (ms) {
                     u32 base = 0;
                     if (lane == 0) base = atomicAdd(&ctr[1], (u32)__popcll(ms));
-                    base = __shfl(base, 0);
+                    base = __builtin_amdgcn_readfirstlane(base);       // (the whole wave is here: lane 0 is its first lane)
                     if (solid) {
                         const u32 pos = base + __popcll(ms & ((1ull << lane) - 1));
                         solid_keys[begin + pos] = key;
@@ -1905,11 +1916,13 @@ __global__ __launch_bounds__(NT, 8) void k_count2v3(const K2* __restrict__ keys,
     __shared__ u32 tc[C2V_SLOTS];
     __shared__ u32 lh[CNT_LH];
     __shared__ u32 s_ctr[2][4];                 // [parity][ndist, out, ovf]
+    __shared__ unsigned short s_wl[NT / 64][NKEYS * 64];      // per wave: the slots its lanes claimed, dense by rank (as in k_count1v3; 70 KB of LDS in all)
     const int tid = threadIdx.x, lane = tid & 63;
+    unsigned short* const wl = s_wl[__builtin_amdgcn_readfirstlane(tid >> 6)];
     for (int s = tid; s < C2V_SLOTS; s += NT) { tk[s] = DSK_EMPTY; tc[s] = 0; }
     for (int b = tid; b < CNT_LH; b += NT) lh[b] = 0;
     if (tid < 8) s_ctr[tid >> 2][tid & 3] = 0;
-    u32 ones = 0;
+    u32 ones = 0;          // abundance-1 keys this wave has seen (wave-uniform; flushed at the end)
     u64 ndist_acc = 0;
     auto range_lo = [&](u32 qq) { const u32 c = qq < cp.F ? qq : cp.F - 1; return subcnt[c]; };
     auto count_of = [&](u32 qq, u32 lo) { return qq < cp.F ? ((int)lo < 0 ? 0u : lo) : 0u; };      // (chained: counted by k_count_chained_mw)
@@ -1955,12 +1968,15 @@ __global__ __launch_bounds__(NT, 8) void k_count2v3(const K2* __restrict__ keys,
                 sentinel = sentinel || kx.w[1] == DSK_EMPTY;
             }
         }
-        {
-            u32 mine = 0;
+        u32 T = 0;                                           // claims of this wave (wave-uniform)
 #pragma unroll
-            for (int j = 0; j < NKEYS; ++j) mine += (u32)__popcll(__ballot(at[j] != CNT_NONE && (at[j] >> 31)));
-            if (lane == 0 && mine) atomicAdd(&ctr[0], mine);
+        for (int j = 0; j < NKEYS; ++j) {
+            const bool claim = at[j] != CNT_NONE && (at[j] >> 31);
+            const u64 m = __ballot(claim);
+            if (claim) wl[T + lanes_below(m)] = (unsigned short)(at[j] & 0x7FFFFFFFu);
+            T += (u32)__popcll(m);
         }
+        if (lane == 0 && T) atomicAdd(&ctr[0], T);
         lds_barrier();
         {   // every key against the low word of its slot (the claiming lanes' stores are visible now)
             bool wrong = false;
@@ -1982,18 +1998,16 @@ __global__ __launch_bounds__(NT, 8) void k_count2v3(const K2* __restrict__ keys,
             for (int s = tid; s < C2V_SLOTS; s += NT) { tk[s] = DSK_EMPTY; tc[s] = 0; }
             if (tid == 0) atomicOr(overflow, 1u);
         } else {
-#pragma unroll
-            for (int j = 0; j < NKEYS; ++j) {
-                const bool act = at[j] != CNT_NONE && (at[j] >> 31);
-                if (!__ballot(act)) continue;                      // (wave-uniform)
+            for (u32 r0 = 0; r0 < T; r0 += 64) {                   // ceil(T / 64) dense passes
+                const bool act = r0 + lane < T;
                 u64 top = 0, low = 0; u32 c = 0;
                 if (act) {
-                    const u32 slot = at[j] & 0x7FFFFFFFu;
+                    const u32 slot = wl[r0 + lane];
                     top = tk[slot]; low = tl[slot]; c = tc[slot];
                     tk[slot] = DSK_EMPTY; tc[slot] = 0;
                 }
                 const u64 m1 = __ballot(act && c == 1);
-                if (lane == 0) ones += __popcll(m1);
+                ones += __popcll(m1);
                 if (act && c > 1) {
                     const u32 bin = c < cp.histo_max ? c : cp.histo_max;
                     if (bin < CNT_LH) atomicAdd(&lh[bin], 1u);
@@ -2004,7 +2018,7 @@ __global__ __launch_bounds__(NT, 8) void k_count2v3(const K2* __restrict__ keys,
                 if (ms) {
                     u32 base = 0;
                     if (lane == 0) base = atomicAdd(&ctr[1], (u32)__popcll(ms));
-                    base = __shfl(base, 0);
+                    base = __builtin_amdgcn_readfirstlane(base);       // (the whole wave is here: lane 0 is its first lane)
                     if (solid) {
                         const u32 pos = base + __popcll(ms & ((1ull << lane) - 1));
                         K2 row; row.w[0] = low; row.w[1] = top;
