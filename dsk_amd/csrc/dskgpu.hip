@@ -1863,6 +1863,7 @@ void dskgpu_destroy(dskgpu_ctx* ctx) {
     ctx->sender.release(); ctx->l0_sender.release();
     ctx->query.release();
     ctx->unitigs.release();
+    ctx->threading.release();
     ctx->filtered.release();
     if (ctx->land) (void)hipHostFree(ctx->land);
     for (DevBuf* b : bufs) b->release();

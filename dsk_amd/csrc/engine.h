@@ -6,7 +6,8 @@
 // last result (dskgpu_query_*) and owns dskgpu_ctx::query; graph.hip answers the de Bruijn neighbourhood of k-mers from the same index
 // (dskgpu_graph_*); unitigs.hip compacts the rows' graph into unitigs and links them (dskgpu_unitigs*, dskgpu_unitig_edges*) and owns dskgpu_ctx::unitigs;
 // tips.hip takes rows out of a result (dskgpu_filter_rows) and finds and clips the tips of the compacted graph (dskgpu_graph_tips, dskgpu_clip_tips) and owns dskgpu_ctx::filtered;
-// bubbles.hip finds and pops the simple bubbles with the same rounds (dskgpu_graph_bubbles, dskgpu_pop_bubbles, dskgpu_simplify).  Private to the library.
+// bubbles.hip finds and pops the simple bubbles with the same rounds (dskgpu_graph_bubbles, dskgpu_pop_bubbles, dskgpu_simplify);
+// thread.hip threads reads through the compacted graph (dskgpu_thread_*) and owns dskgpu_ctx::threading.  Private to the library.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -166,6 +167,17 @@ struct Unitigs {
     void invalidate() { stats = dskgpu_unitig_stats{}; e_stats = dskgpu_unitig_edge_stats{}; valid = false; e_valid = false; }      // as Query::invalidate
 };
 
+// Reads threaded through the compacted graph (thread.hip), kept by dskgpu_thread_reads until the rows change: the walks as CSR offsets into
+// steps (n_walks + 1 of them), the first and last stream position and (j(first), j(last)) of every walk, the oriented unitig of every step,
+// and the read support of every unitig and every edge of the compaction the stream was threaded through (n_unitigs, n_edges: theirs).
+struct Threading {
+    DevBuf offsets, steps, first, last, ends, usup, esup;
+    dskgpu_thread_stats stats{};
+    u64 n_unitigs = 0, n_edges = 0;
+    bool valid = false;            // a threading of the current result is kept (dskgpu_ctx::drop_result and dskgpu_filter_rows drop it)
+    void release() { for (DevBuf* b : {&offsets, &steps, &first, &last, &ends, &usup, &esup}) b->release(); stats = dskgpu_thread_stats{}; n_unitigs = n_edges = 0; valid = false; }
+};
+
 // The rows that dskgpu_filter_rows kept (tips.hip): two sets of row arrays, so that a filter of filtered rows reads one set and writes the
 // other; cur = the set res_w / res_ab point into, -1 = the result is still the count's own.  part_off: DSKGPU_F_PARTITION_ORDER, the first
 // kept row of every partition (n_parts + 1 entries) -- rows_partition_range reads them instead of the row sort's while cur >= 0.
@@ -298,10 +310,11 @@ struct dskgpu_ctx {
     std::vector<u64> hist;
     Query query;
     Unitigs unitigs;
+    Threading threading;
     Filtered filtered;
     // a count starts, or its result is not to be read: the index of the old rows and their unitigs go with them, and so does their memory
     // -- up to 32 + 8 bytes per row that the count about to run may need (a no-op for a context that was never queried)
-    void drop_result() { have_result = false; query.release(); unitigs.release(); filtered.release(); }
+    void drop_result() { have_result = false; query.release(); unitigs.release(); threading.release(); filtered.release(); }
     // the read stream changed: what was learnt about the old reads -- their kept encoding apart (enc_keep: the caller's to clear) -- goes
     void reads_changed() { enc_fresh = false; sender.prepared = false; sender.exact = false; opt2_off = false; opt1_off = false; mw_v3_off = false; rec_l0_off = false; last_rows = 0; }
 

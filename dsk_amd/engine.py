@@ -81,6 +81,17 @@ class _UnitigEdgeStats(C.Structure):
     ]
 
 
+class _ThreadStats(C.Structure):
+    _fields_ = [
+        ("n_valid", C.c_uint64),
+        ("n_placed", C.c_uint64),
+        ("n_walks", C.c_uint64),
+        ("n_steps", C.c_uint64),
+        ("max_steps", C.c_uint64),
+        ("reserved", C.c_uint64 * 3),
+    ]
+
+
 class _TipParams(C.Structure):
     _fields_ = [
         ("max_nodes", C.c_uint32),
@@ -166,6 +177,7 @@ EXPORTS = [
     "dskgpu_unitigs", "dskgpu_unitigs_rows", "dskgpu_unitigs_table", "dskgpu_unitigs_stream", "dskgpu_unitig_edges", "dskgpu_unitig_edges_table",
     "dskgpu_filter_rows", "dskgpu_graph_tips", "dskgpu_clip_tips",
     "dskgpu_graph_bubbles", "dskgpu_pop_bubbles", "dskgpu_simplify",
+    "dskgpu_thread_place", "dskgpu_thread_reads", "dskgpu_thread_walks", "dskgpu_thread_support",
     "dskgpu_k_encode", "dskgpu_k_enumerate", "dskgpu_k_minimizers",
     "dskgpu_group_create", "dskgpu_group_destroy", "dskgpu_group_last_error", "dskgpu_group_size", "dskgpu_group_ctx",
     "dskgpu_group_transport", "dskgpu_group_count", "dskgpu_group_exchanged_words", "dskgpu_group_sliced_steps", "dskgpu_group_histogram", "dskgpu_group_histogram2d",
@@ -275,6 +287,14 @@ def load_library():
     lib.dskgpu_pop_bubbles.restype = C.c_int
     lib.dskgpu_simplify.argtypes = [vp, C.POINTER(_TipParams), C.POINTER(_BubbleParams), C.c_uint32, C.POINTER(_SimplifyStats)]
     lib.dskgpu_simplify.restype = C.c_int
+    lib.dskgpu_thread_place.argtypes = [vp, vp, u64, vp, vp]
+    lib.dskgpu_thread_place.restype = C.c_int
+    lib.dskgpu_thread_reads.argtypes = [vp, vp, u64, C.POINTER(_ThreadStats)]
+    lib.dskgpu_thread_reads.restype = C.c_int
+    lib.dskgpu_thread_walks.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.dskgpu_thread_walks.restype = C.c_int
+    lib.dskgpu_thread_support.argtypes = [vp, vp, vp]
+    lib.dskgpu_thread_support.restype = C.c_int
     lib.dskgpu_k_encode.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_enumerate.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_minimizers.argtypes = [vp, vp, u64, vp, vp]
@@ -766,6 +786,89 @@ class KmerCounter:
                 for V in targets[off[U]: off[U + 1]]:
                     f.write("L\t%d\t%s\t%d\t%s\t%s\n" % (U >> 1, "-" if U & 1 else "+", int(V) >> 1, "-" if int(V) & 1 else "+", overlap))
         return {"n_segments": len(seqs), "n_links": int(len(targets))}
+
+    # -- reads threaded through the compacted graph (include/dskgpu.h: dskgpu_thread_*)
+    def thread_place(self, d_bytes: int, nbytes: int, d_unitig: int, d_off: int) -> None:
+        """d_bytes: a read stream on the device; d_unitig / d_off: nbytes u32 each on the device <- the oriented unitig U(p) = 2 u + t and the
+        offset j(p) of the window ending at every byte, 0xFFFFFFFF / 0 where the window is not placed; either may be 0."""
+        self._ck(self._lib.dskgpu_thread_place(self._h, C.c_void_p(d_bytes) if d_bytes else None, nbytes, C.c_void_p(d_unitig) if d_unitig else None,
+                                               C.c_void_p(d_off) if d_off else None))
+
+    def thread_reads(self, d_bytes: int, nbytes: int) -> dict:
+        """Thread the stream through the compacted graph of the last result and keep the walks and the supports in the context -> the stats:
+        n_valid, n_placed, n_walks, n_steps, max_steps."""
+        st = _ThreadStats()
+        self._ck(self._lib.dskgpu_thread_reads(self._h, C.c_void_p(d_bytes) if d_bytes else None, nbytes, C.byref(st)))
+        self._thread_stats = {name: int(getattr(st, name)) for name, _ in _ThreadStats._fields_ if name != "reserved"}
+        return dict(self._thread_stats)
+
+    def thread_walks(self, d_offsets: int, d_steps: int, d_first: int, d_last: int, d_ends: int) -> None:
+        """d_offsets: n_walks + 1 u64 (CSR into the steps), d_steps: n_steps u32, d_first / d_last: n_walks u64, d_ends: 2 * n_walks u32
+        (j(first), j(last)), all on the device; any may be 0."""
+        self._ck(self._lib.dskgpu_thread_walks(self._h, *(C.c_void_p(p) if p else None for p in (d_offsets, d_steps, d_first, d_last, d_ends))))
+
+    def thread_support(self, d_unitig_support: int, d_edge_support: int) -> None:
+        """d_unitig_support: n_unitigs u64, d_edge_support: n_edges u64 (the entries of unitig_edges_table), on the device; either may be 0."""
+        self._ck(self._lib.dskgpu_thread_support(self._h, *(C.c_void_p(p) if p else None for p in (d_unitig_support, d_edge_support))))
+
+    def thread_place_tensor(self, stream):
+        """stream: CUDA uint8 tensor holding a read stream.  -> (int32[nbytes] U(p), int32[nbytes] j(p)); -1 / 0 where the window is not placed."""
+        import torch
+        if not stream.is_cuda or stream.dtype != torch.uint8:
+            raise ValueError("thread_place_tensor: a CUDA uint8 tensor is needed")
+        stream = stream.contiguous()
+        n = stream.numel()
+        U, j = torch.full((n,), -1, dtype=torch.int32, device=stream.device), torch.zeros(n, dtype=torch.int32, device=stream.device)
+        torch.cuda.current_stream(stream.device).synchronize()      # the context's stream is not torch's: what torch enqueued is done before the kernel runs
+        self.thread_place(stream.data_ptr() if n else 0, n, U.data_ptr() if n else 0, j.data_ptr() if n else 0)
+        return U, j
+
+    def thread_reads_tensor(self, stream) -> dict:
+        """stream: CUDA uint8 tensor holding a read stream.  -> the stats of thread_reads; the tables: thread_walks_tensor, thread_support_tensor."""
+        import torch
+        if not stream.is_cuda or stream.dtype != torch.uint8:
+            raise ValueError("thread_reads_tensor: a CUDA uint8 tensor is needed")
+        stream = stream.contiguous()
+        torch.cuda.current_stream(stream.device).synchronize()
+        return self.thread_reads(stream.data_ptr() if stream.numel() else 0, stream.numel())
+
+    def thread_walks_tensor(self):
+        """-> (int64[n_walks + 1] CSR offsets, int32[n_steps] oriented unitigs, int64[n_walks] first, int64[n_walks] last,
+        int32[n_walks, 2] (j(first), j(last))), CUDA tensors, of the threading the last thread_reads of this object kept (its stats size
+        the tensors; when the library has dropped the threading since, the call raises DSKGPU_E_STATE)."""
+        import torch
+        st = getattr(self, "_thread_stats", None) or {"n_walks": 0, "n_steps": 0}
+        nw, ns = st["n_walks"], st["n_steps"]
+        dev = torch.device("cuda", self.device)
+        off, steps = torch.zeros(nw + 1, dtype=torch.int64, device=dev), torch.zeros(ns, dtype=torch.int32, device=dev)
+        first, last = torch.zeros(nw, dtype=torch.int64, device=dev), torch.zeros(nw, dtype=torch.int64, device=dev)
+        ends = torch.zeros((nw, 2), dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()              # the context's stream is not torch's: the zero fill is done before the copies write
+        self.thread_walks(off.data_ptr(), steps.data_ptr() if ns else 0, first.data_ptr() if nw else 0, last.data_ptr() if nw else 0,
+                          ends.data_ptr() if nw else 0)
+        return off, steps, first, last, ends
+
+    def thread_support_tensor(self):
+        """-> (int64[n_unitigs] placed positions per unitig, int64[n_edges] edge steps per entry of unitig_edges_tensor's table), CUDA tensors."""
+        import torch
+        ne = self.unitig_edges()["n_edges"]
+        nu = self.unitigs()["n_unitigs"]
+        dev = torch.device("cuda", self.device)
+        usup, esup = torch.zeros(max(nu, 1), dtype=torch.int64, device=dev), torch.zeros(max(ne, 1), dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        self.thread_support(usup.data_ptr(), esup.data_ptr())
+        return usup[:nu], esup[:ne]
+
+    def write_gfa_walks(self, path: str) -> dict:
+        """write_gfa, followed by one P line per walk of the kept threading: P <TAB> w<i> <TAB> <u>+,<u>-,... <TAB> *.
+        -> dict(n_segments, n_links, n_paths)."""
+        out = self.write_gfa(path)
+        off, steps, _, _, _ = (t.cpu().numpy() for t in self.thread_walks_tensor())
+        with open(path, "a") as f:
+            for w in range(len(off) - 1):
+                f.write("P\tw%d\t%s\t*\n" % (w, ",".join("%d%s" % (int(U) >> 1, "-" if int(U) & 1 else "+") for U in steps[off[w]: off[w + 1]])))
+        out["n_paths"] = int(len(off) - 1)
+        return out
 
     # -- rows out of a result, and the tips of the compacted graph (include/dskgpu.h: dskgpu_filter_rows / _graph_tips / _clip_tips)
     def filter_rows(self, d_keep: int) -> int:

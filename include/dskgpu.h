@@ -530,6 +530,61 @@ int dskgpu_pop_bubbles(dskgpu_ctx* ctx, const dskgpu_bubble_params* params, dskg
  * Errors: those of the two calls, checked for both sets of parameters before anything runs. */
 int dskgpu_simplify(dskgpu_ctx* ctx, const dskgpu_tip_params* tip_params, const dskgpu_bubble_params* bubble_params, uint32_t max_passes, dskgpu_simplify_stats* stats);
 
+/* ---- reads threaded through the compacted graph: the way back from reads to the graph that the calls above build and clean -- what
+ * Minia's contig stage, the users of BCALM / Bandage and every repeat resolution ask next: where on the graph does this read lie, and which
+ * edges does it walk?  A count at k gives the abundance of the nodes; an edge U -> V is a (k+1)-mer, so its read support needs the reads.
+ * In the notation of the unitig and edge sections (row r, oriented node o = 2 r + s, oriented unitig U = 2 u + t, first(U), last(U), E(U),
+ * L[u] = the rows of u) and with text(U) = the sequence of u as dskgpu_unitigs_stream gives it for t = 0, its reverse complement for t = 1:
+ *   PLACEMENT  of byte position p of a read stream (the input convention above, any alignment): the window ending at p is PLACED when it is
+ *              valid (exactly dskgpu_k_enumerate's validity) and its canonical k-mer is a row r of the current result.  Its node is
+ *              o(p) = 2 r + s, s = 0 when the window read forward equals the canonical string (a row that is its own reverse complement:
+ *              always s = 0), else s = 1.  With unitig[r] = u and pos[r] = (i << 1) | s_r (dskgpu_unitigs_rows): U(p) = 2 u, j(p) = i when
+ *              s == s_r, else U(p) = 2 u + 1, j(p) = L[u] - 1 - i; a palindromic row has U(p) = 2 u, j(p) = 0.  Equivalently:
+ *              text(U(p))[j(p) .. j(p) + k) is the window in upper case, and of the two readings of a palindrome's unitig the even one is
+ *              named.  Not placed: U = 0xFFFFFFFF, j = 0.
+ *   WALK       a maximal run of consecutive placed positions first .. last: it never crosses a byte that ends a window, nor a k-mer that is
+ *              no row.  Inside a walk, position p > first is an EDGE STEP when j(p) == 0, else an INSIDE STEP.  From the link rules: an inside
+ *              step has U(p) = U(p - 1) and j(p) = j(p - 1) + 1; an edge step has j(p - 1) = L[U(p - 1) >> 1] - 1 and U(p) in E(U(p - 1)) --
+ *              also at the closing edge 2u -> 2u of a cycle, the self edge of poly-A, the hairpin U -> U ^ 1 at odd k, and into and out of a
+ *              palindrome's unitig through its even reading.  The device checks that U(p) is among the at most 4 targets of U(p - 1); a miss
+ *              is DSKGPU_E_DEVICE, an internal error, as the edge build does for its own fact.
+ *   STEPS      of a walk: U(first) followed by U(p) of every edge step, in order.  Its windows number last - first + 1 =
+ *              sum of L[U_i >> 1] - j(first) - (L[U_m >> 1] - 1 - j(last)); the steps' texts glued with k - 1 letters of overlap, j(first)
+ *              letters cut at the front and L - 1 - j(last) at the back, are the stream's bytes first - k + 1 .. last in upper case.  This
+ *              is what GFA calls a path.
+ *   SUPPORT    unitig_support[u] = placed positions with U(p) >> 1 == u; edge_support[e] = edge steps whose (U(p - 1), U(p)) is entry e of
+ *              the CSR table of dskgpu_unitig_edges_table.
+ * Both builders (dskgpu_thread_place, dskgpu_thread_reads) build the edges, the compaction and the lookup index when they are not there,
+ * run on the context's stream, are synchronous on return and leave the reads (a kept encoding included), the result, the stats and the
+ * sender state alone.  Positions, walks and steps are 64-bit counts; there is no cap on nbytes.  Stage times: "thread place" and "thread
+ * walks", plus those of what the call built.
+ * Memory: dskgpu_thread_reads takes, and frees before it returns, the 2-bit form of the stream (0.375 bytes per stream byte) + 8 bytes per
+ * stream byte for the placements (+ 48 bytes per 1024 stream bytes of block sums); what it keeps is 32 bytes per walk, 4 per step, 8 per
+ * unitig and 8 per edge.  A stream too big for the free HBM can be threaded in pieces cut behind any byte that ends a window (a '\n'):
+ * walks never cross one, so the pieces' walks concatenate -- first / last shifted by the bytes before the piece -- and the supports add.
+ * Errors: a null ctx, a null d_bytes with nbytes > 0: DSKGPU_E_ARG; no result DSKGPU_E_STATE; a context with world_size > 1 DSKGPU_E_STATE
+ * and more than 2^31 - 1 rows DSKGPU_E_STATE (the text says so, as for the unitigs); a table call when no threading is kept DSKGPU_E_STATE;
+ * DSKGPU_E_NOMEM leaves the context, its result and what was built before usable.  nbytes == 0: DSKGPU_OK, nothing is done, all-zero
+ * stats, and the table calls after it write d_offsets[0] = 0 only.  A result with zero rows places nothing: n_valid is still counted,
+ * there are no walks. */
+typedef struct dskgpu_thread_stats {
+    uint64_t n_valid, n_placed, n_walks, n_steps, max_steps, reserved[3];
+} dskgpu_thread_stats;                                   /* 64 bytes; valid windows, placed positions, walks, steps, the most steps of one walk */
+/* Stateless, like dskgpu_query_reads: d_unitig u32[nbytes] = U(p), d_off u32[nbytes] = j(p), on the device.  Either may be NULL; both NULL:
+ * DSKGPU_E_ARG. */
+int dskgpu_thread_place(dskgpu_ctx* ctx, const void* d_bytes, uint64_t nbytes, void* d_unitig, void* d_off);
+/* Thread the stream and keep the walks, the steps, both supports and the stats in the context, as the compaction is kept: dropped by the
+ * next count, by dskgpu_filter_rows (and so by dskgpu_clip_tips / _pop_bubbles / _simplify), by the next dskgpu_thread_reads and by
+ * dskgpu_destroy.  stats may be NULL. */
+int dskgpu_thread_reads(dskgpu_ctx* ctx, const void* d_bytes, uint64_t nbytes, dskgpu_thread_stats* stats);
+/* The kept walks, on the device, numbered by ascending first: d_offsets u64[n_walks + 1] (CSR into the steps; d_offsets[n_walks] = n_steps),
+ * d_steps u32[n_steps], d_first / d_last u64[n_walks], d_ends u32[2 * n_walks] = (j(first), j(last)) of every walk.  Any may be NULL; all
+ * NULL: DSKGPU_E_ARG. */
+int dskgpu_thread_walks(dskgpu_ctx* ctx, void* d_offsets, void* d_steps, void* d_first, void* d_last, void* d_ends);
+/* The kept supports, on the device: d_unitig_support u64[n_unitigs], d_edge_support u64[n_edges].  Either may be NULL; both NULL:
+ * DSKGPU_E_ARG. */
+int dskgpu_thread_support(dskgpu_ctx* ctx, void* d_unitig_support, void* d_edge_support);
+
 /* ---- the same call on N GPUs of one node, inside ONE process (what `dsk -nb-gpus N` runs): the reference's
  * single `execute()` (src/DSK.cpp:55-60) still leaves ONE storage with a flat list of solid partitions
  * (utils/dsk2ascii.cpp:61,77).  A group owns one ctx per rank (world_size = n_ranks, rank r on devices[r], its own
