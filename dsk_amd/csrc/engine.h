@@ -7,7 +7,9 @@
 // (dskgpu_graph_*); unitigs.hip compacts the rows' graph into unitigs and links them (dskgpu_unitigs*, dskgpu_unitig_edges*) and owns dskgpu_ctx::unitigs;
 // tips.hip takes rows out of a result (dskgpu_filter_rows) and finds and clips the tips of the compacted graph (dskgpu_graph_tips, dskgpu_clip_tips) and owns dskgpu_ctx::filtered;
 // bubbles.hip finds and pops the simple bubbles with the same rounds (dskgpu_graph_bubbles, dskgpu_pop_bubbles, dskgpu_simplify);
-// thread.hip threads reads through the compacted graph (dskgpu_thread_*) and owns dskgpu_ctx::threading.  Private to the library.
+// thread.hip threads reads through the compacted graph (dskgpu_thread_*) and owns dskgpu_ctx::threading;
+// components.hip labels the connected components of the compacted graph and takes the small ones out (dskgpu_components*, dskgpu_graph_small_components,
+// dskgpu_drop_components) and owns dskgpu_ctx::unitigs.cc.  Private to the library.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -78,6 +80,7 @@ struct Tuning {
     u32 mp_pass_mkeys = 0;                      // DSKGPU_MP_PASS_MKEYS: keys (millions) per pass of an input that needs several passes (default 1000)
     u64 rs_slab_rows = 0;                       // DSKGPU_RS_SLAB_ROWS: rows per slab of the row sort for >= 2^32 rows (tests: forces that path, with small slabs, on a small input)
     bool unitig_stages = false;                 // DSKGPU_UNITIG_STAGES: the build of the unitigs marks "unitig links" / "unitig ranking" / "unitig numbering" instead of "unitigs" (tools/bench_unitigs.py)
+    bool cc_plain = false, cc_stages = false;   // DSKGPU_CC_PLAIN: the component table by one add per unitig and column instead of the wave-combined form; DSKGPU_CC_STAGES: the build of the components marks "component labelling" / "component numbering" / "component table" instead of "components" (tools/bench_components.py)
     void read() {
         auto on = [](const char* n) { return getenv(n) != nullptr; };
         auto num = [](const char* n, u64 dflt) { const char* e = getenv(n); return e ? (u64)atoll(e) : dflt; };
@@ -91,6 +94,7 @@ struct Tuning {
         no_sample = on("DSKGPU_NO_SAMPLE"); no_heavy = on("DSKGPU_NO_HEAVY"); verbose = on("DSKGPU_VERBOSE"); no_level0 = on("DSKGPU_NO_LEVEL0"); l0_passes = (u32)num("DSKGPU_L0_PASSES", 0); mp_pass_mkeys = (u32)num("DSKGPU_MP_PASS_MKEYS", 0); rs_max_rows = num("DSKGPU_RS_MAX_ROWS", 0); l0_keys = on("DSKGPU_L0_KEYS"); sk_generic = on("DSKGPU_SK_GENERIC"); ps_maxc = (u32)num("DSKGPU_PS_MAXC", 0);
         rs_slab_rows = num("DSKGPU_RS_SLAB_ROWS", 0);
         unitig_stages = on("DSKGPU_UNITIG_STAGES");
+        cc_plain = on("DSKGPU_CC_PLAIN"); cc_stages = on("DSKGPU_CC_STAGES");
         rs_block_rows = (u32)num("DSKGPU_RS_BLOCK_ROWS", 0); rs_bbits = (u32)num("DSKGPU_RS_BBITS", 0); rs_heavy = (u32)num("DSKGPU_RS_HEAVY", 0);
     }
 };
@@ -155,16 +159,28 @@ struct Query {
 // number and (position << 1 | orientation), per unitig the stream offset (n_unitigs + 1 of them), the abundance sum and the kind.
 // The edges between the unitigs, built on the first dskgpu_unitig_edges* call on top of the compaction: per oriented unitig U = 2 u + t its
 // last node (ends) and the CSR offset of its targets (e_offsets, 2 n_unitigs + 1 of them), per edge the oriented unitig it leads to.
+// The connected components of that graph (components.hip), built on the first dskgpu_components* call on top of the edges and kept with them:
+// per unitig its component, per component its smallest unitig (first) and the four columns of the table, cols[col * n_components + c] with
+// col = unitigs, rows, ab_sum, edges.  4 bytes per unitig + 36 per component.
+struct Components {
+    DevBuf comp, first, cols;
+    dskgpu_component_stats stats{};
+    bool valid = false;            // they are those of the edges of the current result
+    void release() { for (DevBuf* b : {&comp, &first, &cols}) b->release(); stats = dskgpu_component_stats{}; valid = false; }
+    void invalidate() { stats = dskgpu_component_stats{}; valid = false; }
+};
+
 struct Unitigs {
     DevBuf unitig, pos, offsets, ab_sum, kind;
     DevBuf ends, e_offsets, e_targets;
+    Components cc;                 // (they go wherever the edges go)
     dskgpu_unitig_stats stats{};
     dskgpu_unitig_edge_stats e_stats{};
     bool valid = false;            // they compact the current result (dskgpu_ctx::drop_result clears it)
     bool e_valid = false;          // ... and the edges are those of that compaction
-    void release_edges() { for (DevBuf* b : {&ends, &e_offsets, &e_targets}) b->release(); e_stats = dskgpu_unitig_edge_stats{}; e_valid = false; }
+    void release_edges() { for (DevBuf* b : {&ends, &e_offsets, &e_targets}) b->release(); e_stats = dskgpu_unitig_edge_stats{}; e_valid = false; cc.release(); }
     void release() { for (DevBuf* b : {&unitig, &pos, &offsets, &ab_sum, &kind}) b->release(); stats = dskgpu_unitig_stats{}; valid = false; release_edges(); }
-    void invalidate() { stats = dskgpu_unitig_stats{}; e_stats = dskgpu_unitig_edge_stats{}; valid = false; e_valid = false; }      // as Query::invalidate
+    void invalidate() { stats = dskgpu_unitig_stats{}; e_stats = dskgpu_unitig_edge_stats{}; valid = false; e_valid = false; cc.invalidate(); }      // as Query::invalidate
 };
 
 // Reads threaded through the compacted graph (thread.hip), kept by dskgpu_thread_reads until the rows change: the walks as CSR offsets into

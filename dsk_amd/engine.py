@@ -144,6 +144,35 @@ class _SimplifyStats(C.Structure):
     ]
 
 
+class _ComponentStats(C.Structure):
+    _fields_ = [
+        ("n_components", C.c_uint64),
+        ("n_single", C.c_uint64),
+        ("max_unitigs", C.c_uint64),
+        ("max_rows", C.c_uint64),
+        ("n_rounds", C.c_uint64),
+        ("reserved", C.c_uint64 * 3),
+    ]
+
+
+class _ComponentParams(C.Structure):
+    _fields_ = [
+        ("min_rows", C.c_uint32),
+        ("max_abundance", C.c_uint32),
+        ("reserved", C.c_uint32 * 6),
+    ]
+
+
+class _ComponentDropStats(C.Structure):
+    _fields_ = [
+        ("n_small", C.c_uint64),
+        ("n_unitigs_dropped", C.c_uint64),
+        ("n_rows_dropped", C.c_uint64),
+        ("n_rows_left", C.c_uint64),
+        ("reserved", C.c_uint64 * 4),
+    ]
+
+
 MG_BUCKETS = 4096      # DSKGPU_MG_BUCKETS
 MG_SPLIT = 255         # DSKGPU_MG_SPLIT
 
@@ -177,6 +206,7 @@ EXPORTS = [
     "dskgpu_unitigs", "dskgpu_unitigs_rows", "dskgpu_unitigs_table", "dskgpu_unitigs_stream", "dskgpu_unitig_edges", "dskgpu_unitig_edges_table",
     "dskgpu_filter_rows", "dskgpu_graph_tips", "dskgpu_clip_tips",
     "dskgpu_graph_bubbles", "dskgpu_pop_bubbles", "dskgpu_simplify",
+    "dskgpu_components", "dskgpu_components_labels", "dskgpu_components_table", "dskgpu_graph_small_components", "dskgpu_drop_components",
     "dskgpu_thread_place", "dskgpu_thread_reads", "dskgpu_thread_walks", "dskgpu_thread_support",
     "dskgpu_k_encode", "dskgpu_k_enumerate", "dskgpu_k_minimizers",
     "dskgpu_group_create", "dskgpu_group_destroy", "dskgpu_group_last_error", "dskgpu_group_size", "dskgpu_group_ctx",
@@ -287,6 +317,16 @@ def load_library():
     lib.dskgpu_pop_bubbles.restype = C.c_int
     lib.dskgpu_simplify.argtypes = [vp, C.POINTER(_TipParams), C.POINTER(_BubbleParams), C.c_uint32, C.POINTER(_SimplifyStats)]
     lib.dskgpu_simplify.restype = C.c_int
+    lib.dskgpu_components.argtypes = [vp, C.POINTER(_ComponentStats)]
+    lib.dskgpu_components.restype = C.c_int
+    lib.dskgpu_components_labels.argtypes = [vp, vp, vp]
+    lib.dskgpu_components_labels.restype = C.c_int
+    lib.dskgpu_components_table.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.dskgpu_components_table.restype = C.c_int
+    lib.dskgpu_graph_small_components.argtypes = [vp, C.POINTER(_ComponentParams), vp, vp, C.POINTER(_ComponentDropStats)]
+    lib.dskgpu_graph_small_components.restype = C.c_int
+    lib.dskgpu_drop_components.argtypes = [vp, C.POINTER(_ComponentParams), C.POINTER(_ComponentDropStats)]
+    lib.dskgpu_drop_components.restype = C.c_int
     lib.dskgpu_thread_place.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_thread_place.restype = C.c_int
     lib.dskgpu_thread_reads.argtypes = [vp, vp, u64, C.POINTER(_ThreadStats)]
@@ -978,6 +1018,78 @@ class KmerCounter:
         st = _SimplifyStats()
         self._ck(self._lib.dskgpu_simplify(self._h, C.byref(tp) if tp is not None else None, C.byref(bp) if bp is not None else None, max_passes, C.byref(st)))
         return {"n_passes": int(st.n_passes), "n_rows_left": int(st.n_rows_left), "tips": self._tip_stats(st.tips), "bubbles": self._bubble_stats(st.bubbles)}
+
+    # -- the connected components of the compacted graph (include/dskgpu.h: dskgpu_components* / _graph_small_components / _drop_components)
+    @staticmethod
+    def _drop_stats(st) -> dict:
+        return {name: int(getattr(st, name)) for name, _ in _ComponentDropStats._fields_ if name != "reserved"}
+
+    def components(self) -> dict:
+        """Build the components of the last result's compacted graph (the edges, the compaction and the index too when they are not there)
+        -> the stats: n_components, n_single, max_unitigs, max_rows, n_rounds (launches of the labelling)."""
+        st = _ComponentStats()
+        self._ck(self._lib.dskgpu_components(self._h, C.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in _ComponentStats._fields_ if name != "reserved"}
+
+    def components_labels(self, d_unitig_comp: int, d_row_comp: int) -> None:
+        """d_unitig_comp: n_unitigs u32 on the device <- the component of every unitig; d_row_comp: n_rows u32 <- that of every row's unitig;
+        either may be 0."""
+        self._ck(self._lib.dskgpu_components_labels(self._h, C.c_void_p(d_unitig_comp) if d_unitig_comp else None, C.c_void_p(d_row_comp) if d_row_comp else None))
+
+    def components_labels_tensor(self):
+        """-> (int32[n_unitigs] component of every unitig, int32[n_rows] component of every row), CUDA tensors."""
+        import torch
+        nu = self.unitigs()["n_unitigs"]
+        n = self.result_device()[2]
+        dev = torch.device("cuda", self.device)
+        ucomp, rcomp = torch.zeros(max(nu, 1), dtype=torch.int32, device=dev), torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()              # the context's stream is not torch's: the zero fill is done before the kernels write
+        self.components_labels(ucomp.data_ptr(), rcomp.data_ptr())
+        return ucomp[:nu], rcomp[:n]
+
+    def components_table(self, d_first: int, d_unitigs: int, d_rows: int, d_ab_sum: int, d_edges: int) -> None:
+        """d_first: n_components u32 (the smallest unitig of every component), d_unitigs / d_rows / d_ab_sum / d_edges: n_components u64 each,
+        on the device; any may be 0."""
+        self._ck(self._lib.dskgpu_components_table(self._h, *(C.c_void_p(p) if p else None for p in (d_first, d_unitigs, d_rows, d_ab_sum, d_edges))))
+
+    def components_table_tensor(self):
+        """-> (int32[n_c] first, int64[n_c] unitigs, int64[n_c] rows, int64[n_c] ab_sum, int64[n_c] edges), CUDA tensors."""
+        import torch
+        nc = self.components()["n_components"]
+        dev = torch.device("cuda", self.device)
+        first = torch.zeros(max(nc, 1), dtype=torch.int32, device=dev)
+        cols = [torch.zeros(max(nc, 1), dtype=torch.int64, device=dev) for _ in range(4)]
+        torch.cuda.current_stream(dev).synchronize()
+        self.components_table(first.data_ptr(), *(c.data_ptr() for c in cols))
+        return (first[:nc],) + tuple(c[:nc] for c in cols)
+
+    def small_components(self, min_rows: int, max_abundance: int = 0, d_row_drop: int = 0, d_comp_small: int = 0) -> dict:
+        """The small-component rule on the last result, which stays as it is: a component is small when it has fewer than min_rows rows and
+        (max_abundance == 0 or its mean abundance is at most max_abundance).  d_row_drop: n_rows bytes on the device <- 1 = the row's
+        component is small; d_comp_small: n_components bytes <- 1 = small; either may be 0.  -> n_small, n_unitigs_dropped, n_rows_dropped,
+        n_rows_left."""
+        par, st = _ComponentParams(min_rows=min_rows, max_abundance=max_abundance), _ComponentDropStats()
+        self._ck(self._lib.dskgpu_graph_small_components(self._h, C.byref(par), C.c_void_p(d_row_drop) if d_row_drop else None,
+                                                         C.c_void_p(d_comp_small) if d_comp_small else None, C.byref(st)))
+        return self._drop_stats(st)
+
+    def small_components_tensor(self, min_rows: int, max_abundance: int = 0):
+        """-> (uint8[n_rows] the row's component is small, uint8[n_components] small, the stats of small_components), CUDA tensors."""
+        import torch
+        nc = self.components()["n_components"]
+        n = self.result_device()[2]
+        dev = torch.device("cuda", self.device)
+        row_drop, comp_small = torch.zeros(n, dtype=torch.uint8, device=dev), torch.zeros(nc, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()              # the context's stream is not torch's: the zero fill is done before the kernels write
+        st = self.small_components(min_rows, max_abundance, row_drop.data_ptr() if n else 0, comp_small.data_ptr() if nc else 0)
+        return row_drop, comp_small, st
+
+    def drop_components(self, min_rows: int, max_abundance: int = 0) -> dict:
+        """Take the rows of the small components out of the result (one filter_rows; one application is final).  On return the unitigs, the
+        edges and the components of the rows left are built.  -> n_small, n_unitigs_dropped, n_rows_dropped, n_rows_left."""
+        par, st = _ComponentParams(min_rows=min_rows, max_abundance=max_abundance), _ComponentDropStats()
+        self._ck(self._lib.dskgpu_drop_components(self._h, C.byref(par), C.byref(st)))
+        return self._drop_stats(st)
 
     # -- kernel-level entry points (parity tests)
     def k_encode(self, d_bytes: int, nbytes: int, d_packed: int, d_invalid: int) -> None:

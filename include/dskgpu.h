@@ -530,6 +530,69 @@ int dskgpu_pop_bubbles(dskgpu_ctx* ctx, const dskgpu_bubble_params* params, dskg
  * Errors: those of the two calls, checked for both sets of parameters before anything runs. */
 int dskgpu_simplify(dskgpu_ctx* ctx, const dskgpu_tip_params* tip_params, const dskgpu_bubble_params* bubble_params, uint32_t max_passes, dskgpu_simplify_stats* stats);
 
+/* ---- connected components: the first GLOBAL question about the graph -- which pieces does it fall into, and how big is each?  Every call
+ * above looks at one unitig and its neighbours.  Clipping and popping leave small isolated pieces behind -- chains of error k-mers that hang on
+ * nothing, short contaminant fragments: neither tips (an isolated unitig is never clipped) nor bubbles --, which every assembler removes by
+ * size right after tips and bubbles; and a metagenome or transcriptome graph is processed, drawn and binned piece by piece, from one
+ * component label per unitig.  Exact integer arithmetic; in the notation of the unitig, edge and tip sections (unitig u, readings U = 2u + t,
+ * E(U), L[u], S[u] = ab_sum[u]):
+ *   JOINED     u ~ v <=> some entry of the CSR table of dskgpu_unitig_edges_table has source U and target V with U >> 1 == u and V >> 1 == v.
+ *              Every entry counts in both directions; self edges join nothing.
+ *   SYMMETRY   for every entry U -> V there is an entry from a reading of v to a reading of u: outside the unitigs of palindromes this is
+ *              the last fact of the edge section (flip(V) -> flip(U)); for an edge into a palindrome's unitig 2v, both readings of v have
+ *              the successors of the one node, and one of them is first(U ^ 1).  The device treats every entry as undirected and does not
+ *              need it.
+ *   COMPONENT  a class of the reflexive-transitive closure of ~; its LABEL is the smallest unitig number in it.  Components are numbered
+ *              0 .. n_components - 1 by ascending label, first[c].  A cycle unitig with no other edge, a palindrome without neighbours and
+ *              every other isolated unitig is a component by itself.
+ *   TABLE      per component c: unitigs[c] = its unitigs, rows[c] = the sum of their L[u], ab_sum[c] = the sum of their S[u] (exact in 64
+ *              bits), edges[c] = the CSR entries whose source lies in c, self edges included.  The columns add up to n_unitigs, n_rows, the
+ *              sum of all abundances and n_edges.  The bases of a component are rows[c] + (k - 1) * unitigs[c].
+ *   SMALL      small[c] <=> rows[c] < min_rows && (max_abundance == 0 || ab_sum[c] <= (uint64_t)max_abundance * rows[c]).  min_rows counts
+ *              k-mers and is at least 1; rows[c] < 2^31, so the product stays inside 64 bits.
+ * The row order changes the numbering, never the partition of the k-mers; nothing depends on it otherwise.
+ * ONE APPLICATION IS FINAL: removing whole components changes no adjacency byte of any kept row, so the unitigs, the edges and the
+ * components of the kept rows are exactly the old ones that were not small, renumbered; a second application removes nothing; there are no
+ * rounds.
+ * The labelling is a lock-free union-find that hooks the larger root under the smaller, so the labels do not depend on scheduling, and it is
+ * three launches whatever the graph (set the parents, hook, flatten): there is no round count to bound, n_rounds is always 3 (0 for a result
+ * without rows).  A walk that does not end within 4 * n_unitigs + 64 steps -- none can -- is DSKGPU_E_DEVICE, an internal error.
+ * The components are kept in the context with the edges (4 bytes per unitig + 36 per component; 12 bytes per unitig more, and the scan's
+ * scratch, while they are built): built on first use by any of the five calls -- which build the edges, the compaction and the lookup index
+ * below them when they are not there yet --, dropped or invalidated wherever the edges are: when the next count starts, by
+ * dskgpu_filter_rows (and so by dskgpu_clip_tips / _pop_bubbles / _simplify) and by dskgpu_destroy.  The calls run on the context's stream, are
+ * synchronous on return and change nothing else in the context: the reads (a kept encoding included), the result, the stats and the sender
+ * state stay as they are.  Stage times: "components" (the build), "component rows" (d_row_comp), "small components", "filter rows", and
+ * those of what a call built below them.
+ * Errors: a null ctx DSKGPU_E_ARG; no result DSKGPU_E_STATE; more than 2^31 - 1 rows DSKGPU_E_STATE; a context with world_size > 1
+ * DSKGPU_E_STATE (the text names world_size): a rank's unitigs are not the group's; DSKGPU_E_NOMEM leaves the context, its result and what
+ * was built before usable.  A result with zero rows: all-zero stats, nothing is written. */
+typedef struct dskgpu_component_stats {
+    uint64_t n_components, n_single, max_unitigs, max_rows, n_rounds, reserved[3];
+} dskgpu_component_stats;                                /* 64 bytes; n_single: components of one unitig; max_*: the most unitigs / rows of one component; n_rounds: launches of the labelling */
+typedef struct dskgpu_component_params {
+    uint32_t min_rows, max_abundance, reserved[6];
+} dskgpu_component_params;                               /* 32 bytes; min_rows >= 1, max_abundance 0 = no limit */
+typedef struct dskgpu_component_drop_stats {
+    uint64_t n_small, n_unitigs_dropped, n_rows_dropped, n_rows_left, reserved[4];
+} dskgpu_component_drop_stats;                           /* 64 bytes */
+/* Build the components now (optional) and fill `stats` (may be NULL). */
+int dskgpu_components(dskgpu_ctx* ctx, dskgpu_component_stats* stats);
+/* On the device: d_unitig_comp u32[n_unitigs] = the component of every unitig, d_row_comp u32[n_rows] = that of every row's unitig (result
+ * order).  Either may be NULL; both NULL: DSKGPU_E_ARG. */
+int dskgpu_components_labels(dskgpu_ctx* ctx, void* d_unitig_comp, void* d_row_comp);
+/* The table, on the device: d_first u32[n_components], the four columns u64[n_components] each.  Any may be NULL; all NULL: DSKGPU_E_ARG. */
+int dskgpu_components_table(dskgpu_ctx* ctx, void* d_first, void* d_unitigs, void* d_rows, void* d_ab_sum, void* d_edges);
+/* The rule on the current result; no row changes.  d_row_drop u8[n_rows]: 1 = the row's component is small; d_comp_small u8[n_components]:
+ * 1 = small; stats: the small components, their unitigs and rows, n_rows_left = n_rows - n_rows_dropped.  Any may be NULL; all three NULL, a
+ * NULL params or min_rows == 0: DSKGPU_E_ARG. */
+int dskgpu_graph_small_components(dskgpu_ctx* ctx, const dskgpu_component_params* params, void* d_row_drop, void* d_comp_small, dskgpu_component_drop_stats* stats);
+/* Mark the small components, take their rows out with one dskgpu_filter_rows and leave the compaction, the edges and the components of the
+ * FINAL rows built, like dskgpu_clip_tips.  When nothing is small nothing is filtered and nothing invalidated.  What dskgpu_filter_rows says
+ * about the count's stats, the histogram, the partitions of either row order and a kept threading holds here.  stats (may be NULL): what was
+ * dropped, n_rows_left = the final n_rows.  Errors: those of dskgpu_graph_small_components. */
+int dskgpu_drop_components(dskgpu_ctx* ctx, const dskgpu_component_params* params, dskgpu_component_drop_stats* stats);
+
 /* ---- reads threaded through the compacted graph: the way back from reads to the graph that the calls above build and clean -- what
  * Minia's contig stage, the users of BCALM / Bandage and every repeat resolution ask next: where on the graph does this read lie, and which
  * edges does it walk?  A count at k gives the abundance of the nodes; an edge U -> V is a (k+1)-mer, so its read support needs the reads.
