@@ -9,7 +9,8 @@
 // bubbles.hip finds and pops the simple bubbles with the same rounds (dskgpu_graph_bubbles, dskgpu_pop_bubbles, dskgpu_simplify);
 // thread.hip threads reads through the compacted graph (dskgpu_thread_*) and owns dskgpu_ctx::threading;
 // components.hip labels the connected components of the compacted graph and takes the small ones out (dskgpu_components*, dskgpu_graph_small_components,
-// dskgpu_drop_components) and owns dskgpu_ctx::unitigs.cc.  Private to the library.
+// dskgpu_drop_components) and owns dskgpu_ctx::unitigs.cc;
+// correct.hip corrects substitution errors in a read stream against the rows (dskgpu_correct_reads) and keeps nothing.  Private to the library.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -81,6 +82,7 @@ struct Tuning {
     u64 rs_slab_rows = 0;                       // DSKGPU_RS_SLAB_ROWS: rows per slab of the row sort for >= 2^32 rows (tests: forces that path, with small slabs, on a small input)
     bool unitig_stages = false;                 // DSKGPU_UNITIG_STAGES: the build of the unitigs marks "unitig links" / "unitig ranking" / "unitig numbering" instead of "unitigs" (tools/bench_unitigs.py)
     bool cc_plain = false, cc_stages = false;   // DSKGPU_CC_PLAIN: the component table by one add per unitig and column instead of the wave-combined form; DSKGPU_CC_STAGES: the build of the components marks "component labelling" / "component numbering" / "component table" instead of "components" (tools/bench_components.py)
+    bool correct_staged = false;                // DSKGPU_CORRECT_STAGED: the trials of dskgpu_correct_reads by the staged pair (one window of every alternative as a batch, then a wave per surviving candidate) instead of one thread per candidate, which is the default because it measured faster (profiles/read_correction.md; tests, tools/bench_correct.py)
     void read() {
         auto on = [](const char* n) { return getenv(n) != nullptr; };
         auto num = [](const char* n, u64 dflt) { const char* e = getenv(n); return e ? (u64)atoll(e) : dflt; };
@@ -95,6 +97,7 @@ struct Tuning {
         rs_slab_rows = num("DSKGPU_RS_SLAB_ROWS", 0);
         unitig_stages = on("DSKGPU_UNITIG_STAGES");
         cc_plain = on("DSKGPU_CC_PLAIN"); cc_stages = on("DSKGPU_CC_STAGES");
+        correct_staged = on("DSKGPU_CORRECT_STAGED");
         rs_block_rows = (u32)num("DSKGPU_RS_BLOCK_ROWS", 0); rs_bbits = (u32)num("DSKGPU_RS_BBITS", 0); rs_heavy = (u32)num("DSKGPU_RS_HEAVY", 0);
     }
 };

@@ -92,6 +92,30 @@ class _ThreadStats(C.Structure):
     ]
 
 
+class _CorrectParams(C.Structure):
+    _fields_ = [
+        ("trust_min", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint64 * 3),
+    ]
+
+
+class _CorrectStats(C.Structure):
+    _fields_ = [
+        ("n_valid", C.c_uint64),
+        ("n_trusted", C.c_uint64),
+        ("n_gaps", C.c_uint64),
+        ("n_interior", C.c_uint64),
+        ("n_head", C.c_uint64),
+        ("n_tail", C.c_uint64),
+        ("n_skipped", C.c_uint64),
+        ("n_corrected", C.c_uint64),
+        ("n_ambiguous", C.c_uint64),
+        ("n_unfixable", C.c_uint64),
+        ("reserved", C.c_uint64 * 6),
+    ]
+
+
 class _TipParams(C.Structure):
     _fields_ = [
         ("max_nodes", C.c_uint32),
@@ -208,6 +232,7 @@ EXPORTS = [
     "dskgpu_graph_bubbles", "dskgpu_pop_bubbles", "dskgpu_simplify",
     "dskgpu_components", "dskgpu_components_labels", "dskgpu_components_table", "dskgpu_graph_small_components", "dskgpu_drop_components",
     "dskgpu_thread_place", "dskgpu_thread_reads", "dskgpu_thread_walks", "dskgpu_thread_support",
+    "dskgpu_correct_reads",
     "dskgpu_k_encode", "dskgpu_k_enumerate", "dskgpu_k_minimizers",
     "dskgpu_group_create", "dskgpu_group_destroy", "dskgpu_group_last_error", "dskgpu_group_size", "dskgpu_group_ctx",
     "dskgpu_group_transport", "dskgpu_group_count", "dskgpu_group_exchanged_words", "dskgpu_group_sliced_steps", "dskgpu_group_histogram", "dskgpu_group_histogram2d",
@@ -335,6 +360,8 @@ def load_library():
     lib.dskgpu_thread_walks.restype = C.c_int
     lib.dskgpu_thread_support.argtypes = [vp, vp, vp]
     lib.dskgpu_thread_support.restype = C.c_int
+    lib.dskgpu_correct_reads.argtypes = [vp, vp, u64, C.POINTER(_CorrectParams), vp, vp, C.POINTER(_CorrectStats)]
+    lib.dskgpu_correct_reads.restype = C.c_int
     lib.dskgpu_k_encode.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_enumerate.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_minimizers.argtypes = [vp, vp, u64, vp, vp]
@@ -909,6 +936,32 @@ class KmerCounter:
                 f.write("P\tw%d\t%s\t*\n" % (w, ",".join("%d%s" % (int(U) >> 1, "-" if int(U) & 1 else "+") for U in steps[off[w]: off[w + 1]])))
         out["n_paths"] = int(len(off) - 1)
         return out
+
+    # -- substitution errors in reads corrected against the result (include/dskgpu.h: dskgpu_correct_reads)
+    def correct_reads(self, d_bytes: int, nbytes: int, d_out: int = 0, d_state: int = 0, trust_min: int = 0) -> dict:
+        """d_bytes: a read stream on the device.  d_out: nbytes u8 on the device <- the stream with every corrected byte replaced (may equal
+        d_bytes: in place; 0: a dry run).  d_state: nbytes u8 <- 0 / 1 / 2 = no valid window / not trusted / trusted at every byte of the
+        INPUT; may be 0.  trust_min: the abundance from which a row is trusted (0, 1: any row).  One substitution per gap of k untrusted
+        windows; nothing else is corrected.  -> the stats: n_valid, n_trusted, n_gaps, n_interior, n_head, n_tail, n_skipped, n_corrected,
+        n_ambiguous, n_unfixable."""
+        par, st = _CorrectParams(trust_min=trust_min), _CorrectStats()
+        self._ck(self._lib.dskgpu_correct_reads(self._h, C.c_void_p(d_bytes) if d_bytes else None, nbytes, C.byref(par), C.c_void_p(d_out) if d_out else None,
+                                                C.c_void_p(d_state) if d_state else None, C.byref(st)))
+        return {name: int(getattr(st, name)) for name, _ in _CorrectStats._fields_ if name != "reserved"}
+
+    def correct_reads_tensor(self, t, trust_min: int = 0, want_state: bool = False):
+        """t: CUDA uint8 tensor holding a read stream (left as it is).  -> (uint8[nbytes] the corrected stream, the stats of correct_reads
+        [, uint8[nbytes] the states of the input])."""
+        import torch
+        if not t.is_cuda or t.dtype != torch.uint8:
+            raise ValueError("correct_reads_tensor: a CUDA uint8 tensor is needed")
+        t = t.contiguous()
+        n = t.numel()
+        out = torch.empty_like(t)
+        state = torch.zeros(n, dtype=torch.uint8, device=t.device) if want_state else None
+        torch.cuda.current_stream(t.device).synchronize()          # the context's stream is not torch's: what torch enqueued is done before the kernels run
+        st = self.correct_reads(t.data_ptr() if n else 0, n, out.data_ptr() if n else 0, state.data_ptr() if want_state and n else 0, trust_min)
+        return (out, st, state) if want_state else (out, st)
 
     # -- rows out of a result, and the tips of the compacted graph (include/dskgpu.h: dskgpu_filter_rows / _graph_tips / _clip_tips)
     def filter_rows(self, d_keep: int) -> int:

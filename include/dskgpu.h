@@ -648,6 +648,48 @@ int dskgpu_thread_walks(dskgpu_ctx* ctx, void* d_offsets, void* d_steps, void* d
  * DSKGPU_E_ARG. */
 int dskgpu_thread_support(dskgpu_ctx* ctx, void* d_unitig_support, void* d_edge_support);
 
+/* ---- substitution errors in reads corrected against the count: the other use of a k-mer spectrum (what Bloocoo does with the output of a
+ * count).  The rows of the current result are the trusted set: after dskgpu_filter_rows / _simplify / _drop_components, the rows left.
+ *   STATE      Positions and validity are those of dskgpu_query_reads / dskgpu_k_enumerate.  The window ending at byte p is TRUSTED when it
+ *              is valid, its canonical k-mer is a row, and that row's abundance is >= trust_min (0 and 1: any row).  state(p) = 0: no valid
+ *              window ends at p; 1: valid, not trusted; 2: trusted.
+ *   GAP        a maximal run [a, b] of positions of state 1, m = b - a + 1 windows.  A gap lies inside one run of bases, so the two positions
+ *              beside it decide its SHAPE and its candidate byte e:
+ *                interior  state(a - 1) == 2, state(b + 1) == 2 and m == k                              e = a
+ *                head      state(a - 1) == 0 (or a == 0), state(b + 1) == 2 and m <= k                  e = b - k + 1
+ *                tail      state(a - 1) == 2, state(b + 1) == 0 (or b is the last byte) and m <= k      e = a
+ *                skipped   anything else: m > k, an interior gap shorter than k, no trusted neighbour   none
+ *              In the three shaped cases the windows that contain byte e are exactly the windows of the gap.
+ *   TRIAL      For each of the three bases x other than the one at e, put x at e: x WORKS when every window ending in [a, b] is then
+ *              trusted.  Exactly one x works: the gap is CORRECTED, byte e becomes the letter of x in the case of the byte it replaces
+ *              (letter | (old & 0x20)).  More than one: AMBIGUOUS.  None: UNFIXABLE.  Nothing is written in either case.
+ * All gaps are judged against the INPUT stream and applied together.  They cannot interact: a window of one gap never contains the
+ * candidate byte of another, and the states beside a gap belong to no gap.  So the result does not depend on order or scheduling, and one
+ * application is final: correcting the corrected stream corrects nothing and reports the same ambiguous, unfixable and skipped gaps.
+ * Limits: substitutions only, one per gap.  Indels, two errors inside one gap (closer than k: one long gap, skipped) and quality values are
+ * out of scope.  One context: a rank of a group holds only the k-mers it owns, which are not the trusted set.
+ * d_bytes: the stream on the device, any alignment.  params: NULL = the defaults (trust_min 0); flags and reserved must be 0.  d_out:
+ * u8[nbytes] on the device, any alignment: the input with the corrected bytes replaced and every other byte copied; it may equal d_bytes
+ * (in place; any other overlap is undefined) or be NULL (a dry run: statistics and states only).  d_state: u8[nbytes] or NULL: state(p) of
+ * the INPUT.  stats: may be NULL.  n_valid / n_trusted: positions of state >= 1 / of state 2; n_gaps = n_interior + n_head + n_tail +
+ * n_skipped; n_interior + n_head + n_tail = n_corrected + n_ambiguous + n_unfixable.
+ * Like dskgpu_query_reads the call is stateless, synchronous on return, runs on the context's stream, builds the lookup index on first
+ * use and encodes the stream into buffers of its own (freed before it returns: 1.375 bytes per stream byte + 25 per candidate); it touches
+ * neither the reads of the context, nor the result, the stats or any graph state.  Every k in 1..128, either row order, several passes.
+ * Stage times: "correct states", "correct gaps", "correct trials" (+ "query index").
+ * Errors: a null ctx, a null d_bytes with nbytes > 0, non-zero flags or reserved words, a stream longer than one launch of the read frame
+ * takes (as dskgpu_query_reads): DSKGPU_E_ARG; no result DSKGPU_E_STATE; a context with world_size > 1 DSKGPU_E_STATE (the text says so);
+ * DSKGPU_E_NOMEM leaves everything usable.  nbytes == 0: DSKGPU_OK, all-zero stats.  A result with zero rows: every valid window is state
+ * 1, nothing is corrected. */
+typedef struct dskgpu_correct_params {
+    uint32_t trust_min, flags; uint64_t reserved[3];
+} dskgpu_correct_params;                                 /* 32 bytes; flags and reserved must be 0 */
+typedef struct dskgpu_correct_stats {
+    uint64_t n_valid, n_trusted, n_gaps, n_interior, n_head, n_tail, n_skipped, n_corrected, n_ambiguous, n_unfixable, reserved[6];
+} dskgpu_correct_stats;                                  /* 128 bytes */
+int dskgpu_correct_reads(dskgpu_ctx* ctx, const void* d_bytes, uint64_t nbytes, const dskgpu_correct_params* params, void* d_out, void* d_state,
+                         dskgpu_correct_stats* stats);
+
 /* ---- the same call on N GPUs of one node, inside ONE process (what `dsk -nb-gpus N` runs): the reference's
  * single `execute()` (src/DSK.cpp:55-60) still leaves ONE storage with a flat list of solid partitions
  * (utils/dsk2ascii.cpp:61,77).  A group owns one ctx per rank (world_size = n_ranks, rank r on devices[r], its own
