@@ -19,14 +19,9 @@ int bubbles_enqueue(dskgpu_ctx* ctx, const dskgpu_bubble_params& p, unsigned cha
     Filtered& F = ctx->filtered;
     const Unitigs& U = ctx->unitigs;
     const u64 nu = U.stats.n_unitigs;
-    if (const int rc = query_ensure(ctx, F.ends, nu * 8, "bubble ends")) return rc;
-    if (const int rc = query_ensure(ctx, F.len, nu * 4, "bubble lengths")) return rc;
+    if (const int rc = bubble_candidates(ctx, p.max_nodes)) return rc;
     if (const int rc = query_ensure(ctx, F.bits, nu, "bubble bits")) return rc;
-    const dim3 ugrid(blocks(nu, 256));
-    hipLaunchKernelGGL(k_bubble_candidates, ugrid, dim3(256), 0, ctx->stream, U.offsets.as<u64>(), U.kind.as<unsigned char>(), U.e_offsets.as<u64>(), U.e_targets.as<u32>(), nu,
-                       U.e_stats.n_edges, (int)ctx->cfg.kmer_size, p.max_nodes, F.ends.as<u64>(), F.len.as<u32>());
-    CKL("k_bubble_candidates");
-    hipLaunchKernelGGL(k_bubble_decide, ugrid, dim3(256), 0, ctx->stream, F.ends.as<u64>(), F.len.as<u32>(), U.ab_sum.as<u64>(), U.e_offsets.as<u64>(), U.e_targets.as<u32>(), nu,
+    hipLaunchKernelGGL(k_bubble_decide, dim3(blocks(nu, 256)), dim3(256), 0, ctx->stream, F.ends.as<u64>(), F.len.as<u32>(), U.ab_sum.as<u64>(), U.e_offsets.as<u64>(), U.e_targets.as<u32>(), nu,
                        U.e_stats.n_edges, p.max_diff, F.bits.as<unsigned char>(), F.rec.as<u64>());
     CKL("k_bubble_decide");
     return flag_rows(ctx, d_row_pop, want_keep);
@@ -44,6 +39,19 @@ void add_round(dskgpu_bubble_stats& t, const u64* h) {
 }
 
 }  // namespace
+
+// enqueue the candidates of the current result, whose edges are there: Filtered::ends and ::len of every unitig.  variants.hip starts from them too
+int bubble_candidates(dskgpu_ctx* ctx, u32 max_nodes) {
+    Filtered& F = ctx->filtered;
+    const Unitigs& U = ctx->unitigs;
+    const u64 nu = U.stats.n_unitigs;
+    if (const int rc = query_ensure(ctx, F.ends, nu * 8, "bubble ends")) return rc;
+    if (const int rc = query_ensure(ctx, F.len, nu * 4, "bubble lengths")) return rc;
+    hipLaunchKernelGGL(k_bubble_candidates, dim3(blocks(nu, 256)), dim3(256), 0, ctx->stream, U.offsets.as<u64>(), U.kind.as<unsigned char>(), U.e_offsets.as<u64>(), U.e_targets.as<u32>(), nu,
+                       U.e_stats.n_edges, (int)ctx->cfg.kmer_size, max_nodes, F.ends.as<u64>(), F.len.as<u32>());
+    CKL("k_bubble_candidates");
+    return DSKGPU_OK;
+}
 
 extern "C" {
 

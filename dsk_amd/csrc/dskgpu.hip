@@ -1864,6 +1864,7 @@ void dskgpu_destroy(dskgpu_ctx* ctx) {
     ctx->query.release();
     ctx->unitigs.release();
     ctx->threading.release();
+    ctx->variants.release();
     ctx->filtered.release();
     if (ctx->land) (void)hipHostFree(ctx->land);
     for (DevBuf* b : bufs) b->release();

@@ -10,7 +10,8 @@
 // thread.hip threads reads through the compacted graph (dskgpu_thread_*) and owns dskgpu_ctx::threading;
 // components.hip labels the connected components of the compacted graph and takes the small ones out (dskgpu_components*, dskgpu_graph_small_components,
 // dskgpu_drop_components) and owns dskgpu_ctx::unitigs.cc;
-// correct.hip corrects substitution errors in a read stream against the rows (dskgpu_correct_reads) and keeps nothing.  Private to the library.
+// correct.hip corrects substitution errors in a read stream against the rows (dskgpu_correct_reads) and keeps nothing;
+// variants.hip reports the bubbles as pairs of sequences (dskgpu_variants*) and owns dskgpu_ctx::variants.  Private to the library.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -197,6 +198,15 @@ struct Threading {
     void release() { for (DevBuf* b : {&offsets, &steps, &first, &last, &ends, &usup, &esup}) b->release(); stats = dskgpu_thread_stats{}; n_unitigs = n_edges = 0; valid = false; }
 };
 
+// The bubbles of the compacted graph reported as variants (variants.hip), kept by dskgpu_variants until the rows change: the records (8 x u32
+// per variant), the offsets of the 2 n_variants lines of the variant stream (+ 1) and the stream itself.  32 + 16 bytes per variant + the stream.
+struct Variants {
+    DevBuf rec, off, stream;
+    dskgpu_variant_stats stats{};
+    bool valid = false;            // the variants of the current result are kept (dskgpu_ctx::drop_result and dskgpu_filter_rows drop them)
+    void release() { for (DevBuf* b : {&rec, &off, &stream}) b->release(); stats = dskgpu_variant_stats{}; valid = false; }
+};
+
 // The rows that dskgpu_filter_rows kept (tips.hip): two sets of row arrays, so that a filter of filtered rows reads one set and writes the
 // other; cur = the set res_w / res_ab point into, -1 = the result is still the count's own.  part_off: DSKGPU_F_PARTITION_ORDER, the first
 // kept row of every partition (n_parts + 1 entries) -- rows_partition_range reads them instead of the row sort's while cur >= 0.
@@ -330,10 +340,11 @@ struct dskgpu_ctx {
     Query query;
     Unitigs unitigs;
     Threading threading;
+    Variants variants;
     Filtered filtered;
     // a count starts, or its result is not to be read: the index of the old rows and their unitigs go with them, and so does their memory
     // -- up to 32 + 8 bytes per row that the count about to run may need (a no-op for a context that was never queried)
-    void drop_result() { have_result = false; query.release(); unitigs.release(); threading.release(); filtered.release(); }
+    void drop_result() { have_result = false; query.release(); unitigs.release(); threading.release(); variants.release(); filtered.release(); }
     // the read stream changed: what was learnt about the old reads -- their kept encoding apart (enc_keep: the caller's to clear) -- goes
     void reads_changed() { enc_fresh = false; sender.prepared = false; sender.exact = false; opt2_off = false; opt1_off = false; mw_v3_off = false; rec_l0_off = false; last_rows = 0; }
 
@@ -427,3 +438,6 @@ int read_record(dskgpu_ctx* ctx, std::vector<u64>& h, u64 n_off);      // the ro
 int filter_apply(dskgpu_ctx* ctx, const unsigned char* keep, const u64* new_off, u64 n_off);      // the kept rows become the result
 // per row, bit 1 of Filtered::bits of its unitig -> d_row_flag (may be null) and, with want_keep, its complement -> Filtered::keep
 int flag_rows(dskgpu_ctx* ctx, unsigned char* d_row_flag, bool want_keep);
+
+// bubbles.hip
+int bubble_candidates(dskgpu_ctx* ctx, u32 max_nodes);   // enqueue k_bubble_candidates on the current result, whose edges are there: Filtered::ends / ::len

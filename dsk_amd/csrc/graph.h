@@ -139,6 +139,16 @@ __device__ __forceinline__ void graph_adj(const QTable& T, const KN<W> (&x)[R], 
     }
 }
 
+// the two bits of base j (0 = last base) of x, and the letter of a code: what unitigs.h and variants.h write sequences with
+template <int W> __device__ __forceinline__ u32 u_base(const KN<W>& x, int j) {
+    const int wi = (2 * j) >> 6;
+    u64 word = x.w[0];
+#pragma unroll
+    for (int q = 1; q < W; ++q) word = (wi == q) ? x.w[q] : word;
+    return (u32)(word >> ((2 * j) & 63)) & 3u;
+}
+__device__ __forceinline__ unsigned char u_letter(u32 code) { return (unsigned char)(0x47544341u >> (8u * code)); }      // "ACTG"
+
 // A block takes 256 * R consecutive rows, thread t of it the rows t, t + 256, ...: a wave reads 64 neighbouring words of every word
 // array and writes 64 neighbouring bytes.  d_adj may be null (degree table only), deg may be null (bytes only).  The degree table is
 // counted per block in LDS and leaves as one vector atomic add per non-zero cell and block.

@@ -69,16 +69,6 @@ template <int W> __device__ __forceinline__ bool u_same(const KN<W>& a, const KN
     for (int i = 0; i < W; ++i) eq = eq && a.w[i] == b.w[i];
     return eq;
 }
-// the two bits of base j (0 = last base) of x
-template <int W> __device__ __forceinline__ u32 u_base(const KN<W>& x, int j) {
-    const int wi = (2 * j) >> 6;
-    u64 word = x.w[0];
-#pragma unroll
-    for (int q = 1; q < W; ++q) word = (wi == q) ? x.w[q] : word;
-    return (u32)(word >> ((2 * j) & 63)) & 3u;
-}
-__device__ __forceinline__ unsigned char u_letter(u32 code) { return (unsigned char)(0x47544341u >> (8u * code)); }      // "ACTG"
-
 template <int W>
 __global__ __launch_bounds__(256) void k_unitig_links(RowsIn rows, u64 n, int k, QTable T, const unsigned char* __restrict__ adj,
                                                       u32* __restrict__ nxt, u64* __restrict__ P) {

@@ -168,6 +168,30 @@ class _SimplifyStats(C.Structure):
     ]
 
 
+class _VariantParams(C.Structure):
+    _fields_ = [
+        ("max_nodes", C.c_uint32),
+        ("max_diff", C.c_uint32),
+        ("reserved", C.c_uint32 * 6),
+    ]
+
+
+class _VariantStats(C.Structure):
+    _fields_ = [
+        ("n_variants", C.c_uint64),
+        ("n_snps", C.c_uint64),
+        ("n_multi", C.c_uint64),
+        ("n_indels", C.c_uint64),
+        ("n_complex", C.c_uint64),
+        ("n_unitigs", C.c_uint64),
+        ("stream_bytes", C.c_uint64),
+        ("max_letters", C.c_uint64),
+    ]
+
+
+VARIANT_KINDS = {1: "SNP", 2: "MULTI", 3: "INDEL", 4: "COMPLEX"}      # kind of a variant record (include/dskgpu.h: "variant reporting")
+
+
 class _ComponentStats(C.Structure):
     _fields_ = [
         ("n_components", C.c_uint64),
@@ -233,6 +257,7 @@ EXPORTS = [
     "dskgpu_components", "dskgpu_components_labels", "dskgpu_components_table", "dskgpu_graph_small_components", "dskgpu_drop_components",
     "dskgpu_thread_place", "dskgpu_thread_reads", "dskgpu_thread_walks", "dskgpu_thread_support",
     "dskgpu_correct_reads",
+    "dskgpu_variants", "dskgpu_variants_table", "dskgpu_variants_stream",
     "dskgpu_k_encode", "dskgpu_k_enumerate", "dskgpu_k_minimizers",
     "dskgpu_group_create", "dskgpu_group_destroy", "dskgpu_group_last_error", "dskgpu_group_size", "dskgpu_group_ctx",
     "dskgpu_group_transport", "dskgpu_group_count", "dskgpu_group_exchanged_words", "dskgpu_group_sliced_steps", "dskgpu_group_histogram", "dskgpu_group_histogram2d",
@@ -352,6 +377,12 @@ def load_library():
     lib.dskgpu_graph_small_components.restype = C.c_int
     lib.dskgpu_drop_components.argtypes = [vp, C.POINTER(_ComponentParams), C.POINTER(_ComponentDropStats)]
     lib.dskgpu_drop_components.restype = C.c_int
+    lib.dskgpu_variants.argtypes = [vp, C.POINTER(_VariantParams), C.POINTER(_VariantStats)]
+    lib.dskgpu_variants.restype = C.c_int
+    lib.dskgpu_variants_table.argtypes = [vp, vp]
+    lib.dskgpu_variants_table.restype = C.c_int
+    lib.dskgpu_variants_stream.argtypes = [vp, vp, vp, u64]
+    lib.dskgpu_variants_stream.restype = C.c_int
     lib.dskgpu_thread_place.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_thread_place.restype = C.c_int
     lib.dskgpu_thread_reads.argtypes = [vp, vp, u64, C.POINTER(_ThreadStats)]
@@ -1071,6 +1102,70 @@ class KmerCounter:
         st = _SimplifyStats()
         self._ck(self._lib.dskgpu_simplify(self._h, C.byref(tp) if tp is not None else None, C.byref(bp) if bp is not None else None, max_passes, C.byref(st)))
         return {"n_passes": int(st.n_passes), "n_rows_left": int(st.n_rows_left), "tips": self._tip_stats(st.tips), "bubbles": self._bubble_stats(st.bubbles)}
+
+    # -- the bubbles of the compacted graph reported as variants (include/dskgpu.h: dskgpu_variants / _variants_table / _variants_stream)
+    def variants(self, max_nodes: Optional[int] = None, max_diff: int = 4) -> dict:
+        """Find the variants of the last result -- the pairs of sibling unitigs of the bubble rule -- and keep their records and their
+        stream in the context; the result stays as it is.  max_nodes None = 2 * kmer_size.  -> the stats: n_variants, n_snps, n_multi,
+        n_indels, n_complex, n_unitigs (the unitigs in a variant), stream_bytes, max_letters (the longest text compared)."""
+        par, st = _VariantParams(max_nodes=2 * self.kmer_size if max_nodes is None else max_nodes, max_diff=max_diff), _VariantStats()
+        self._ck(self._lib.dskgpu_variants(self._h, C.byref(par), C.byref(st)))
+        self._variant_stats = {name: int(getattr(st, name)) for name, _ in _VariantStats._fields_}
+        return dict(self._variant_stats)
+
+    def variants_table(self, d_records: int) -> None:
+        """d_records: 8 * n_variants u32 on the device <- A, B, from, to, lcp, lcs, n_mismatch, kind of every kept variant."""
+        self._ck(self._lib.dskgpu_variants_table(self._h, C.c_void_p(d_records) if d_records else None))
+
+    def variants_stream(self, d_offsets: int, d_bytes: int, capacity: int = 0) -> None:
+        """d_offsets: 2 * n_variants + 1 u64 on the device <- the first byte of every line of the variant stream (the last: stream_bytes);
+        d_bytes: capacity bytes <- text(A) '\\n' text(B) '\\n' of every kept variant; either may be 0."""
+        self._ck(self._lib.dskgpu_variants_stream(self._h, C.c_void_p(d_offsets) if d_offsets else None, C.c_void_p(d_bytes) if d_bytes else None, capacity))
+
+    def variants_tensor(self):
+        """-> int64[n_variants, 8] (A, B, from, to, lcp, lcs, n_mismatch, kind), a CUDA tensor, of the variants the last variants() of this
+        object kept (its stats size the tensor; when the library has dropped them since, the call raises DSKGPU_E_STATE)."""
+        import torch
+        n = (getattr(self, "_variant_stats", None) or {"n_variants": 0})["n_variants"]
+        dev = torch.device("cuda", self.device)
+        rec = torch.zeros((max(n, 1), 8), dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()              # the context's stream is not torch's: the zero fill is done before the copy writes
+        self.variants_table(rec.data_ptr())
+        return rec[:n].to(torch.int64) & 0xFFFFFFFF
+
+    def variants_stream_tensor(self):
+        """-> (int64[2 * n_variants + 1] line offsets, uint8[stream_bytes] the variant stream), CUDA tensors, of the kept variants."""
+        import torch
+        st = getattr(self, "_variant_stats", None) or {"n_variants": 0, "stream_bytes": 0}
+        n, nb = st["n_variants"], st["stream_bytes"]
+        dev = torch.device("cuda", self.device)
+        off, text = torch.zeros(2 * n + 1, dtype=torch.int64, device=dev), torch.zeros(max(nb, 1), dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        self.variants_stream(off.data_ptr(), text.data_ptr(), nb)
+        return off, text[:nb]
+
+    def write_variants(self, path: str) -> dict:
+        """The kept variants as FASTA, two records per variant:
+        >v<i>|a|<KIND>|<u>+ from=<U> to=<U> L=<nodes> S=<abundance sum> lcp=<n> lcs=<n> n_mismatch=<n>
+        and the same with |b| and the oriented unitig of the second branch, oriented unitigs in GFA style (17+ / 17-).
+        -> dict(n_variants, n_snps, n_multi, n_indels, n_complex)."""
+        rec = self.variants_tensor().cpu().numpy()
+        off, text = (t.cpu().numpy() for t in self.variants_stream_tensor())
+        offsets, ab_sum, _ = (t.cpu().numpy() for t in self.unitigs_table_tensor())
+        nodes = np.diff(offsets.astype(np.int64)) - self.kmer_size
+        raw = text.tobytes()
+
+        def gfa(U):
+            return "%d%s" % (int(U) >> 1, "-" if int(U) & 1 else "+")
+
+        with open(path, "w") as f:
+            for i, (A, B, frm, to, lcp, lcs, nm, kind) in enumerate(rec.tolist()):
+                for j, (side, U) in enumerate((("a", A), ("b", B))):
+                    f.write(">v%d|%s|%s|%s from=%s to=%s L=%d S=%d lcp=%d lcs=%d n_mismatch=%d\n" % (
+                        i, side, VARIANT_KINDS[kind], gfa(U), gfa(frm), gfa(to), int(nodes[U >> 1]), int(ab_sum[U >> 1]), lcp, lcs, nm))
+                    f.write(raw[int(off[2 * i + j]): int(off[2 * i + j + 1]) - 1].decode() + "\n")
+        st = self._variant_stats
+        return {name: st[name] for name in ("n_variants", "n_snps", "n_multi", "n_indels", "n_complex")}
 
     # -- the connected components of the compacted graph (include/dskgpu.h: dskgpu_components* / _graph_small_components / _drop_components)
     @staticmethod

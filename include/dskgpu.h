@@ -648,6 +648,49 @@ int dskgpu_thread_walks(dskgpu_ctx* ctx, void* d_offsets, void* d_steps, void* d
  * DSKGPU_E_ARG. */
 int dskgpu_thread_support(dskgpu_ctx* ctx, void* d_unitig_support, void* d_edge_support);
 
+/* ---- variant reporting: the bubbles of the compacted graph as pairs of sequences -- what DiscoSnp does on top of a GATB count.  The bubble
+ * rule finds every pair of parallel branches between the same two ends; dskgpu_pop_bubbles can only delete the weaker one.  These calls say
+ * which unitig is whose sibling, in which reading the two run in parallel, and what differs between them.  They read the tables the bubble
+ * rule reads and keep its definitions word for word; exact integer arithmetic, nothing depends on the row order except the numbering.  In
+ * the notation of the tip and bubble sections (L[u], S[u], U = 2u + t, E(U), cand, in(u), out(u)) and with text(U) of the threading section,
+ * with parameters max_nodes and max_diff:
+ *   VARIANT    an unordered pair of unitigs a < b in which b is a SIBLING of a by the bubble rule (siblinghood is symmetric).  Each pair is
+ *              reported once, so a three-way bubble gives three variants.
+ *   READINGS   from = in(a) ^ 1 and to = out(a); A = 2a; B = the X in E(from) with X >> 1 == b -- the reading in which `from` reaches b,
+ *              read off the tables as they are (palindromes get no special case).
+ *   ORDER      variants are numbered by ascending (a, b).
+ *   DIFFERENCE text(A) and text(B), of na = k + L[a] - 1 and nb = k + L[b] - 1 letters, compared in full: lcp = the length of the longest
+ *              common prefix (<= min(na, nb)); lcs = the length of the longest common suffix, capped at min(na, nb) - lcp (the usual
+ *              left-aligned trimming; the cap bites for an indel inside a run or tandem repeat).  L[a] == L[b]: n_mismatch = the Hamming
+ *              distance, kind = 1 (SNP) when it is 1, kind = 2 (MULTI) when it is 2 or more; it cannot be 0, equal texts would be the
+ *              same rows.  L[a] != L[b]: n_mismatch = 0, kind = 3 (INDEL) when lcp + lcs == min(na, nb), else kind = 4 (COMPLEX: a
+ *              substitution next to an indel).
+ *   RECORD     eight u32 (32 bytes) per variant: A, B, from, to, lcp, lcs, n_mismatch, kind.
+ *   STREAM     for variant i: text(A_i) '\n' text(B_i) '\n' -- a read stream by the input convention; offsets u64[2 * n_variants + 1] = the
+ *              first byte of every line, the last entry = stream_bytes = sum(L[a] + L[b]) + 2 * n_variants * k.  Counting the stream at k
+ *              with abundance_min = 1 gives exactly the rows of the unitigs that are in some variant, each with abundance = the number of
+ *              variants its unitig is in.
+ * dskgpu_variants finds the variants of the current result, which stays untouched, and keeps the records, the stream and the stats in the
+ * context, the way a threading is kept (48 bytes per variant + the stream; while it runs, 33 bytes per unitig, 16 per variant and one byte
+ * per letter of the unitigs in a variant -- the whole unitig stream is never made): dropped by the next count, by dskgpu_filter_rows (and so by
+ * dskgpu_clip_tips / _pop_bubbles / _simplify / _drop_components), by the next dskgpu_variants and by dskgpu_destroy.  It builds the edges,
+ * the compaction and the lookup index when they are not there, and leaves alone the reads (a kept encoding included), the result, the stats,
+ * the sender state and a kept threading.  stats (may be NULL): n_unitigs = the unitigs in at least one variant (n_in_bubbles of
+ * dskgpu_graph_bubbles with the same parameters), max_letters = the longest text compared.  Runs on the context's stream, synchronous on
+ * return.  Stage time: "variants" (and those of what the call built).
+ * Errors, as for dskgpu_graph_bubbles: a null ctx or params, max_nodes 0 or > 65535: DSKGPU_E_ARG; no result DSKGPU_E_STATE; a context with
+ * world_size > 1 DSKGPU_E_STATE (the text names world_size); more than 2^31 - 1 rows DSKGPU_E_STATE; a copy call when nothing is kept
+ * DSKGPU_E_STATE; DSKGPU_E_NOMEM leaves the context, its result and what was built before usable.  A result with zero rows, or zero
+ * variants: all-zero stats, and the copy calls write d_offsets[0] = 0 and nothing else. */
+typedef struct dskgpu_variant_params { uint32_t max_nodes, max_diff, reserved[6]; } dskgpu_variant_params;   /* 32 bytes; as dskgpu_bubble_params */
+typedef struct dskgpu_variant_stats  { uint64_t n_variants, n_snps, n_multi, n_indels, n_complex, n_unitigs, stream_bytes, max_letters; } dskgpu_variant_stats; /* 64 bytes */
+int dskgpu_variants(dskgpu_ctx* ctx, const dskgpu_variant_params* params, dskgpu_variant_stats* stats);
+/* The kept records, on the device: d_records u32[8 * n_variants].  A null d_records: DSKGPU_E_ARG. */
+int dskgpu_variants_table(dskgpu_ctx* ctx, void* d_records);
+/* The kept variant stream, on the device: d_offsets u64[2 * n_variants + 1], d_bytes u8[stream_bytes].  Either may be NULL; both NULL:
+ * DSKGPU_E_ARG.  capacity = the bytes d_bytes can hold; capacity < stream_bytes with a non-null d_bytes: DSKGPU_E_ARG, nothing is written. */
+int dskgpu_variants_stream(dskgpu_ctx* ctx, void* d_offsets, void* d_bytes, uint64_t capacity);
+
 /* ---- substitution errors in reads corrected against the count: the other use of a k-mer spectrum (what Bloocoo does with the output of a
  * count).  The rows of the current result are the trusted set: after dskgpu_filter_rows / _simplify / _drop_components, the rows left.
  *   STATE      Positions and validity are those of dskgpu_query_reads / dskgpu_k_enumerate.  The window ending at byte p is TRUSTED when it
