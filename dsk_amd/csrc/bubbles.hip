@@ -1,13 +1,14 @@
-// bubbles.hip -- the simple bubbles of the compacted de Bruijn graph found and popped on the device, and tips and bubbles in turn until the
-// graph stops changing: dskgpu_graph_bubbles / dskgpu_pop_bubbles / dskgpu_simplify (include/dskgpu.h).  Host side of bubbles.h.
-// The bubble rule reads the tables of unitigs.hip (ensure_edges builds them) and nothing else; a round is the round of tips.hip, with its
-// record, keep flags, scan and compaction (engine.h): the four counters of the rule and the new partition offsets are read back at once.
+// bubbles.hip -- the simple bubbles of the compacted de Bruijn graph found and popped on the device, and the rules in turn until the graph
+// stops changing: dskgpu_graph_bubbles / dskgpu_pop_bubbles / dskgpu_simplify / dskgpu_simplify_all (include/dskgpu.h).  Host side of
+// bubbles.h.  The bubble rule reads the tables of unitigs.hip (ensure_edges builds them) and nothing else; a round is the round of tips.hip
+// (round_once / rounds_run of engine.h), with its record, keep flags, scan and compaction: the four counters of the rule and the new
+// partition offsets are read back at once.
 #include <hip/hip_runtime.h>
 
 #include "engine.h"
 #include "bubbles.h"
 
-static_assert(BS_COUNT == REC_COUNTERS, "the bubble rule's counters are the record's");
+static_assert(BS_COUNT == REC_COUNTERS && BS_ROWS == REC_ROWS, "the bubble rule's counters are the record's");
 
 namespace {
 
@@ -15,7 +16,8 @@ unsigned blocks(u64 items, u64 per_block) { return (unsigned)((items + per_block
 
 // enqueue one round of the rule on the current result, whose edges are there: bits per unitig (F.bits), the counters into the record,
 // d_row_pop (may be null) and, with want_keep, the keep flags of the rows (F.keep).  n_rows > 0
-int bubbles_enqueue(dskgpu_ctx* ctx, const dskgpu_bubble_params& p, unsigned char* d_row_pop, bool want_keep) {
+int bubbles_enqueue(dskgpu_ctx* ctx, const void* params, unsigned char* d_row_pop, bool want_keep) {
+    const dskgpu_bubble_params& p = *static_cast<const dskgpu_bubble_params*>(params);
     Filtered& F = ctx->filtered;
     const Unitigs& U = ctx->unitigs;
     const u64 nu = U.stats.n_unitigs;
@@ -34,8 +36,38 @@ int check_params(dskgpu_ctx* ctx, const dskgpu_bubble_params* p, const char* who
     return DSKGPU_OK;
 }
 
-void add_round(dskgpu_bubble_stats& t, const u64* h) {
-    t.n_candidates += h[BS_CAND]; t.n_in_bubbles += h[BS_IN_BUBBLES]; t.n_popped += h[BS_POPPED]; t.n_rows_popped += h[BS_ROWS];
+void set_counters(dskgpu_bubble_stats& t, const u64* h) {
+    t.n_candidates = h[BS_CAND]; t.n_in_bubbles = h[BS_IN_BUBBLES]; t.n_popped = h[BS_POPPED]; t.n_rows_popped = h[BS_ROWS];
+}
+
+// passes of (dskgpu_clip_tips, dskgpu_pop_bubbles, dskgpu_remove_connections), a null parameter set skipping its part, until a pass removes
+// no row: dskgpu_simplify (no third part) and dskgpu_simplify_all.  s: the sums, whatever the return code
+int simplify_passes(dskgpu_ctx* ctx, const char* who, const dskgpu_tip_params* tip_params, const dskgpu_bubble_params* bubble_params,
+                    const dskgpu_connection_params* connection_params, uint32_t max_passes, dskgpu_simplify_all_stats& s) {
+    s = dskgpu_simplify_all_stats{};
+    if (max_passes > 16) return fail(ctx, DSKGPU_E_ARG, std::string(who) + ": max_passes must be in 0..16");
+    if (tip_params && (tip_params->max_nodes == 0 || tip_params->max_nodes > B_MAX_NODES || tip_params->max_rounds > 64))
+        return fail(ctx, DSKGPU_E_ARG, std::string(who) + ": tip_params: max_nodes must be in 1..65535 and max_rounds in 0..64");
+    if (bubble_params) if (const int rc = check_params(ctx, bubble_params, (std::string(who) + ": bubble_params").c_str(), true)) return rc;
+    if (connection_params) if (const int rc = connection_check_params(ctx, connection_params, (std::string(who) + ": connection_params").c_str(), true)) return rc;
+    const u32 passes = max_passes ? max_passes : 16;
+    int rc = DSKGPU_OK;
+    for (u32 pass = 0; pass < passes && rc == DSKGPU_OK; ++pass) {
+        dskgpu_tip_stats t{}; dskgpu_bubble_stats b{}; dskgpu_connection_stats c{};
+        if (tip_params) rc = dskgpu_clip_tips(ctx, tip_params, &t);            // (an error in any part: what it did is in its stats, and in the sums)
+        if (bubble_params && rc == DSKGPU_OK) rc = dskgpu_pop_bubbles(ctx, bubble_params, &b);
+        if (connection_params && rc == DSKGPU_OK) rc = dskgpu_remove_connections(ctx, connection_params, &c);
+        s.tips.n_candidates += t.n_candidates; s.tips.n_tips += t.n_tips; s.tips.n_outranked += t.n_outranked;
+        s.tips.n_rows_clipped += t.n_rows_clipped; s.tips.n_rounds += t.n_rounds;
+        s.bubbles.n_candidates += b.n_candidates; s.bubbles.n_in_bubbles += b.n_in_bubbles; s.bubbles.n_popped += b.n_popped;
+        s.bubbles.n_rows_popped += b.n_rows_popped; s.bubbles.n_rounds += b.n_rounds;
+        s.connections.n_candidates += c.n_candidates; s.connections.n_one_sided += c.n_one_sided; s.connections.n_removed += c.n_removed;
+        s.connections.n_rows_removed += c.n_rows_removed; s.connections.n_rounds += c.n_rounds;
+        if (t.n_rows_clipped + b.n_rows_popped + c.n_rows_removed == 0) break;
+        ++s.n_passes;
+    }
+    s.n_rows_left = s.tips.n_rows_left = s.bubbles.n_rows_left = s.connections.n_rows_left = ctx->n_rows;
+    return rc;
 }
 
 }  // namespace
@@ -59,22 +91,10 @@ int dskgpu_graph_bubbles(dskgpu_ctx* ctx, const dskgpu_bubble_params* params, vo
     if (!ctx) return DSKGPU_E_ARG;
     if (!d_row_pop && !d_unitig_bits && !stats) return fail(ctx, DSKGPU_E_ARG, "dskgpu_graph_bubbles: no output pointer");
     if (const int rc = check_params(ctx, params, "dskgpu_graph_bubbles", false)) return rc;
-    if (const int rc = ensure_edges(ctx, "dskgpu_graph_bubbles")) return rc;
+    u64 h[REC_COUNTERS];
+    if (const int rc = round_once(ctx, "dskgpu_graph_bubbles", "bubbles", bubbles_enqueue, params, d_row_pop, d_unitig_bits, h)) return rc;
     dskgpu_bubble_stats t{};
-    if (ctx->n_rows == 0) {
-        if (const int rc = query_finish(ctx)) return rc;
-        if (stats) *stats = t;
-        return DSKGPU_OK;
-    }
-    std::vector<u64> old_off, h;
-    if (const int rc = begin_record(ctx, false, old_off)) return abandon(ctx, rc);
-    if (const int rc = bubbles_enqueue(ctx, *params, static_cast<unsigned char*>(d_row_pop), false)) return abandon(ctx, rc);
-    if (d_unitig_bits) CK(hipMemcpyAsync(d_unitig_bits, ctx->filtered.bits.p, ctx->unitigs.stats.n_unitigs, hipMemcpyDeviceToDevice, ctx->stream));
-    ctx->mark("bubbles");
-    if (const int rc = read_record(ctx, h, 0)) return abandon(ctx, rc);
-    if (const int rc = query_finish(ctx)) return rc;
-    add_round(t, h.data());
-    t.n_rounds = 1; t.n_rows_left = ctx->n_rows - t.n_rows_popped;
+    if (ctx->n_rows) { set_counters(t, h); t.n_rounds = 1; t.n_rows_left = ctx->n_rows - t.n_rows_popped; }
     if (stats) *stats = t;
     return DSKGPU_OK;
 }
@@ -82,26 +102,11 @@ int dskgpu_graph_bubbles(dskgpu_ctx* ctx, const dskgpu_bubble_params* params, vo
 int dskgpu_pop_bubbles(dskgpu_ctx* ctx, const dskgpu_bubble_params* params, dskgpu_bubble_stats* stats) {
     if (!ctx) return DSKGPU_E_ARG;
     if (const int rc = check_params(ctx, params, "dskgpu_pop_bubbles", true)) return rc;
-    const u64 max_rounds = params->max_rounds ? params->max_rounds : 64;
+    u64 h[REC_COUNTERS], n_rounds;
     dskgpu_bubble_stats t{};
-    std::vector<u64> old_off, h;
-    int rc = DSKGPU_OK;
-    for (;;) {
-        if ((rc = ensure_edges(ctx, "dskgpu_pop_bubbles"))) break;            // (of the final rows too: the graph is ready when the call returns)
-        if (ctx->n_rows == 0 || t.n_rounds == max_rounds) { rc = query_finish(ctx); break; }
-        const u64 n = ctx->n_rows;
-        if ((rc = begin_record(ctx, true, old_off)) || (rc = bubbles_enqueue(ctx, *params, nullptr, true))) { abandon(ctx, rc); break; }
-        ctx->mark("bubbles");
-        const unsigned char* keep = ctx->filtered.keep.as<unsigned char>();
-        if ((rc = filter_scan(ctx, keep, old_off)) || (rc = read_record(ctx, h, old_off.size()))) { abandon(ctx, rc); break; }
-        if (h[BS_POPPED] == 0) { add_round(t, h.data()); rc = query_finish(ctx); break; }
-        if (h[BS_ROWS] + h.back() != n) { rc = abandon(ctx, fail(ctx, DSKGPU_E_DEVICE, "dskgpu_pop_bubbles: the popped rows and the kept rows do not add up (internal error)")); break; }
-        if ((rc = filter_apply(ctx, keep, h.data() + REC_COUNTERS, old_off.size()))) { abandon(ctx, rc); break; }
-        ctx->mark("filter rows");
-        add_round(t, h.data());
-        ++t.n_rounds;
-        if ((rc = query_finish(ctx))) break;
-    }
+    const int rc = rounds_run(ctx, "dskgpu_pop_bubbles", "bubbles", params->max_rounds ? params->max_rounds : 64, bubbles_enqueue, params, h, &n_rounds);
+    set_counters(t, h);
+    t.n_rounds = n_rounds;
     t.n_rows_left = ctx->n_rows;
     if (stats) *stats = t;
     return rc;
@@ -110,26 +115,23 @@ int dskgpu_pop_bubbles(dskgpu_ctx* ctx, const dskgpu_bubble_params* params, dskg
 int dskgpu_simplify(dskgpu_ctx* ctx, const dskgpu_tip_params* tip_params, const dskgpu_bubble_params* bubble_params, uint32_t max_passes, dskgpu_simplify_stats* stats) {
     if (!ctx) return DSKGPU_E_ARG;
     if (!tip_params && !bubble_params) return fail(ctx, DSKGPU_E_ARG, "dskgpu_simplify: null tip_params and bubble_params");
-    if (max_passes > 16) return fail(ctx, DSKGPU_E_ARG, "dskgpu_simplify: max_passes must be in 0..16");
-    if (tip_params && (tip_params->max_nodes == 0 || tip_params->max_nodes > B_MAX_NODES || tip_params->max_rounds > 64))
-        return fail(ctx, DSKGPU_E_ARG, "dskgpu_simplify: tip_params: max_nodes must be in 1..65535 and max_rounds in 0..64");
-    if (bubble_params) if (const int rc = check_params(ctx, bubble_params, "dskgpu_simplify: bubble_params", true)) return rc;
-    const u32 passes = max_passes ? max_passes : 16;
+    dskgpu_simplify_all_stats a;
+    const int rc = simplify_passes(ctx, "dskgpu_simplify", tip_params, bubble_params, nullptr, max_passes, a);
+    if (rc == DSKGPU_E_ARG) return rc;                                       // (nothing ran: stats stays as it is)
     dskgpu_simplify_stats s{};
-    int rc = DSKGPU_OK;
-    for (u32 pass = 0; pass < passes && rc == DSKGPU_OK; ++pass) {
-        dskgpu_tip_stats t{}; dskgpu_bubble_stats b{};
-        if (tip_params) rc = dskgpu_clip_tips(ctx, tip_params, &t);            // (an error in either half: what it did is in its stats, and in the sums)
-        if (bubble_params && rc == DSKGPU_OK) rc = dskgpu_pop_bubbles(ctx, bubble_params, &b);
-        s.tips.n_candidates += t.n_candidates; s.tips.n_tips += t.n_tips; s.tips.n_outranked += t.n_outranked;
-        s.tips.n_rows_clipped += t.n_rows_clipped; s.tips.n_rounds += t.n_rounds;
-        s.bubbles.n_candidates += b.n_candidates; s.bubbles.n_in_bubbles += b.n_in_bubbles; s.bubbles.n_popped += b.n_popped;
-        s.bubbles.n_rows_popped += b.n_rows_popped; s.bubbles.n_rounds += b.n_rounds;
-        if (t.n_rows_clipped + b.n_rows_popped == 0) break;
-        ++s.n_passes;
-    }
-    s.n_rows_left = s.tips.n_rows_left = s.bubbles.n_rows_left = ctx->n_rows;
+    s.n_passes = a.n_passes; s.n_rows_left = a.n_rows_left; s.tips = a.tips; s.bubbles = a.bubbles;
     if (stats) *stats = s;
+    return rc;
+}
+
+int dskgpu_simplify_all(dskgpu_ctx* ctx, const dskgpu_tip_params* tip_params, const dskgpu_bubble_params* bubble_params,
+                        const dskgpu_connection_params* connection_params, uint32_t max_passes, dskgpu_simplify_all_stats* stats) {
+    if (!ctx) return DSKGPU_E_ARG;
+    if (!tip_params && !bubble_params && !connection_params) return fail(ctx, DSKGPU_E_ARG, "dskgpu_simplify_all: null tip_params, bubble_params and connection_params");
+    dskgpu_simplify_all_stats a;
+    const int rc = simplify_passes(ctx, "dskgpu_simplify_all", tip_params, bubble_params, connection_params, max_passes, a);
+    if (rc == DSKGPU_E_ARG) return rc;
+    if (stats) *stats = a;
     return rc;
 }
 

@@ -6,7 +6,8 @@
 // last result (dskgpu_query_*) and owns dskgpu_ctx::query; graph.hip answers the de Bruijn neighbourhood of k-mers from the same index
 // (dskgpu_graph_*); unitigs.hip compacts the rows' graph into unitigs and links them (dskgpu_unitigs*, dskgpu_unitig_edges*) and owns dskgpu_ctx::unitigs;
 // tips.hip takes rows out of a result (dskgpu_filter_rows) and finds and clips the tips of the compacted graph (dskgpu_graph_tips, dskgpu_clip_tips) and owns dskgpu_ctx::filtered;
-// bubbles.hip finds and pops the simple bubbles with the same rounds (dskgpu_graph_bubbles, dskgpu_pop_bubbles, dskgpu_simplify);
+// bubbles.hip finds and pops the simple bubbles with the same rounds (dskgpu_graph_bubbles, dskgpu_pop_bubbles) and runs the rules in turn (dskgpu_simplify, dskgpu_simplify_all);
+// connections.hip finds and removes the erroneous connections with the same rounds (dskgpu_graph_connections, dskgpu_remove_connections);
 // thread.hip threads reads through the compacted graph (dskgpu_thread_*) and owns dskgpu_ctx::threading;
 // components.hip labels the connected components of the compacted graph and takes the small ones out (dskgpu_components*, dskgpu_graph_small_components,
 // dskgpu_drop_components) and owns dskgpu_ctx::unitigs.cc;
@@ -212,7 +213,8 @@ struct Variants {
 // kept row of every partition (n_parts + 1 entries) -- rows_partition_range reads them instead of the row sort's while cur >= 0.
 // The rest is scratch: scan = the exclusive scan of the keep flags, rec = the record a round reads back ([REC_COUNTERS counters | new
 // partition offsets]), off_in = the old partition offsets on the device; info / len / bits / keep = the tip rule's per-unitig and per-row
-// bytes; the bubble rule (bubbles.hip) uses len / bits / keep too and ends = the two ends of every candidate, one word per unitig.
+// bytes; the bubble rule (bubbles.hip) uses len / bits / keep too and ends = the two ends of every candidate, one word per unitig; the
+// connection rule (connections.hip) uses info / len / bits / keep.
 // Like the index and the compaction it is kept between calls (9 bytes per row + 14 per unitig of the largest call), so that a caller
 // who drives the rounds pays no allocation per round, and goes with the result (dskgpu_ctx::drop_result).
 struct Filtered {
@@ -428,9 +430,10 @@ int query_finish(dskgpu_ctx* ctx);                       // ... and the wait for
 // unitigs.hip
 int ensure_edges(dskgpu_ctx* ctx, const char* who);      // the edges of the current result's compaction: there already, or built now (opens the call's stage marks)
 
-// tips.hip: the machinery of a round that takes rows out, shared by the tip and the bubble rule.  The record of a round (Filtered::rec) is
-// [REC_COUNTERS counters of the rule, zeroed | one new offset per entry of old_off]; the last new offset is the kept total
-enum { REC_COUNTERS = 4 };
+// tips.hip: the machinery of a round that takes rows out, shared by the tip, the bubble and the connection rule.  The record of a round
+// (Filtered::rec) is [REC_COUNTERS counters of the rule, zeroed | one new offset per entry of old_off]; the last new offset is the kept
+// total.  Counter REC_ROWS of every rule is the number of rows it flags
+enum { REC_COUNTERS = 4, REC_ROWS = 3 };
 int abandon(dskgpu_ctx* ctx, int rc);                    // a call gives up: wait for the stream, forget its stage marks, -> rc
 int begin_record(dskgpu_ctx* ctx, bool with_offsets, std::vector<u64>& old_off);      // the record, its counters zeroed; with_offsets: old_off = the partitions' first rows and n_rows
 int filter_scan(dskgpu_ctx* ctx, const unsigned char* keep, const std::vector<u64>& old_off);      // enqueue the scan of the keep flags and the new offsets into the record
@@ -438,6 +441,16 @@ int read_record(dskgpu_ctx* ctx, std::vector<u64>& h, u64 n_off);      // the ro
 int filter_apply(dskgpu_ctx* ctx, const unsigned char* keep, const u64* new_off, u64 n_off);      // the kept rows become the result
 // per row, bit 1 of Filtered::bits of its unitig -> d_row_flag (may be null) and, with want_keep, its complement -> Filtered::keep
 int flag_rows(dskgpu_ctx* ctx, unsigned char* d_row_flag, bool want_keep);
+// a rule: enqueue one round on the current result, whose edges are there (n_rows > 0): the bits of every unitig into Filtered::bits, the
+// counters into the record, then flag_rows(d_row_flag, want_keep).  params: the rule's parameter structure
+typedef int (*RoundEnqueue)(dskgpu_ctx* ctx, const void* params, unsigned char* d_row_flag, bool want_keep);
+// one round, no row changes: counters[REC_COUNTERS] (zero when there are no rows), the bits copied to d_unitig_bits (may be null)
+int round_once(dskgpu_ctx* ctx, const char* who, const char* stage, RoundEnqueue enqueue, const void* params, void* d_row_flag, void* d_unitig_bits, u64* counters);
+// rounds of (rule -> filter) until a round flags no row or max_rounds rounds have removed rows: counters[REC_COUNTERS] = the sums, *n_rounds
+int rounds_run(dskgpu_ctx* ctx, const char* who, const char* stage, u64 max_rounds, RoundEnqueue enqueue, const void* params, u64* counters, u64* n_rounds);
 
 // bubbles.hip
 int bubble_candidates(dskgpu_ctx* ctx, u32 max_nodes);   // enqueue k_bubble_candidates on the current result, whose edges are there: Filtered::ends / ::len
+
+// connections.hip
+int connection_check_params(dskgpu_ctx* ctx, const dskgpu_connection_params* p, const char* who, bool rounds);      // DSKGPU_E_ARG and its text, or DSKGPU_OK

@@ -11,7 +11,7 @@
 #include "engine.h"
 #include "tips.h"
 
-static_assert(TS_COUNT == REC_COUNTERS, "the tip rule's counters are the record's");
+static_assert(TS_COUNT == REC_COUNTERS && TS_ROWS == REC_ROWS, "the tip rule's counters are the record's");
 
 namespace {
 
@@ -19,7 +19,7 @@ unsigned blocks(u64 items, u64 per_block) { return (unsigned)((items + per_block
 
 }  // namespace
 
-// ---- the machinery of a round (engine.h), shared with bubbles.hip
+// ---- the machinery of a round (engine.h), shared with bubbles.hip and connections.hip
 int abandon(dskgpu_ctx* ctx, int rc) {
     (void)hipStreamSynchronize(ctx->stream);
     ctx->marks.clear(); ctx->ev_used = 0;
@@ -117,11 +117,60 @@ int flag_rows(dskgpu_ctx* ctx, unsigned char* d_row_flag, bool want_keep) {
     return DSKGPU_OK;
 }
 
+// one round of a rule on the current result, no row changes (dskgpu_graph_tips and its kin, whose arguments the caller has checked): builds
+// the edges, enqueues the rule, copies the bits out and reads the counters back.  A result without rows: zero counters, nothing written
+int round_once(dskgpu_ctx* ctx, const char* who, const char* stage, RoundEnqueue enqueue, const void* params, void* d_row_flag, void* d_unitig_bits, u64* counters) {
+    std::fill(counters, counters + REC_COUNTERS, 0ull);
+    if (const int rc = ensure_edges(ctx, who)) return rc;
+    if (ctx->n_rows == 0) return query_finish(ctx);
+    std::vector<u64> old_off, h;
+    if (const int rc = begin_record(ctx, false, old_off)) return abandon(ctx, rc);
+    if (const int rc = enqueue(ctx, params, static_cast<unsigned char*>(d_row_flag), false)) return abandon(ctx, rc);
+    if (d_unitig_bits) CK(hipMemcpyAsync(d_unitig_bits, ctx->filtered.bits.p, ctx->unitigs.stats.n_unitigs, hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->mark(stage);
+    if (const int rc = read_record(ctx, h, 0)) return abandon(ctx, rc);
+    if (const int rc = query_finish(ctx)) return rc;
+    std::copy(h.begin(), h.begin() + REC_COUNTERS, counters);
+    return DSKGPU_OK;
+}
+
+// rounds of (the rule -> the filter of the rows it flags) until a round flags no row or max_rounds rounds have removed some (dskgpu_clip_tips
+// and its kin).  counters: the sums over the rounds that ran, the last one that removed nothing included; *n_rounds: the rounds that removed
+// something.  On return, an error or not, the context holds the result of the rounds that were done
+int rounds_run(dskgpu_ctx* ctx, const char* who, const char* stage, u64 max_rounds, RoundEnqueue enqueue, const void* params, u64* counters, u64* n_rounds) {
+    std::fill(counters, counters + REC_COUNTERS, 0ull);
+    *n_rounds = 0;
+    std::vector<u64> old_off, h;
+    int rc = DSKGPU_OK;
+    for (;;) {
+        if ((rc = ensure_edges(ctx, who))) break;                            // (of the final rows too: the graph is ready when the call returns)
+        if (ctx->n_rows == 0 || *n_rounds == max_rounds) { rc = query_finish(ctx); break; }
+        const u64 n = ctx->n_rows;
+        if ((rc = begin_record(ctx, true, old_off)) || (rc = enqueue(ctx, params, nullptr, true))) { abandon(ctx, rc); break; }
+        ctx->mark(stage);
+        const unsigned char* keep = ctx->filtered.keep.as<unsigned char>();
+        if ((rc = filter_scan(ctx, keep, old_off)) || (rc = read_record(ctx, h, old_off.size()))) { abandon(ctx, rc); break; }
+        if (h[REC_ROWS] == 0) {                                               // (every unitig has a row: no row flagged <=> no unitig flagged)
+            for (int i = 0; i < REC_COUNTERS; ++i) counters[i] += h[i];
+            rc = query_finish(ctx);
+            break;
+        }
+        if (h[REC_ROWS] + h.back() != n) { rc = abandon(ctx, fail(ctx, DSKGPU_E_DEVICE, std::string(who) + ": the removed rows and the kept rows do not add up (internal error)")); break; }
+        if ((rc = filter_apply(ctx, keep, h.data() + REC_COUNTERS, old_off.size()))) { abandon(ctx, rc); break; }
+        ctx->mark("filter rows");
+        for (int i = 0; i < REC_COUNTERS; ++i) counters[i] += h[i];
+        ++*n_rounds;
+        if ((rc = query_finish(ctx))) break;
+    }
+    return rc;
+}
+
 namespace {
 
 // enqueue one round of the rule on the current result, whose edges are there: bits per unitig (F.bits), the counters into the record,
 // d_row_tip (may be null) and, with want_keep, the keep flags of the rows (F.keep).  n_rows > 0
-int tips_enqueue(dskgpu_ctx* ctx, const dskgpu_tip_params& p, unsigned char* d_row_tip, bool want_keep) {
+int tips_enqueue(dskgpu_ctx* ctx, const void* params, unsigned char* d_row_tip, bool want_keep) {
+    const dskgpu_tip_params& p = *static_cast<const dskgpu_tip_params*>(params);
     Filtered& F = ctx->filtered;
     const Unitigs& U = ctx->unitigs;
     const u64 nu = U.stats.n_unitigs;
@@ -144,8 +193,8 @@ int check_params(dskgpu_ctx* ctx, const dskgpu_tip_params* p, const char* who) {
     return DSKGPU_OK;
 }
 
-void add_round(dskgpu_tip_stats& t, const u64* h) {
-    t.n_candidates += h[TS_CAND]; t.n_tips += h[TS_TIPS]; t.n_outranked += h[TS_OUTRANKED]; t.n_rows_clipped += h[TS_ROWS];
+void set_counters(dskgpu_tip_stats& t, const u64* h) {
+    t.n_candidates = h[TS_CAND]; t.n_tips = h[TS_TIPS]; t.n_outranked = h[TS_OUTRANKED]; t.n_rows_clipped = h[TS_ROWS];
 }
 
 }  // namespace
@@ -175,22 +224,10 @@ int dskgpu_graph_tips(dskgpu_ctx* ctx, const dskgpu_tip_params* params, void* d_
     if (!ctx) return DSKGPU_E_ARG;
     if (!d_row_tip && !d_unitig_tip && !stats) return fail(ctx, DSKGPU_E_ARG, "dskgpu_graph_tips: no output pointer");
     if (const int rc = check_params(ctx, params, "dskgpu_graph_tips")) return rc;
-    if (const int rc = ensure_edges(ctx, "dskgpu_graph_tips")) return rc;
+    u64 h[REC_COUNTERS];
+    if (const int rc = round_once(ctx, "dskgpu_graph_tips", "tips", tips_enqueue, params, d_row_tip, d_unitig_tip, h)) return rc;
     dskgpu_tip_stats t{};
-    if (ctx->n_rows == 0) {
-        if (const int rc = query_finish(ctx)) return rc;
-        if (stats) *stats = t;
-        return DSKGPU_OK;
-    }
-    std::vector<u64> old_off, h;
-    if (const int rc = begin_record(ctx, false, old_off)) return abandon(ctx, rc);
-    if (const int rc = tips_enqueue(ctx, *params, static_cast<unsigned char*>(d_row_tip), false)) return abandon(ctx, rc);
-    if (d_unitig_tip) CK(hipMemcpyAsync(d_unitig_tip, ctx->filtered.bits.p, ctx->unitigs.stats.n_unitigs, hipMemcpyDeviceToDevice, ctx->stream));
-    ctx->mark("tips");
-    if (const int rc = read_record(ctx, h, 0)) return abandon(ctx, rc);
-    if (const int rc = query_finish(ctx)) return rc;
-    add_round(t, h.data());
-    t.n_rounds = 1; t.n_rows_left = ctx->n_rows - t.n_rows_clipped;
+    if (ctx->n_rows) { set_counters(t, h); t.n_rounds = 1; t.n_rows_left = ctx->n_rows - t.n_rows_clipped; }
     if (stats) *stats = t;
     return DSKGPU_OK;
 }
@@ -199,26 +236,11 @@ int dskgpu_clip_tips(dskgpu_ctx* ctx, const dskgpu_tip_params* params, dskgpu_ti
     if (!ctx) return DSKGPU_E_ARG;
     if (const int rc = check_params(ctx, params, "dskgpu_clip_tips")) return rc;
     if (params->max_rounds > 64) return fail(ctx, DSKGPU_E_ARG, "dskgpu_clip_tips: max_rounds must be in 0..64");
-    const u64 max_rounds = params->max_rounds ? params->max_rounds : 64;
+    u64 h[REC_COUNTERS], n_rounds;
     dskgpu_tip_stats t{};
-    std::vector<u64> old_off, h;
-    int rc = DSKGPU_OK;
-    for (;;) {
-        if ((rc = ensure_edges(ctx, "dskgpu_clip_tips"))) break;              // (of the final rows too: the graph is ready when the call returns)
-        if (ctx->n_rows == 0 || t.n_rounds == max_rounds) { rc = query_finish(ctx); break; }
-        const u64 n = ctx->n_rows;
-        if ((rc = begin_record(ctx, true, old_off)) || (rc = tips_enqueue(ctx, *params, nullptr, true))) { abandon(ctx, rc); break; }
-        ctx->mark("tips");
-        const unsigned char* keep = ctx->filtered.keep.as<unsigned char>();
-        if ((rc = filter_scan(ctx, keep, old_off)) || (rc = read_record(ctx, h, old_off.size()))) { abandon(ctx, rc); break; }
-        if (h[TS_TIPS] == 0) { add_round(t, h.data()); rc = query_finish(ctx); break; }
-        if (h[TS_ROWS] + h.back() != n) { rc = abandon(ctx, fail(ctx, DSKGPU_E_DEVICE, "dskgpu_clip_tips: the tips' rows and the kept rows do not add up (internal error)")); break; }
-        if ((rc = filter_apply(ctx, keep, h.data() + TS_COUNT, old_off.size()))) { abandon(ctx, rc); break; }
-        ctx->mark("filter rows");
-        add_round(t, h.data());
-        ++t.n_rounds;
-        if ((rc = query_finish(ctx))) break;
-    }
+    const int rc = rounds_run(ctx, "dskgpu_clip_tips", "tips", params->max_rounds ? params->max_rounds : 64, tips_enqueue, params, h, &n_rounds);
+    set_counters(t, h);
+    t.n_rounds = n_rounds;
     t.n_rows_left = ctx->n_rows;
     if (stats) *stats = t;
     return rc;

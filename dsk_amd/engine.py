@@ -168,6 +168,39 @@ class _SimplifyStats(C.Structure):
     ]
 
 
+class _ConnectionParams(C.Structure):
+    _fields_ = [
+        ("max_nodes", C.c_uint32),
+        ("min_ratio", C.c_uint32),
+        ("max_abundance", C.c_uint32),
+        ("max_rounds", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class _ConnectionStats(C.Structure):
+    _fields_ = [
+        ("n_candidates", C.c_uint64),
+        ("n_one_sided", C.c_uint64),
+        ("n_removed", C.c_uint64),
+        ("n_rows_removed", C.c_uint64),
+        ("n_rounds", C.c_uint64),
+        ("n_rows_left", C.c_uint64),
+        ("reserved", C.c_uint64 * 2),
+    ]
+
+
+class _SimplifyAllStats(C.Structure):
+    _fields_ = [
+        ("n_passes", C.c_uint64),
+        ("n_rows_left", C.c_uint64),
+        ("reserved", C.c_uint64 * 6),
+        ("tips", _TipStats),
+        ("bubbles", _BubbleStats),
+        ("connections", _ConnectionStats),
+    ]
+
+
 class _VariantParams(C.Structure):
     _fields_ = [
         ("max_nodes", C.c_uint32),
@@ -254,6 +287,7 @@ EXPORTS = [
     "dskgpu_unitigs", "dskgpu_unitigs_rows", "dskgpu_unitigs_table", "dskgpu_unitigs_stream", "dskgpu_unitig_edges", "dskgpu_unitig_edges_table",
     "dskgpu_filter_rows", "dskgpu_graph_tips", "dskgpu_clip_tips",
     "dskgpu_graph_bubbles", "dskgpu_pop_bubbles", "dskgpu_simplify",
+    "dskgpu_graph_connections", "dskgpu_remove_connections", "dskgpu_simplify_all",
     "dskgpu_components", "dskgpu_components_labels", "dskgpu_components_table", "dskgpu_graph_small_components", "dskgpu_drop_components",
     "dskgpu_thread_place", "dskgpu_thread_reads", "dskgpu_thread_walks", "dskgpu_thread_support",
     "dskgpu_correct_reads",
@@ -367,6 +401,13 @@ def load_library():
     lib.dskgpu_pop_bubbles.restype = C.c_int
     lib.dskgpu_simplify.argtypes = [vp, C.POINTER(_TipParams), C.POINTER(_BubbleParams), C.c_uint32, C.POINTER(_SimplifyStats)]
     lib.dskgpu_simplify.restype = C.c_int
+    lib.dskgpu_graph_connections.argtypes = [vp, C.POINTER(_ConnectionParams), vp, vp, C.POINTER(_ConnectionStats)]
+    lib.dskgpu_graph_connections.restype = C.c_int
+    lib.dskgpu_remove_connections.argtypes = [vp, C.POINTER(_ConnectionParams), C.POINTER(_ConnectionStats)]
+    lib.dskgpu_remove_connections.restype = C.c_int
+    lib.dskgpu_simplify_all.argtypes = [vp, C.POINTER(_TipParams), C.POINTER(_BubbleParams), C.POINTER(_ConnectionParams), C.c_uint32,
+                                        C.POINTER(_SimplifyAllStats)]
+    lib.dskgpu_simplify_all.restype = C.c_int
     lib.dskgpu_components.argtypes = [vp, C.POINTER(_ComponentStats)]
     lib.dskgpu_components.restype = C.c_int
     lib.dskgpu_components_labels.argtypes = [vp, vp, vp]
@@ -1086,22 +1127,87 @@ class KmerCounter:
         keyword arguments of clip_tips / pop_bubbles (None = their defaults), or False to skip that half.  On return the unitigs and the
         edges of the rows left are built: write_gfa writes the cleaned graph.  -> {n_passes, n_rows_left, tips: the sums of clip_tips'
         dicts, bubbles: those of pop_bubbles'}."""
-        tp = bp = None
-        if tips is not False:
-            a = dict(tips or {})
-            mn = a.pop("max_nodes", None)
-            tp = _TipParams(max_nodes=self.kmer_size if mn is None else mn, max_abundance=a.pop("max_abundance", 0), max_rounds=a.pop("max_rounds", 0))
-            if a:
-                raise TypeError("simplify: unknown tip arguments %s" % sorted(a))
-        if bubbles is not False:
-            a = dict(bubbles or {})
-            mn = a.pop("max_nodes", None)
-            bp = _BubbleParams(max_nodes=2 * self.kmer_size if mn is None else mn, max_diff=a.pop("max_diff", 4), max_rounds=a.pop("max_rounds", 0))
-            if a:
-                raise TypeError("simplify: unknown bubble arguments %s" % sorted(a))
+        tp, bp = self._tip_params_of(tips), self._bubble_params_of(bubbles)
         st = _SimplifyStats()
         self._ck(self._lib.dskgpu_simplify(self._h, C.byref(tp) if tp is not None else None, C.byref(bp) if bp is not None else None, max_passes, C.byref(st)))
         return {"n_passes": int(st.n_passes), "n_rows_left": int(st.n_rows_left), "tips": self._tip_stats(st.tips), "bubbles": self._bubble_stats(st.bubbles)}
+
+    def _tip_params_of(self, tips):
+        """the tip part of simplify / simplify_all: a dict of clip_tips' keyword arguments, None = its defaults, False = no such part"""
+        if tips is False:
+            return None
+        a = dict(tips or {})
+        mn = a.pop("max_nodes", None)
+        tp = _TipParams(max_nodes=self.kmer_size if mn is None else mn, max_abundance=a.pop("max_abundance", 0), max_rounds=a.pop("max_rounds", 0))
+        if a:
+            raise TypeError("simplify: unknown tip arguments %s" % sorted(a))
+        return tp
+
+    def _bubble_params_of(self, bubbles):
+        if bubbles is False:
+            return None
+        a = dict(bubbles or {})
+        mn = a.pop("max_nodes", None)
+        bp = _BubbleParams(max_nodes=2 * self.kmer_size if mn is None else mn, max_diff=a.pop("max_diff", 4), max_rounds=a.pop("max_rounds", 0))
+        if a:
+            raise TypeError("simplify: unknown bubble arguments %s" % sorted(a))
+        return bp
+
+    # -- the erroneous connections of the compacted graph, and all three rules in turn (include/dskgpu.h: dskgpu_graph_connections /
+    # _remove_connections / _simplify_all)
+    @staticmethod
+    def _connection_stats(st) -> dict:
+        return {name: int(getattr(st, name)) for name, _ in _ConnectionStats._fields_ if name != "reserved"}
+
+    def graph_connections(self, max_nodes: int, min_ratio: int = 4, max_abundance: int = 0, d_row_rem: int = 0, d_unitig_bits: int = 0) -> dict:
+        """One round of the erroneous-connection rule on the last result, which stays as it is.  d_row_rem: n_rows bytes on the device <- 1 =
+        the row's unitig is removed; d_unitig_bits: n_unitigs bytes <- bit 0 candidate, bit 1 removed, bit 2 weak at the end 2u, bit 3 weak
+        at the end 2u + 1; either may be 0.  -> the round's counts: n_candidates, n_one_sided, n_removed, n_rows_removed, n_rounds (1),
+        n_rows_left."""
+        par, st = _ConnectionParams(max_nodes=max_nodes, min_ratio=min_ratio, max_abundance=max_abundance), _ConnectionStats()
+        self._ck(self._lib.dskgpu_graph_connections(self._h, C.byref(par), C.c_void_p(d_row_rem) if d_row_rem else None,
+                                                    C.c_void_p(d_unitig_bits) if d_unitig_bits else None, C.byref(st)))
+        return self._connection_stats(st)
+
+    def graph_connections_tensor(self, max_nodes: int, min_ratio: int = 4, max_abundance: int = 0):
+        """-> (uint8[n_rows] row is removed, uint8[n_unitigs] candidate | removed << 1 | weak at 2u << 2 | weak at 2u + 1 << 3, the stats of
+        graph_connections), CUDA tensors."""
+        import torch
+        nu = self.unitigs()["n_unitigs"]
+        n = self.result_device()[2]
+        dev = torch.device("cuda", self.device)
+        row_rem, unitig_bits = torch.zeros(n, dtype=torch.uint8, device=dev), torch.zeros(nu, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()              # the context's stream is not torch's: the zero fill is done before the kernels write
+        st = self.graph_connections(max_nodes, min_ratio, max_abundance, row_rem.data_ptr() if n else 0, unitig_bits.data_ptr() if nu else 0)
+        return row_rem, unitig_bits, st
+
+    def remove_connections(self, max_nodes: Optional[int] = None, min_ratio: int = 4, max_abundance: int = 0, max_rounds: int = 0) -> dict:
+        """Rounds of (connections -> filter_rows) until a round removes nothing or max_rounds (0 = 64) rounds have removed; max_nodes None =
+        2 * kmer_size.  On return the unitigs and the edges of the rows left are built.  -> the sums over the rounds, n_rounds = rounds that
+        removed, n_rows_left = the rows of the result now."""
+        par = _ConnectionParams(max_nodes=2 * self.kmer_size if max_nodes is None else max_nodes, min_ratio=min_ratio, max_abundance=max_abundance,
+                                max_rounds=max_rounds)
+        st = _ConnectionStats()
+        self._ck(self._lib.dskgpu_remove_connections(self._h, C.byref(par), C.byref(st)))
+        return self._connection_stats(st)
+
+    def simplify_all(self, tips: Optional[dict] = None, bubbles: Optional[dict] = None, connections: Optional[dict] = None, max_passes: int = 0) -> dict:
+        """Passes of (clip_tips, pop_bubbles, then remove_connections) until a pass removes no row or max_passes (0 = 16) passes have run.
+        tips / bubbles / connections: the keyword arguments of clip_tips / pop_bubbles / remove_connections (None = their defaults), or
+        False to skip that part.  On return the unitigs and the edges of the rows left are built.  -> {n_passes, n_rows_left, tips,
+        bubbles, connections: the sums of the three calls' dicts}."""
+        tp, bp, cp = self._tip_params_of(tips), self._bubble_params_of(bubbles), None
+        if connections is not False:
+            a = dict(connections or {})
+            mn = a.pop("max_nodes", None)
+            cp = _ConnectionParams(max_nodes=2 * self.kmer_size if mn is None else mn, min_ratio=a.pop("min_ratio", 4), max_abundance=a.pop("max_abundance", 0),
+                                   max_rounds=a.pop("max_rounds", 0))
+            if a:
+                raise TypeError("simplify_all: unknown connection arguments %s" % sorted(a))
+        st = _SimplifyAllStats()
+        self._ck(self._lib.dskgpu_simplify_all(self._h, *(C.byref(x) if x is not None else None for x in (tp, bp, cp)), max_passes, C.byref(st)))
+        return {"n_passes": int(st.n_passes), "n_rows_left": int(st.n_rows_left), "tips": self._tip_stats(st.tips), "bubbles": self._bubble_stats(st.bubbles),
+                "connections": self._connection_stats(st.connections)}
 
     # -- the bubbles of the compacted graph reported as variants (include/dskgpu.h: dskgpu_variants / _variants_table / _variants_stream)
     def variants(self, max_nodes: Optional[int] = None, max_diff: int = 4) -> dict:

@@ -530,6 +530,57 @@ int dskgpu_pop_bubbles(dskgpu_ctx* ctx, const dskgpu_bubble_params* params, dskg
  * Errors: those of the two calls, checked for both sets of parameters before anything runs. */
 int dskgpu_simplify(dskgpu_ctx* ctx, const dskgpu_tip_params* tip_params, const dskgpu_bubble_params* bubble_params, uint32_t max_passes, dskgpu_simplify_stats* stats);
 
+/* ---- erroneous connections: the third of the simplifications that Minia and gatb-core's `Graph` run, after tips and bulges.  An erroneous
+ * connection is a short, weakly covered unitig attached at BOTH ends, bridging two well-covered places -- what a chimeric read leaves, a
+ * sequencing error inside a repeat, or a weak branch whose ends fork.  The tip rule ignores it (no dead end), the bubble rule ignores it
+ * unless both ends have exactly one edge and a parallel chain runs between the same two ends; it joins components that should be separate
+ * and splits contigs at forks that should not be there.  The rule reads the same tables as the tip rule and a round takes rows out the same
+ * way (dskgpu_filter_rows); exact integer arithmetic, nothing depends on the row order except the numbering.  In the notation of the tip
+ * section:
+ *   CANDIDATE  cand[u] <=> kind[u] == 0, L[u] <= max_nodes, deg(2u) >= 1 and deg(2u + 1) >= 1, no target of either end is a reading of u
+ *              (V >> 1 != u for every V in E(2u) and E(2u + 1)), and max_abundance == 0 or S[u] <= max_abundance * L[u].
+ *   FLANK      of an end A (2u or 2u + 1): the unitigs V >> 1 for V in E(A), together with X >> 1 for X in E(V ^ 1) for those V, without u
+ *              itself -- everything that meets u's end at that junction: what u runs into, and what else runs into the same nodes.  At
+ *              most 4 + 16 entries; the tables are read as they are, palindromes get no special case.
+ *   WEAK AT A  weak(A) <=> some w in FLANK(A) has S[w] * L[u] > min_ratio * S[u] * L[w] (strict): the mean abundance of w is more than
+ *              min_ratio times that of u.  The products reach 2^87 and are compared in 128 bits.
+ *   REMOVED    rem[u] <=> cand[u], weak(2u) and weak(2u + 1).  ONE-SIDED <=> cand[u] and exactly one end is weak.
+ * min_ratio >= 2 has two consequences: two unitigs can never each be the reason the other is removed, and every removed unitig has, at
+ * each end, a flank unitig that stays in that round.  A ROUND removes the rows of all removed unitigs; the graph of the remaining rows is
+ * compacted again, and a round that removes nothing ends the loop.  dskgpu_simplify_all runs the three rules in turn. */
+typedef struct dskgpu_connection_params {
+    uint32_t max_nodes, min_ratio, max_abundance, max_rounds, reserved[4];
+} dskgpu_connection_params;                              /* 32 bytes; max_nodes 1..65535, min_ratio 2..255, max_abundance 0 = no limit, max_rounds: dskgpu_remove_connections / dskgpu_simplify_all only */
+typedef struct dskgpu_connection_stats {
+    uint64_t n_candidates, n_one_sided, n_removed, n_rows_removed, n_rounds, n_rows_left, reserved[2];
+} dskgpu_connection_stats;                               /* 64 bytes */
+typedef struct dskgpu_simplify_all_stats {
+    uint64_t n_passes, n_rows_left, reserved[6];
+    dskgpu_tip_stats tips;
+    dskgpu_bubble_stats bubbles;
+    dskgpu_connection_stats connections;
+} dskgpu_simplify_all_stats;                             /* 256 bytes */
+/* One round of the rule on the current result; no row changes.  d_row_rem u8[n_rows]: 1 = the row's unitig is removed; d_unitig_bits
+ * u8[n_unitigs]: bit 0 = candidate, bit 1 = removed, bit 2 = weak at the end 2u, bit 3 = weak at the end 2u + 1; stats: the counts of this
+ * round with n_rounds = 1 and n_rows_left = n_rows - n_rows_removed.  The outputs, their NULL rules, what the call builds, what it leaves
+ * alone and its errors are those of dskgpu_graph_bubbles; in addition min_ratio < 2 or > 255: DSKGPU_E_ARG.  Stage time: "connections"
+ * (and those of what the call built). */
+int dskgpu_graph_connections(dskgpu_ctx* ctx, const dskgpu_connection_params* params, void* d_row_rem, void* d_unitig_bits, dskgpu_connection_stats* stats);
+/* Rounds of (dskgpu_graph_connections -> dskgpu_filter_rows of the rows that are on no removed unitig) until a round removes nothing or
+ * max_rounds rounds have removed (1..64; 0 = 64; more: DSKGPU_E_ARG), with the contract of dskgpu_pop_bubbles: stats (may be NULL) holds
+ * the sums over the rounds that ran, n_rounds = the rounds that removed something, n_rows_left = the final n_rows; a round reads back one
+ * small record; an error in a later round leaves the consistent result of the rounds already done; on return the compaction and the edges
+ * of the FINAL rows are built.  Stage times: "connections", "filter rows", and those of every rebuild.  Errors: those of
+ * dskgpu_graph_connections. */
+int dskgpu_remove_connections(dskgpu_ctx* ctx, const dskgpu_connection_params* params, dskgpu_connection_stats* stats);
+/* Passes of (dskgpu_clip_tips, then dskgpu_pop_bubbles, then dskgpu_remove_connections) until a pass removes no row or max_passes passes
+ * have run (1..16; 0 = 16; more: DSKGPU_E_ARG).  A NULL parameter set skips that part; all three NULL: DSKGPU_E_ARG.  With
+ * connection_params == NULL the rows left and the tips / bubbles stats are exactly those of dskgpu_simplify.  stats (may be NULL): as for
+ * dskgpu_simplify, with the sums of the third call in connections and n_rows_left = the final n_rows in all four places.
+ * Errors: those of the three calls, checked for all sets of parameters before anything runs. */
+int dskgpu_simplify_all(dskgpu_ctx* ctx, const dskgpu_tip_params* tip_params, const dskgpu_bubble_params* bubble_params,
+                        const dskgpu_connection_params* connection_params, uint32_t max_passes, dskgpu_simplify_all_stats* stats);
+
 /* ---- connected components: the first GLOBAL question about the graph -- which pieces does it fall into, and how big is each?  Every call
  * above looks at one unitig and its neighbours.  Clipping and popping leave small isolated pieces behind -- chains of error k-mers that hang on
  * nothing, short contaminant fragments: neither tips (an isolated unitig is never clipped) nor bubbles --, which every assembler removes by
