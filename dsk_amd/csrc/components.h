@@ -12,7 +12,7 @@
 //                      trees have no cycle, every walk ends, and the root of a finished component is its smallest unitig: the label, whatever
 //                      the scheduling.  Every access to parent[] in this launch is a relaxed agent-scope atomic -- the eight L2s of the chip are
 //                      not coherent for plain loads inside a launch, and a find that spins on a stale line never ends.  The steps of one
-//                      thread are counted against 4 * n_unitigs + 64, which no walk can reach; a thread that does sets CS_BROKEN and stops
+//                      thread are counted against 4 * n_unitigs + 64, which no walk can reach; a thread that does sets CM_BROKEN and stops
 //   k_cc_flatten       a launch of its own, so plain loads: label[u] = the root above u
 //   k_cc_number        rank = the exclusive scan of (label[u] == u): comp[u] = rank[label[u]], first[rank[u]] = u for the roots
 //   k_cc_table<false>  the per-component sums, one add per unitig and column: the yardstick
@@ -21,7 +21,7 @@
 //                      the lanes that share it, their four sums by a butterfly of cross-lane adds.  The first round's sums of every wave meet
 //                      in LDS, where wave 0 adds up those of the block's leading component: one lane issues its four no-return adds, the other
 //                      components among the waves' leaders get theirs.  A second round per wave, then whatever lanes are left add for themselves
-//   k_cc_stats         per component: CS_SINGLE += (unitigs == 1), CS_MAXU / CS_MAXR = the most unitigs / rows; per block in LDS first
+//   k_cc_stats         per component: CM_SINGLE += (unitigs == 1), CM_MAXU / CM_MAXR = the most unitigs / rows; per block in LDS first
 //   k_cc_small         per component: small[c] by the rule; CR_SMALL / CR_UNITIGS / CR_ROWS of the small ones into the round's record
 //   k_cc_rows<FLAGS>   per row, through unitig[r] and comp[]: the component (u32) or the small flag of it and / or its complement (u8); four
 //                      / sixteen rows per thread, leaving as one 16-byte store where the output is 16-byte aligned
@@ -31,10 +31,10 @@
 #include "layouts.h"
 
 #define C_NONE 0xFFFFFFFFu                 // no component, no unitig
-#define C_BLOCK 1024                       // threads of a k_cc_table block: 16 waves meet in LDS
-#define C_WAVES (C_BLOCK / 64)
+#define CC_BLOCK 1024                       // threads of a k_cc_table block: 16 waves meet in LDS
+#define CC_WAVES (CC_BLOCK / 64)
 
-enum CStat { CS_BROKEN = 0, CS_SINGLE, CS_MAXU, CS_MAXR, CS_COUNT };
+enum CompStat { CM_BROKEN = 0, CM_SINGLE, CM_MAXU, CM_MAXR, CM_COUNT };
 enum CRec { CR_SMALL = 0, CR_UNITIGS, CR_ROWS, CR_SPARE, CR_COUNT };
 enum CCol { CC_UNITIGS = 0, CC_ROWS, CC_AB, CC_EDGES, CC_COUNT };      // the columns of the table: cols[col * n_c + c]
 
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(256) void k_cc_hook(const u64* __restrict__ e_offse
         if (v[i] == C_NONE || (u64)v[i] >= n_unitigs || (u64)v[i] == u) continue;      // self edges join nothing
         cc_unite(parent, (u32)u, v[i], steps);
     }
-    if (steps == 0) atomicAdd(reinterpret_cast<unsigned long long*>(&stat[CS_BROKEN]), 1ull);
+    if (steps == 0) atomicAdd(reinterpret_cast<unsigned long long*>(&stat[CM_BROKEN]), 1ull);
 }
 
 __global__ __launch_bounds__(256) void k_cc_flatten(const u32* __restrict__ parent, u64 n_unitigs, u32* __restrict__ label, u64* __restrict__ stat) {
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(256) void k_cc_flatten(const u32* __restrict__ pare
         x = p;
     }
     label[u] = x;
-    if (broken) atomicAdd(reinterpret_cast<unsigned long long*>(&stat[CS_BROKEN]), 1ull);
+    if (broken) atomicAdd(reinterpret_cast<unsigned long long*>(&stat[CM_BROKEN]), 1ull);
 }
 
 // the root flag as the scan's input
@@ -142,9 +142,9 @@ __device__ __forceinline__ void cc_wave_sums(bool mine, u64& rows, u64& ab, u32&
 }
 
 template <bool COMBINE>
-__global__ __launch_bounds__(C_BLOCK) void k_cc_table(const u32* __restrict__ comp, const u64* __restrict__ offsets, const u64* __restrict__ ab_sum,
+__global__ __launch_bounds__(CC_BLOCK) void k_cc_table(const u32* __restrict__ comp, const u64* __restrict__ offsets, const u64* __restrict__ ab_sum,
                                                       const u64* __restrict__ e_offsets, u64 n_unitigs, int k, u64 n_c, u64* __restrict__ cols) {
-    const u64 u = (u64)blockIdx.x * C_BLOCK + threadIdx.x;
+    const u64 u = (u64)blockIdx.x * CC_BLOCK + threadIdx.x;
     u32 c = C_NONE; u64 L = 0, S = 0; u32 E = 0;
     if (u < n_unitigs) {
         c = comp[u];
@@ -155,8 +155,8 @@ __global__ __launch_bounds__(C_BLOCK) void k_cc_table(const u32* __restrict__ co
         if (have) cc_add_all(cols, n_c, c, 1ull, L, S, (u64)E);
         return;
     }
-    __shared__ u32 s_key[C_WAVES], s_cnt[C_WAVES], s_edges[C_WAVES];
-    __shared__ u64 s_rows[C_WAVES], s_ab[C_WAVES];
+    __shared__ u32 s_key[CC_WAVES], s_cnt[CC_WAVES], s_edges[CC_WAVES];
+    __shared__ u64 s_rows[CC_WAVES], s_ab[CC_WAVES];
     const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     // round 1: the component of the wave's first lane; its sums go to LDS
     {
@@ -172,7 +172,7 @@ __global__ __launch_bounds__(C_BLOCK) void k_cc_table(const u32* __restrict__ co
     }
     __syncthreads();
     if (wave == 0) {                                                           // the waves' leaders: those of the block's leading component as one
-        const bool in = lane < C_WAVES;
+        const bool in = lane < CC_WAVES;
         const u32 key = in ? s_key[lane] : C_NONE, lead = s_key[0];
         const bool mine = key != C_NONE && key == lead;
         u64 r = in ? s_rows[lane] : 0ull, a = in ? s_ab[lane] : 0ull; u32 e = in ? s_edges[lane] : 0u, n = in ? s_cnt[lane] : 0u;
@@ -212,8 +212,8 @@ __global__ __launch_bounds__(256) void k_cc_stats(const u64* __restrict__ cols, 
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        if (s_single) atomicAdd(reinterpret_cast<unsigned long long*>(&stat[CS_SINGLE]), s_single);
-        atomicMax(reinterpret_cast<unsigned long long*>(&stat[CS_MAXU]), s_maxu); atomicMax(reinterpret_cast<unsigned long long*>(&stat[CS_MAXR]), s_maxr);
+        if (s_single) atomicAdd(reinterpret_cast<unsigned long long*>(&stat[CM_SINGLE]), s_single);
+        atomicMax(reinterpret_cast<unsigned long long*>(&stat[CM_MAXU]), s_maxu); atomicMax(reinterpret_cast<unsigned long long*>(&stat[CM_MAXR]), s_maxr);
     }
 }
 

@@ -2,7 +2,7 @@
 // dskgpu_components / _components_labels / _components_table / dskgpu_graph_small_components / dskgpu_drop_components (include/dskgpu.h).
 // Host side of components.h; owns dskgpu_ctx::unitigs.cc.  The build reads the tables of unitigs.hip (ensure_edges builds them) and nothing
 // else, and reads back two small records: the number of components, which sizes the table, and its counters.  The components go wherever
-// the edges go (Unitigs::release_edges / ::invalidate).  Removing the small ones is the round of tips.hip with its record, keep flags, scan
+// the edges go (Unitigs::release_edges / ::invalidate).  Removing the small ones is the round of rowfilter.hip with its record, keep flags, scan
 // and compaction (engine.h) -- one round: whole components go, so no adjacency byte of a kept row changes.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
@@ -15,8 +15,6 @@
 static_assert(CR_COUNT == REC_COUNTERS, "the small-component counters are the record's");
 
 namespace {
-
-unsigned blocks(u64 items, u64 per_block) { return (unsigned)((items + per_block - 1) / per_block); }
 
 // the scratch of the build (12 bytes per unitig + the scan's): freed when build() returns, whatever way
 struct Scratch {
@@ -35,10 +33,10 @@ int build(dskgpu_ctx* ctx) {
     if (const int rc = query_ensure(ctx, S.parent, nu * 4, "component parents")) return rc;
     if (const int rc = query_ensure(ctx, S.label, nu * 4, "component roots")) return rc;
     if (const int rc = query_ensure(ctx, S.rank, nu * 4, "component ranks")) return rc;
-    if (const int rc = query_ensure(ctx, S.stat, CS_COUNT * 8, "component counters")) return rc;
+    if (const int rc = query_ensure(ctx, S.stat, CM_COUNT * 8, "component counters")) return rc;
     u32 *parent = S.parent.as<u32>(), *label = S.label.as<u32>(), *rank = S.rank.as<u32>(); u64* stat = S.stat.as<u64>();
     const dim3 ugrid(blocks(nu, 256));
-    CK(hipMemsetAsync(stat, 0, CS_COUNT * 8, ctx->stream));
+    CK(hipMemsetAsync(stat, 0, CM_COUNT * 8, ctx->stream));
     // 1. the labelling: three launches whatever the graph
     hipLaunchKernelGGL(k_cc_init, ugrid, dim3(256), 0, ctx->stream, parent, nu);
     CKL("k_cc_init");
@@ -53,13 +51,13 @@ int build(dskgpu_ctx* ctx) {
     CK(rocprim::exclusive_scan(nullptr, tmp_bytes, flags, rank, 0u, (size_t)nu, rocprim::plus<u32>(), ctx->stream));      // LIBRARY SCAN (rocprim): plumbing, 4 bytes per unitig
     if (const int rc = query_ensure(ctx, S.tmp, tmp_bytes ? tmp_bytes : 8, "component scan")) return rc;
     CK(rocprim::exclusive_scan(S.tmp.p, tmp_bytes, flags, rank, 0u, (size_t)nu, rocprim::plus<u32>(), ctx->stream));
-    u32 h_last[2] = {0, 0}; u64 h_stat[CS_COUNT] = {0};
+    u32 h_last[2] = {0, 0}; u64 h_stat[CM_COUNT] = {0};
     CK(hipMemcpyAsync(&h_last[0], rank + (nu - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
     CK(hipMemcpyAsync(&h_last[1], label + (nu - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
     CK(hipMemcpyAsync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));
     const u64 n_c = (u64)h_last[0] + ((u64)h_last[1] == nu - 1 ? 1 : 0);
-    if (h_stat[CS_BROKEN] || n_c == 0 || n_c > nu)
+    if (h_stat[CM_BROKEN] || n_c == 0 || n_c > nu)
         return fail(ctx, DSKGPU_E_DEVICE, "dskgpu_components: the union-find did not settle, or a root is missing (internal error)");
     if (const int rc = query_ensure(ctx, X.first, n_c * 4, "component table")) return rc;
     if (const int rc = query_ensure(ctx, X.cols, CC_COUNT * n_c * 8, "component table")) return rc;
@@ -69,19 +67,19 @@ int build(dskgpu_ctx* ctx) {
     // 3. the table
     u64* cols = X.cols.as<u64>();
     CK(hipMemsetAsync(cols, 0, CC_COUNT * n_c * 8, ctx->stream));
-    const dim3 tgrid(blocks(nu, C_BLOCK));
+    const dim3 tgrid(blocks(nu, CC_BLOCK));
     const int k = (int)ctx->cfg.kmer_size;
     if (ctx->tune.cc_plain)
-        hipLaunchKernelGGL(k_cc_table<false>, tgrid, dim3(C_BLOCK), 0, ctx->stream, X.comp.as<u32>(), U.offsets.as<u64>(), U.ab_sum.as<u64>(), U.e_offsets.as<u64>(), nu, k, n_c, cols);
+        hipLaunchKernelGGL(k_cc_table<false>, tgrid, dim3(CC_BLOCK), 0, ctx->stream, X.comp.as<u32>(), U.offsets.as<u64>(), U.ab_sum.as<u64>(), U.e_offsets.as<u64>(), nu, k, n_c, cols);
     else
-        hipLaunchKernelGGL(k_cc_table<true>, tgrid, dim3(C_BLOCK), 0, ctx->stream, X.comp.as<u32>(), U.offsets.as<u64>(), U.ab_sum.as<u64>(), U.e_offsets.as<u64>(), nu, k, n_c, cols);
+        hipLaunchKernelGGL(k_cc_table<true>, tgrid, dim3(CC_BLOCK), 0, ctx->stream, X.comp.as<u32>(), U.offsets.as<u64>(), U.ab_sum.as<u64>(), U.e_offsets.as<u64>(), nu, k, n_c, cols);
     CKL("k_cc_table");
     hipLaunchKernelGGL(k_cc_stats, dim3(blocks(n_c, 256)), dim3(256), 0, ctx->stream, cols, n_c, stat);
     CKL("k_cc_stats");
     ctx->mark(ctx->tune.cc_stages ? "component table" : "components");
     CK(hipMemcpyAsync(h_stat, stat, sizeof(h_stat), hipMemcpyDeviceToHost, ctx->stream));
     CK(hipStreamSynchronize(ctx->stream));                                          // the scratch goes when this returns
-    X.stats.n_components = n_c; X.stats.n_single = h_stat[CS_SINGLE]; X.stats.max_unitigs = h_stat[CS_MAXU]; X.stats.max_rows = h_stat[CS_MAXR];
+    X.stats.n_components = n_c; X.stats.n_single = h_stat[CM_SINGLE]; X.stats.max_unitigs = h_stat[CM_MAXU]; X.stats.max_rows = h_stat[CM_MAXR];
     X.stats.n_rounds = 3;
     return DSKGPU_OK;
 }

@@ -39,10 +39,6 @@ enum CShape { C_INTERIOR = 0, C_HEAD = 1, C_TAIL = 2, C_SKIPPED = 3 };
 struct CGap { u64 e, a; u32 m, shape; };  // candidate byte, first position, windows, CShape
 template <int W> struct CBatch { static constexpr int CAND = W == 1 ? 4 : W == 2 ? 2 : 1; };      // candidates per thread of k_correct_first: 12 / 6 / 3 keys
 
-__device__ __forceinline__ void c_add64(u64* at, u64 v) {
-    (void)__hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(at), (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // stat[first + i] += the sum over the block of mine[i], i < NC: LDS first, one add per counter and block that has something.  Every thread
 // of the block calls it, once per kernel.
 template <int NC>
@@ -53,7 +49,7 @@ __device__ __forceinline__ void c_block_counts(const u32 (&mine)[NC], u64* stat,
 #pragma unroll
     for (int i = 0; i < NC; ++i) if (mine[i]) atomicAdd(&s_cnt[i], mine[i]);
     __syncthreads();
-    if (threadIdx.x < NC && s_cnt[threadIdx.x]) c_add64(stat + first + threadIdx.x, (u64)s_cnt[threadIdx.x]);
+    if (threadIdx.x < NC && s_cnt[threadIdx.x]) q_add64(stat + first + threadIdx.x, (u64)s_cnt[threadIdx.x]);
 }
 
 // Thread t: the N windows ending at bases 32 * (t / TPW) + (t % TPW) * N + j of the encoded stream, as k_query_reads.  state: nwords * 32

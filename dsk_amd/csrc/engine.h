@@ -5,9 +5,9 @@
 // rowsort.hip orders the solid rows (order_rows) and owns the row sort's state (dskgpu_ctx::rs); query.hip answers lookups in the
 // last result (dskgpu_query_*) and owns dskgpu_ctx::query; graph.hip answers the de Bruijn neighbourhood of k-mers from the same index
 // (dskgpu_graph_*); unitigs.hip compacts the rows' graph into unitigs and links them (dskgpu_unitigs*, dskgpu_unitig_edges*) and owns dskgpu_ctx::unitigs;
-// tips.hip takes rows out of a result (dskgpu_filter_rows) and finds and clips the tips of the compacted graph (dskgpu_graph_tips, dskgpu_clip_tips) and owns dskgpu_ctx::filtered;
-// bubbles.hip finds and pops the simple bubbles with the same rounds (dskgpu_graph_bubbles, dskgpu_pop_bubbles) and runs the rules in turn (dskgpu_simplify, dskgpu_simplify_all);
-// connections.hip finds and removes the erroneous connections with the same rounds (dskgpu_graph_connections, dskgpu_remove_connections);
+// rowfilter.hip takes rows out of a result (dskgpu_filter_rows), drives the rounds of (a rule -> the filter of the rows it flags) and owns dskgpu_ctx::filtered;
+// rules.hip finds and clips the tips, finds and pops the simple bubbles and finds and removes the erroneous connections of the compacted graph with those rounds
+// (dskgpu_graph_tips, dskgpu_clip_tips, dskgpu_graph_bubbles, dskgpu_pop_bubbles, dskgpu_graph_connections, dskgpu_remove_connections) and runs the rules in turn (dskgpu_simplify, dskgpu_simplify_all);
 // thread.hip threads reads through the compacted graph (dskgpu_thread_*) and owns dskgpu_ctx::threading;
 // components.hip labels the connected components of the compacted graph and takes the small ones out (dskgpu_components*, dskgpu_graph_small_components,
 // dskgpu_drop_components) and owns dskgpu_ctx::unitigs.cc;
@@ -208,13 +208,13 @@ struct Variants {
     void release() { for (DevBuf* b : {&rec, &off, &stream}) b->release(); stats = dskgpu_variant_stats{}; valid = false; }
 };
 
-// The rows that dskgpu_filter_rows kept (tips.hip): two sets of row arrays, so that a filter of filtered rows reads one set and writes the
+// The rows that dskgpu_filter_rows kept (rowfilter.hip): two sets of row arrays, so that a filter of filtered rows reads one set and writes the
 // other; cur = the set res_w / res_ab point into, -1 = the result is still the count's own.  part_off: DSKGPU_F_PARTITION_ORDER, the first
 // kept row of every partition (n_parts + 1 entries) -- rows_partition_range reads them instead of the row sort's while cur >= 0.
 // The rest is scratch: scan = the exclusive scan of the keep flags, rec = the record a round reads back ([REC_COUNTERS counters | new
 // partition offsets]), off_in = the old partition offsets on the device; info / len / bits / keep = the tip rule's per-unitig and per-row
-// bytes; the bubble rule (bubbles.hip) uses len / bits / keep too and ends = the two ends of every candidate, one word per unitig; the
-// connection rule (connections.hip) uses info / len / bits / keep.
+// bytes; the bubble rule uses len / bits / keep too and ends = the two ends of every candidate, one word per unitig; the
+// connection rule uses info / len / bits / keep (rules.hip).
 // Like the index and the compaction it is kept between calls (9 bytes per row + 14 per unitig of the largest call), so that a caller
 // who drives the rounds pays no allocation per round, and goes with the result (dskgpu_ctx::drop_result).
 struct Filtered {
@@ -393,6 +393,7 @@ struct dskgpu_ctx {
     } while (0)
 
 inline int fail(dskgpu_ctx* ctx, int code, const std::string& msg) { ctx->err = msg; return code; }
+inline unsigned blocks(u64 items, u64 per_block) { return (unsigned)((items + per_block - 1) / per_block); }      // the grid of a kernel that takes per_block items per block
 
 // dskgpu.hip
 int encode_current(dskgpu_ctx* ctx, u64* nwords_out);    // the 2-bit form of the current reads in ctx->packed / inval: encoded now, or kept (dskgpu_encode_reads)
@@ -430,7 +431,7 @@ int query_finish(dskgpu_ctx* ctx);                       // ... and the wait for
 // unitigs.hip
 int ensure_edges(dskgpu_ctx* ctx, const char* who);      // the edges of the current result's compaction: there already, or built now (opens the call's stage marks)
 
-// tips.hip: the machinery of a round that takes rows out, shared by the tip, the bubble and the connection rule.  The record of a round
+// rowfilter.hip: the machinery of a round that takes rows out, shared by the rules of rules.hip and by components.hip.  The record of a round
 // (Filtered::rec) is [REC_COUNTERS counters of the rule, zeroed | one new offset per entry of old_off]; the last new offset is the kept
 // total.  Counter REC_ROWS of every rule is the number of rows it flags
 enum { REC_COUNTERS = 4, REC_ROWS = 3 };
@@ -449,8 +450,5 @@ int round_once(dskgpu_ctx* ctx, const char* who, const char* stage, RoundEnqueue
 // rounds of (rule -> filter) until a round flags no row or max_rounds rounds have removed rows: counters[REC_COUNTERS] = the sums, *n_rounds
 int rounds_run(dskgpu_ctx* ctx, const char* who, const char* stage, u64 max_rounds, RoundEnqueue enqueue, const void* params, u64* counters, u64* n_rounds);
 
-// bubbles.hip
+// rules.hip
 int bubble_candidates(dskgpu_ctx* ctx, u32 max_nodes);   // enqueue k_bubble_candidates on the current result, whose edges are there: Filtered::ends / ::len
-
-// connections.hip
-int connection_check_params(dskgpu_ctx* ctx, const dskgpu_connection_params* p, const char* who, bool rounds);      // DSKGPU_E_ARG and its text, or DSKGPU_OK

@@ -35,6 +35,11 @@ template <int W> struct QBatch { static constexpr int N = Q_KEYS / W < 4 ? 4 : Q
 
 struct QTable { const u64* slots; u64 mask; RowsIn rows; const u32* ab; };
 
+// the no-return 64-bit add of the kernels built on this header (thread.h, correct.h): relaxed, agent scope
+__device__ __forceinline__ void q_add64(u64* at, u64 v) {
+    (void)__hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(at), (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 template <int W> __device__ __forceinline__ u64 q_hash(const KN<W>& c) {
     if constexpr (W == 1) return kmix(c.w[0]);
     else return kmix(c.w[W - 1] ^ kfold_low(c));

@@ -1,25 +1,17 @@
-// tips.hip -- rows taken out of a result on the device, and the tips of the compacted de Bruijn graph found and clipped with it:
-// dskgpu_filter_rows / dskgpu_graph_tips / dskgpu_clip_tips (include/dskgpu.h).  Host side of tips.h; owns dskgpu_ctx::filtered.
-// The filter reads the result (res_w / res_ab / n_rows) and the partition layout (rows_partition_range) and leaves both describing the
-// kept rows, in buffers of its own; the lookup index, the compaction and the edges are marked stale and built again, in the memory they
-// have, by whoever asks next.  The tip rule reads the tables of unitigs.hip (ensure_edges builds them) and nothing else.  A round of
-// dskgpu_clip_tips reads back ONE record: the four counters of the rule and the new partition offsets, the last of which is the kept total.
+// rowfilter.hip -- rows taken out of a result on the device, and the rounds of (a rule -> the filter of the rows it flags) that the graph
+// rules run with it: dskgpu_filter_rows (include/dskgpu.h), round_once / rounds_run and their parts (engine.h).  Host side of rowfilter.h;
+// owns dskgpu_ctx::filtered.  The filter reads the result (res_w / res_ab / n_rows) and the partition layout (rows_partition_range) and
+// leaves both describing the kept rows, in buffers of its own; the lookup index, the compaction and the edges are marked stale and built
+// again, in the memory they have, by whoever asks next.  A round of rounds_run reads back ONE record: the four counters of the rule and the
+// new partition offsets, the last of which is the kept total.
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
 #include "engine.h"
-#include "tips.h"
+#include "rowfilter.h"
 
-static_assert(TS_COUNT == REC_COUNTERS && TS_ROWS == REC_ROWS, "the tip rule's counters are the record's");
-
-namespace {
-
-unsigned blocks(u64 items, u64 per_block) { return (unsigned)((items + per_block - 1) / per_block); }
-
-}  // namespace
-
-// ---- the machinery of a round (engine.h), shared with bubbles.hip and connections.hip
+// ---- the machinery of a round (engine.h), shared with rules.hip and components.hip
 int abandon(dskgpu_ctx* ctx, int rc) {
     (void)hipStreamSynchronize(ctx->stream);
     ctx->marks.clear(); ctx->ev_used = 0;
@@ -165,40 +157,6 @@ int rounds_run(dskgpu_ctx* ctx, const char* who, const char* stage, u64 max_roun
     return rc;
 }
 
-namespace {
-
-// enqueue one round of the rule on the current result, whose edges are there: bits per unitig (F.bits), the counters into the record,
-// d_row_tip (may be null) and, with want_keep, the keep flags of the rows (F.keep).  n_rows > 0
-int tips_enqueue(dskgpu_ctx* ctx, const void* params, unsigned char* d_row_tip, bool want_keep) {
-    const dskgpu_tip_params& p = *static_cast<const dskgpu_tip_params*>(params);
-    Filtered& F = ctx->filtered;
-    const Unitigs& U = ctx->unitigs;
-    const u64 nu = U.stats.n_unitigs;
-    if (const int rc = query_ensure(ctx, F.info, nu, "tip candidates")) return rc;
-    if (const int rc = query_ensure(ctx, F.len, nu * 4, "tip lengths")) return rc;
-    if (const int rc = query_ensure(ctx, F.bits, nu, "tip bits")) return rc;
-    const dim3 ugrid(blocks(nu, 256));
-    hipLaunchKernelGGL(k_tip_candidates, ugrid, dim3(256), 0, ctx->stream, U.offsets.as<u64>(), U.kind.as<unsigned char>(), U.ab_sum.as<u64>(), U.e_offsets.as<u64>(), nu,
-                       (int)ctx->cfg.kmer_size, p.max_nodes, p.max_abundance, F.info.as<unsigned char>(), F.len.as<u32>());
-    CKL("k_tip_candidates");
-    hipLaunchKernelGGL(k_tip_decide, ugrid, dim3(256), 0, ctx->stream, F.info.as<unsigned char>(), F.len.as<u32>(), U.ab_sum.as<u64>(), U.e_offsets.as<u64>(),
-                       U.e_targets.as<u32>(), nu, U.e_stats.n_edges, F.bits.as<unsigned char>(), F.rec.as<u64>());
-    CKL("k_tip_decide");
-    return flag_rows(ctx, d_row_tip, want_keep);
-}
-
-int check_params(dskgpu_ctx* ctx, const dskgpu_tip_params* p, const char* who) {
-    if (!p) return fail(ctx, DSKGPU_E_ARG, std::string(who) + ": null params");
-    if (p->max_nodes == 0 || p->max_nodes > T_MAX_NODES) return fail(ctx, DSKGPU_E_ARG, std::string(who) + ": max_nodes must be in 1..65535");
-    return DSKGPU_OK;
-}
-
-void set_counters(dskgpu_tip_stats& t, const u64* h) {
-    t.n_candidates = h[TS_CAND]; t.n_tips = h[TS_TIPS]; t.n_outranked = h[TS_OUTRANKED]; t.n_rows_clipped = h[TS_ROWS];
-}
-
-}  // namespace
-
 extern "C" {
 
 int dskgpu_filter_rows(dskgpu_ctx* ctx, const void* d_keep, uint64_t* n_kept) {
@@ -213,37 +171,11 @@ int dskgpu_filter_rows(dskgpu_ctx* ctx, const void* d_keep, uint64_t* n_kept) {
     if (const int rc = begin_record(ctx, true, old_off)) return abandon(ctx, rc);
     if (const int rc = filter_scan(ctx, keep, old_off)) return abandon(ctx, rc);
     if (const int rc = read_record(ctx, h, old_off.size())) return abandon(ctx, rc);
-    if (const int rc = filter_apply(ctx, keep, h.data() + TS_COUNT, old_off.size())) return abandon(ctx, rc);
+    if (const int rc = filter_apply(ctx, keep, h.data() + REC_COUNTERS, old_off.size())) return abandon(ctx, rc);
     ctx->mark("filter rows");
     if (const int rc = query_finish(ctx)) return rc;
     if (n_kept) *n_kept = ctx->n_rows;
     return DSKGPU_OK;
-}
-
-int dskgpu_graph_tips(dskgpu_ctx* ctx, const dskgpu_tip_params* params, void* d_row_tip, void* d_unitig_tip, dskgpu_tip_stats* stats) {
-    if (!ctx) return DSKGPU_E_ARG;
-    if (!d_row_tip && !d_unitig_tip && !stats) return fail(ctx, DSKGPU_E_ARG, "dskgpu_graph_tips: no output pointer");
-    if (const int rc = check_params(ctx, params, "dskgpu_graph_tips")) return rc;
-    u64 h[REC_COUNTERS];
-    if (const int rc = round_once(ctx, "dskgpu_graph_tips", "tips", tips_enqueue, params, d_row_tip, d_unitig_tip, h)) return rc;
-    dskgpu_tip_stats t{};
-    if (ctx->n_rows) { set_counters(t, h); t.n_rounds = 1; t.n_rows_left = ctx->n_rows - t.n_rows_clipped; }
-    if (stats) *stats = t;
-    return DSKGPU_OK;
-}
-
-int dskgpu_clip_tips(dskgpu_ctx* ctx, const dskgpu_tip_params* params, dskgpu_tip_stats* stats) {
-    if (!ctx) return DSKGPU_E_ARG;
-    if (const int rc = check_params(ctx, params, "dskgpu_clip_tips")) return rc;
-    if (params->max_rounds > 64) return fail(ctx, DSKGPU_E_ARG, "dskgpu_clip_tips: max_rounds must be in 0..64");
-    u64 h[REC_COUNTERS], n_rounds;
-    dskgpu_tip_stats t{};
-    const int rc = rounds_run(ctx, "dskgpu_clip_tips", "tips", params->max_rounds ? params->max_rounds : 64, tips_enqueue, params, h, &n_rounds);
-    set_counters(t, h);
-    t.n_rounds = n_rounds;
-    t.n_rows_left = ctx->n_rows;
-    if (stats) *stats = t;
-    return rc;
 }
 
 }  // extern "C"

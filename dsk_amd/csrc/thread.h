@@ -36,10 +36,6 @@ struct TGraph { const u32* unitig; const u32* pos; const u64* offsets; u64 n_row
 struct TEdges { const u64* offsets; const u32* targets; u64 n_or, n_edges; };
 struct TWalks { u64 *offsets, *first, *last; u32 *steps, *ends; u64 n_walks, n_steps; };
 
-__device__ __forceinline__ void t_add64(u64* at, u64 v) {
-    (void)__hip_atomic_fetch_add(reinterpret_cast<unsigned long long*>(at), (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // add `mine` of every thread of the block to *counter (64 bits): LDS first, one atomic per block that has something
 __device__ __forceinline__ void t_block_count(u32 mine, u64* counter) {
     __shared__ u32 s_cnt;
@@ -47,7 +43,7 @@ __device__ __forceinline__ void t_block_count(u32 mine, u64* counter) {
     __syncthreads();
     if (mine) atomicAdd(&s_cnt, mine);
     __syncthreads();
-    if (threadIdx.x == 0 && s_cnt) t_add64(counter, (u64)s_cnt);
+    if (threadIdx.x == 0 && s_cnt) q_add64(counter, (u64)s_cnt);
 }
 
 // Thread t: the N windows ending at bases 32 * (t / TPW) + (t % TPW) * N + j of the encoded stream, as k_query_reads.  out_u / out_j: either
@@ -216,9 +212,9 @@ __global__ __launch_bounds__(256) void k_thread_emit(const u32* __restrict__ U, 
         if (head || edge) {
             if (srank < Wk.n_steps) Wk.steps[srank] = u[q];
             ++srank;
-            if (un < n_unitigs) t_add64(usup + un, 0ull - p);
+            if (un < n_unitigs) q_add64(usup + un, 0ull - p);
         }
-        if (stretch_end && un < n_unitigs) t_add64(usup + un, p + 1ull);
+        if (stretch_end && un < n_unitigs) q_add64(usup + un, p + 1ull);
         if (edge) {                                                                   // U(p) among the targets of U(p - 1)
             const u64 from = u[q - 1];
             u64 e = ~0ull;
@@ -228,11 +224,11 @@ __global__ __launch_bounds__(256) void k_thread_emit(const u32* __restrict__ U, 
                 for (u64 i = 0; i < 4; ++i)
                     if (lo + i < hi && lo + i < E.n_edges && E.targets[lo + i] == u[q]) e = lo + i;
             }
-            if (e != ~0ull) t_add64(esup + e, 1ull); else ++broken;
+            if (e != ~0ull) q_add64(esup + e, 1ull); else ++broken;
         }
         if (last && hrank >= 1 && hrank - 1 < Wk.n_walks) { Wk.last[hrank - 1] = p; Wk.ends[2 * (hrank - 1) + 1] = j[q]; }
     }
-    if (broken) t_add64(stat + TS_BROKEN, (u64)broken);
+    if (broken) q_add64(stat + TS_BROKEN, (u64)broken);
 }
 
 __global__ __launch_bounds__(256) void k_thread_maxsteps(const u64* __restrict__ offsets, u64 n_walks, u64* __restrict__ stat) {

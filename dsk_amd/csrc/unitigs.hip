@@ -18,8 +18,6 @@ RowsIn result_rows(const dskgpu_ctx* ctx) {
     return rows;
 }
 
-unsigned blocks(u64 items, u64 per_block) { return (unsigned)((items + per_block - 1) / per_block); }
-
 template <int W>
 void launch_links(dskgpu_ctx* ctx, unsigned char* adj, u32* nxt, u64* P) {
     const u64 n = ctx->n_rows;
@@ -235,7 +233,7 @@ int build_edges(dskgpu_ctx* ctx) {
 
 }  // namespace
 
-// the edges of the current result's compaction: there already, or built now (the compaction and the index below them too).  tips.hip calls it.
+// the edges of the current result's compaction: there already, or built now (the compaction and the index below them too).  rowfilter.hip calls it.
 int ensure_edges(dskgpu_ctx* ctx, const char* who) {
     if (const int rc = ensure_unitigs(ctx, who)) return rc;
     if (ctx->unitigs.e_valid) return DSKGPU_OK;

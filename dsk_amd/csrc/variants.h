@@ -2,10 +2,10 @@
 // dskgpu_variants_table / dskgpu_variants_stream (variants.hip; the definition is in include/dskgpu.h).
 //
 // Notation of bubbles.h: a candidate u is a simple path from P = in(u) ^ 1 to out(u); ends[u] = in(u) << 32 | out(u) and len[u] = L[u] come
-// from k_bubble_candidates (bubbles.h; bubble_candidates() of bubbles.hip launches it), which runs first and is not restated here.  A
+// from k_bubble_candidates (bubbles.h; bubble_candidates() of rules.hip launches it), which runs first and is not restated here.  A
 // variant is a pair a < b with b a sibling of a; its readings are A = 2 a and B = the X in E(P) that reaches b.
 //
-//   k_variant_pairs<EMIT>  per candidate a: E(P) (<= 4 targets X), then ends / len of every w = X >> 1 -- the three levels of batched gathers
+//   k_variant_pairs<EMIT>  per candidate a: E(P) (<= 4 targets X), then ends / len of every w = X >> 1 -- r_siblings of rules.h, the gather
 //                          of k_bubble_decide, without the abundance sums.  The siblings w > a, each once, ascending by w.  EMIT = false
 //                          writes their number, cnt[a]; the host scans it.  EMIT = true writes, from base[a] on, the first half of every
 //                          record (A, B, from, to) as one 16-byte store, the two line lengths of the variant stream, and flag[a] = flag[b]
@@ -30,11 +30,7 @@
 // checked against the table it is used on.
 #pragma once
 #include "graph.h"
-
-#define V_NONE 0xFFFFFFFFu                 // B_NONE of bubbles.h: no oriented unitig
-#define V_NO_ENDS 0xFFFFFFFFFFFFFFFFull    // B_NO_ENDS of bubbles.h: ends[u] of a unitig that is no candidate
-
-#define V_MAX_NODES 65535u                // B_MAX_NODES of bubbles.h: the largest max_nodes
+#include "rules.h"
 
 #define V_SNP 1u
 #define V_MULTI 2u
@@ -52,35 +48,26 @@ __global__ __launch_bounds__(256) void k_variant_pairs(const u64* __restrict__ e
                                                        u64* __restrict__ cnt, const u64* __restrict__ base, u64 n_variants, uint4* __restrict__ rec,
                                                        u64* __restrict__ vlen, unsigned char* __restrict__ flag) {
     const u64 u = (u64)blockIdx.x * 256u + threadIdx.x;
-    const u64 mine = u < n_unitigs ? ends[u] : V_NO_ENDS;
+    const u64 mine = u < n_unitigs ? ends[u] : R_NO_ENDS;
     u64 key[4] = {~0ull, ~0ull, ~0ull, ~0ull};                               // X << 32 | L[w] of a sibling w > u; all ones: none
-    u32 in = V_NONE, out = V_NONE, Lu = 0;
-    if (mine != V_NO_ENDS) {
+    u32 in = R_NONE, out = R_NONE, Lu = 0;
+    if (mine != R_NO_ENDS) {
         in = (u32)(mine >> 32); out = (u32)mine;
         const u64 P = (u64)(in ^ 1u);                                         // (in < 2 n_unitigs, k_bubble_candidates checked it: so is its flip)
         Lu = len[u];
         const u64 p0 = e_offsets[P], p1 = e_offsets[P + 1];
-        const u32 dP = (u32)min(p1 - p0, 4ull);
-        u32 X[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) X[i] = ((u32)i < dP && p0 + i < n_edges) ? e_targets[p0 + i] : V_NONE;
-        u64 we[4]; u32 wl[4];
+        u32 T[4]; RSibling s[4];
+        r_siblings<false>(p0, p1, u, ends, len, nullptr, e_targets, n_unitigs, n_edges, T, s);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const u64 w = (u64)(X[i] >> 1);
-            const bool in_table = X[i] != V_NONE && w < n_unitigs && w != u;
-            we[i] = in_table ? ends[w] : V_NO_ENDS; wl[i] = in_table ? len[w] : 0u;
-        }
+            if (s[i].ends == R_NO_ENDS) continue;
+            const bool same_ends = r_same_ends(T[i], s[i].ends, in, out);
+            const u32 wl = s[i].len, X = T[i];
+            const u32 diff = wl > Lu ? wl - Lu : Lu - wl;
+            bool take = same_ends && diff <= max_diff && (u64)(X >> 1) > u;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            if (we[i] == V_NO_ENDS) continue;                                 // (no target, u itself, or no candidate)
-            const u32 wi = (u32)(we[i] >> 32), wo = (u32)we[i];
-            const bool same_ends = (X[i] & 1u) ? (wi == out && wo == in) : (wo == out && wi == in);
-            const u32 diff = wl[i] > Lu ? wl[i] - Lu : Lu - wl[i];
-            bool take = same_ends && diff <= max_diff && (u64)(X[i] >> 1) > u;
-#pragma unroll
-            for (int j = 0; j < i; ++j) take = take && (key[j] == ~0ull || (u32)(key[j] >> 33) != (X[i] >> 1));      // (each sibling once)
-            if (take) key[i] = (u64)X[i] << 32 | (u64)wl[i];
+            for (int j = 0; j < i; ++j) take = take && (key[j] == ~0ull || (u32)(key[j] >> 33) != (X >> 1));      // (each sibling once)
+            if (take) key[i] = (u64)X << 32 | (u64)wl;
         }
         v_order(key[0], key[1]); v_order(key[2], key[3]); v_order(key[0], key[2]); v_order(key[1], key[3]); v_order(key[1], key[2]);      // ascending by w: the w are distinct
     }

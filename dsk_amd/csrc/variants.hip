@@ -11,8 +11,6 @@
 
 namespace {
 
-unsigned blocks(u64 items, u64 per_block) { return (unsigned)((items + per_block - 1) / per_block); }
-
 // the scratch of dskgpu_variants: freed when build() returns, whatever way
 // (per_unitig: one allocation for what is sized by the unitigs -- [cnt | base | tlen | toff: n_unitigs + 1 words each | stat | flag])
 struct Scratch {
@@ -122,7 +120,7 @@ extern "C" {
 int dskgpu_variants(dskgpu_ctx* ctx, const dskgpu_variant_params* params, dskgpu_variant_stats* stats) {
     if (!ctx) return DSKGPU_E_ARG;
     if (!params) return fail(ctx, DSKGPU_E_ARG, "dskgpu_variants: null params");
-    if (params->max_nodes == 0 || params->max_nodes > V_MAX_NODES) return fail(ctx, DSKGPU_E_ARG, "dskgpu_variants: max_nodes must be in 1..65535");
+    if (params->max_nodes == 0 || params->max_nodes > R_MAX_NODES) return fail(ctx, DSKGPU_E_ARG, "dskgpu_variants: max_nodes must be in 1..65535");
     if (const int rc = ensure_edges(ctx, "dskgpu_variants")) return rc;
     Variants& V = ctx->variants;
     V.release();

@@ -304,6 +304,11 @@ _lib = None
 SLICE_GATE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint32)      # dskgpu_slice_gate: 0 = the stream waits for the slice, else the count stops
 
 
+def _stats_dict(st) -> dict:
+    """a stats structure of the library -> {field: int}, without the reserved words"""
+    return {name: int(getattr(st, name)) for name, _ in st._fields_ if name != "reserved"}
+
+
 def library_path() -> str:
     return os.environ.get("DSKGPU_LIB", os.path.join(_HERE, "libdskgpu.so"))
 
@@ -835,7 +840,7 @@ class KmerCounter:
         max_nodes, stream_bytes, n_rounds."""
         st = _UnitigStats()
         self._ck(self._lib.dskgpu_unitigs(self._h, C.byref(st)))
-        return {name: int(getattr(st, name)) for name, _ in _UnitigStats._fields_ if name != "reserved"}
+        return _stats_dict(st)
 
     def unitigs_rows(self, d_unitig: int, d_pos: int) -> None:
         """d_unitig / d_pos: n_rows u32 each on the device (result order) <- the row's unitig / (position << 1) | orientation; either may be 0."""
@@ -888,7 +893,7 @@ class KmerCounter:
         the compaction below them) -> their stats: n_edges, n_self, n_dead_ends, max_degree."""
         st = _UnitigEdgeStats()
         self._ck(self._lib.dskgpu_unitig_edges(self._h, C.byref(st)))
-        return {name: int(getattr(st, name)) for name, _ in _UnitigEdgeStats._fields_ if name != "reserved"}
+        return _stats_dict(st)
 
     def unitig_edges_table(self, d_offsets: int, d_targets: int, d_ends: int) -> None:
         """d_offsets: 2 * n_unitigs + 1 u64 (CSR), d_targets: n_edges u32 (the oriented unitigs V), d_ends: 2 * n_unitigs u32 (last(U) as an
@@ -938,7 +943,7 @@ class KmerCounter:
         n_valid, n_placed, n_walks, n_steps, max_steps."""
         st = _ThreadStats()
         self._ck(self._lib.dskgpu_thread_reads(self._h, C.c_void_p(d_bytes) if d_bytes else None, nbytes, C.byref(st)))
-        self._thread_stats = {name: int(getattr(st, name)) for name, _ in _ThreadStats._fields_ if name != "reserved"}
+        self._thread_stats = _stats_dict(st)
         return dict(self._thread_stats)
 
     def thread_walks(self, d_offsets: int, d_steps: int, d_first: int, d_last: int, d_ends: int) -> None:
@@ -1019,7 +1024,7 @@ class KmerCounter:
         par, st = _CorrectParams(trust_min=trust_min), _CorrectStats()
         self._ck(self._lib.dskgpu_correct_reads(self._h, C.c_void_p(d_bytes) if d_bytes else None, nbytes, C.byref(par), C.c_void_p(d_out) if d_out else None,
                                                 C.c_void_p(d_state) if d_state else None, C.byref(st)))
-        return {name: int(getattr(st, name)) for name, _ in _CorrectStats._fields_ if name != "reserved"}
+        return _stats_dict(st)
 
     def correct_reads_tensor(self, t, trust_min: int = 0, want_state: bool = False):
         """t: CUDA uint8 tensor holding a read stream (left as it is).  -> (uint8[nbytes] the corrected stream, the stats of correct_reads
@@ -1055,10 +1060,6 @@ class KmerCounter:
         torch.cuda.current_stream(keep.device).synchronize()      # the context's stream is not torch's: the flags are written before the filter reads them
         return self.filter_rows(keep.data_ptr() if n else 0)
 
-    @staticmethod
-    def _tip_stats(st) -> dict:
-        return {name: int(getattr(st, name)) for name, _ in _TipStats._fields_ if name != "reserved"}
-
     def graph_tips(self, max_nodes: int, max_abundance: int = 0, d_row_tip: int = 0, d_unitig_tip: int = 0) -> dict:
         """One round of the tip rule on the last result, which stays as it is.  d_row_tip: n_rows bytes on the device <- 1 = the row's unitig
         is a tip; d_unitig_tip: n_unitigs bytes <- bit 0 candidate, bit 1 tip, bit 2 outranked; either may be 0.  -> the round's counts:
@@ -1066,7 +1067,7 @@ class KmerCounter:
         par, st = _TipParams(max_nodes=max_nodes, max_abundance=max_abundance), _TipStats()
         self._ck(self._lib.dskgpu_graph_tips(self._h, C.byref(par), C.c_void_p(d_row_tip) if d_row_tip else None,
                                              C.c_void_p(d_unitig_tip) if d_unitig_tip else None, C.byref(st)))
-        return self._tip_stats(st)
+        return _stats_dict(st)
 
     def graph_tips_tensor(self, max_nodes: int, max_abundance: int = 0):
         """-> (uint8[n_rows] row is on a tip, uint8[n_unitigs] candidate | tip << 1 | outranked << 2, the stats of graph_tips), CUDA tensors."""
@@ -1086,13 +1087,9 @@ class KmerCounter:
         par = _TipParams(max_nodes=self.kmer_size if max_nodes is None else max_nodes, max_abundance=max_abundance, max_rounds=max_rounds)
         st = _TipStats()
         self._ck(self._lib.dskgpu_clip_tips(self._h, C.byref(par), C.byref(st)))
-        return self._tip_stats(st)
+        return _stats_dict(st)
 
     # -- the simple bubbles of the compacted graph, and tips and bubbles in turn (include/dskgpu.h: dskgpu_graph_bubbles / _pop_bubbles / _simplify)
-    @staticmethod
-    def _bubble_stats(st) -> dict:
-        return {name: int(getattr(st, name)) for name, _ in _BubbleStats._fields_ if name != "reserved"}
-
     def graph_bubbles(self, max_nodes: int, max_diff: int = 4, d_row_pop: int = 0, d_unitig_bits: int = 0) -> dict:
         """One round of the bubble rule on the last result, which stays as it is.  d_row_pop: n_rows bytes on the device <- 1 = the row's
         unitig is popped; d_unitig_bits: n_unitigs bytes <- bit 0 candidate, bit 1 popped, bit 2 in a bubble; either may be 0.  -> the
@@ -1100,7 +1097,7 @@ class KmerCounter:
         par, st = _BubbleParams(max_nodes=max_nodes, max_diff=max_diff), _BubbleStats()
         self._ck(self._lib.dskgpu_graph_bubbles(self._h, C.byref(par), C.c_void_p(d_row_pop) if d_row_pop else None,
                                                 C.c_void_p(d_unitig_bits) if d_unitig_bits else None, C.byref(st)))
-        return self._bubble_stats(st)
+        return _stats_dict(st)
 
     def graph_bubbles_tensor(self, max_nodes: int, max_diff: int = 4):
         """-> (uint8[n_rows] row is popped, uint8[n_unitigs] candidate | popped << 1 | in a bubble << 2, the stats of graph_bubbles), CUDA tensors."""
@@ -1120,7 +1117,7 @@ class KmerCounter:
         par = _BubbleParams(max_nodes=2 * self.kmer_size if max_nodes is None else max_nodes, max_diff=max_diff, max_rounds=max_rounds)
         st = _BubbleStats()
         self._ck(self._lib.dskgpu_pop_bubbles(self._h, C.byref(par), C.byref(st)))
-        return self._bubble_stats(st)
+        return _stats_dict(st)
 
     def simplify(self, tips: Optional[dict] = None, bubbles: Optional[dict] = None, max_passes: int = 0) -> dict:
         """Passes of (clip_tips, then pop_bubbles) until a pass removes no row or max_passes (0 = 16) passes have run.  tips / bubbles: the
@@ -1130,35 +1127,31 @@ class KmerCounter:
         tp, bp = self._tip_params_of(tips), self._bubble_params_of(bubbles)
         st = _SimplifyStats()
         self._ck(self._lib.dskgpu_simplify(self._h, C.byref(tp) if tp is not None else None, C.byref(bp) if bp is not None else None, max_passes, C.byref(st)))
-        return {"n_passes": int(st.n_passes), "n_rows_left": int(st.n_rows_left), "tips": self._tip_stats(st.tips), "bubbles": self._bubble_stats(st.bubbles)}
+        return {"n_passes": int(st.n_passes), "n_rows_left": int(st.n_rows_left), "tips": _stats_dict(st.tips), "bubbles": _stats_dict(st.bubbles)}
+
+    def _rule_params(self, who, part, cls, args, nodes, **defaults):
+        """a part of simplify / simplify_all -> its parameter structure: args is a dict of the rule's keyword arguments, None = its defaults,
+        False = no such part (-> None).  max_nodes None = nodes * kmer_size; defaults: the rule's other arguments"""
+        if args is False:
+            return None
+        a = dict(args or {})
+        mn = a.pop("max_nodes", None)
+        par = cls(max_nodes=nodes * self.kmer_size if mn is None else mn, max_rounds=a.pop("max_rounds", 0), **{k: a.pop(k, v) for k, v in defaults.items()})
+        if a:
+            raise TypeError("%s: unknown %s arguments %s" % (who, part, sorted(a)))
+        return par
 
     def _tip_params_of(self, tips):
-        """the tip part of simplify / simplify_all: a dict of clip_tips' keyword arguments, None = its defaults, False = no such part"""
-        if tips is False:
-            return None
-        a = dict(tips or {})
-        mn = a.pop("max_nodes", None)
-        tp = _TipParams(max_nodes=self.kmer_size if mn is None else mn, max_abundance=a.pop("max_abundance", 0), max_rounds=a.pop("max_rounds", 0))
-        if a:
-            raise TypeError("simplify: unknown tip arguments %s" % sorted(a))
-        return tp
+        return self._rule_params("simplify", "tip", _TipParams, tips, 1, max_abundance=0)
 
     def _bubble_params_of(self, bubbles):
-        if bubbles is False:
-            return None
-        a = dict(bubbles or {})
-        mn = a.pop("max_nodes", None)
-        bp = _BubbleParams(max_nodes=2 * self.kmer_size if mn is None else mn, max_diff=a.pop("max_diff", 4), max_rounds=a.pop("max_rounds", 0))
-        if a:
-            raise TypeError("simplify: unknown bubble arguments %s" % sorted(a))
-        return bp
+        return self._rule_params("simplify", "bubble", _BubbleParams, bubbles, 2, max_diff=4)
+
+    def _connection_params_of(self, connections):
+        return self._rule_params("simplify_all", "connection", _ConnectionParams, connections, 2, min_ratio=4, max_abundance=0)
 
     # -- the erroneous connections of the compacted graph, and all three rules in turn (include/dskgpu.h: dskgpu_graph_connections /
     # _remove_connections / _simplify_all)
-    @staticmethod
-    def _connection_stats(st) -> dict:
-        return {name: int(getattr(st, name)) for name, _ in _ConnectionStats._fields_ if name != "reserved"}
-
     def graph_connections(self, max_nodes: int, min_ratio: int = 4, max_abundance: int = 0, d_row_rem: int = 0, d_unitig_bits: int = 0) -> dict:
         """One round of the erroneous-connection rule on the last result, which stays as it is.  d_row_rem: n_rows bytes on the device <- 1 =
         the row's unitig is removed; d_unitig_bits: n_unitigs bytes <- bit 0 candidate, bit 1 removed, bit 2 weak at the end 2u, bit 3 weak
@@ -1167,7 +1160,7 @@ class KmerCounter:
         par, st = _ConnectionParams(max_nodes=max_nodes, min_ratio=min_ratio, max_abundance=max_abundance), _ConnectionStats()
         self._ck(self._lib.dskgpu_graph_connections(self._h, C.byref(par), C.c_void_p(d_row_rem) if d_row_rem else None,
                                                     C.c_void_p(d_unitig_bits) if d_unitig_bits else None, C.byref(st)))
-        return self._connection_stats(st)
+        return _stats_dict(st)
 
     def graph_connections_tensor(self, max_nodes: int, min_ratio: int = 4, max_abundance: int = 0):
         """-> (uint8[n_rows] row is removed, uint8[n_unitigs] candidate | removed << 1 | weak at 2u << 2 | weak at 2u + 1 << 3, the stats of
@@ -1189,25 +1182,18 @@ class KmerCounter:
                                 max_rounds=max_rounds)
         st = _ConnectionStats()
         self._ck(self._lib.dskgpu_remove_connections(self._h, C.byref(par), C.byref(st)))
-        return self._connection_stats(st)
+        return _stats_dict(st)
 
     def simplify_all(self, tips: Optional[dict] = None, bubbles: Optional[dict] = None, connections: Optional[dict] = None, max_passes: int = 0) -> dict:
         """Passes of (clip_tips, pop_bubbles, then remove_connections) until a pass removes no row or max_passes (0 = 16) passes have run.
         tips / bubbles / connections: the keyword arguments of clip_tips / pop_bubbles / remove_connections (None = their defaults), or
         False to skip that part.  On return the unitigs and the edges of the rows left are built.  -> {n_passes, n_rows_left, tips,
         bubbles, connections: the sums of the three calls' dicts}."""
-        tp, bp, cp = self._tip_params_of(tips), self._bubble_params_of(bubbles), None
-        if connections is not False:
-            a = dict(connections or {})
-            mn = a.pop("max_nodes", None)
-            cp = _ConnectionParams(max_nodes=2 * self.kmer_size if mn is None else mn, min_ratio=a.pop("min_ratio", 4), max_abundance=a.pop("max_abundance", 0),
-                                   max_rounds=a.pop("max_rounds", 0))
-            if a:
-                raise TypeError("simplify_all: unknown connection arguments %s" % sorted(a))
+        tp, bp, cp = self._tip_params_of(tips), self._bubble_params_of(bubbles), self._connection_params_of(connections)
         st = _SimplifyAllStats()
         self._ck(self._lib.dskgpu_simplify_all(self._h, *(C.byref(x) if x is not None else None for x in (tp, bp, cp)), max_passes, C.byref(st)))
-        return {"n_passes": int(st.n_passes), "n_rows_left": int(st.n_rows_left), "tips": self._tip_stats(st.tips), "bubbles": self._bubble_stats(st.bubbles),
-                "connections": self._connection_stats(st.connections)}
+        return {"n_passes": int(st.n_passes), "n_rows_left": int(st.n_rows_left), "tips": _stats_dict(st.tips), "bubbles": _stats_dict(st.bubbles),
+                "connections": _stats_dict(st.connections)}
 
     # -- the bubbles of the compacted graph reported as variants (include/dskgpu.h: dskgpu_variants / _variants_table / _variants_stream)
     def variants(self, max_nodes: Optional[int] = None, max_diff: int = 4) -> dict:
@@ -1274,16 +1260,12 @@ class KmerCounter:
         return {name: st[name] for name in ("n_variants", "n_snps", "n_multi", "n_indels", "n_complex")}
 
     # -- the connected components of the compacted graph (include/dskgpu.h: dskgpu_components* / _graph_small_components / _drop_components)
-    @staticmethod
-    def _drop_stats(st) -> dict:
-        return {name: int(getattr(st, name)) for name, _ in _ComponentDropStats._fields_ if name != "reserved"}
-
     def components(self) -> dict:
         """Build the components of the last result's compacted graph (the edges, the compaction and the index too when they are not there)
         -> the stats: n_components, n_single, max_unitigs, max_rows, n_rounds (launches of the labelling)."""
         st = _ComponentStats()
         self._ck(self._lib.dskgpu_components(self._h, C.byref(st)))
-        return {name: int(getattr(st, name)) for name, _ in _ComponentStats._fields_ if name != "reserved"}
+        return _stats_dict(st)
 
     def components_labels(self, d_unitig_comp: int, d_row_comp: int) -> None:
         """d_unitig_comp: n_unitigs u32 on the device <- the component of every unitig; d_row_comp: n_rows u32 <- that of every row's unitig;
@@ -1325,7 +1307,7 @@ class KmerCounter:
         par, st = _ComponentParams(min_rows=min_rows, max_abundance=max_abundance), _ComponentDropStats()
         self._ck(self._lib.dskgpu_graph_small_components(self._h, C.byref(par), C.c_void_p(d_row_drop) if d_row_drop else None,
                                                          C.c_void_p(d_comp_small) if d_comp_small else None, C.byref(st)))
-        return self._drop_stats(st)
+        return _stats_dict(st)
 
     def small_components_tensor(self, min_rows: int, max_abundance: int = 0):
         """-> (uint8[n_rows] the row's component is small, uint8[n_components] small, the stats of small_components), CUDA tensors."""
@@ -1343,7 +1325,7 @@ class KmerCounter:
         edges and the components of the rows left are built.  -> n_small, n_unitigs_dropped, n_rows_dropped, n_rows_left."""
         par, st = _ComponentParams(min_rows=min_rows, max_abundance=max_abundance), _ComponentDropStats()
         self._ck(self._lib.dskgpu_drop_components(self._h, C.byref(par), C.byref(st)))
-        return self._drop_stats(st)
+        return _stats_dict(st)
 
     # -- kernel-level entry points (parity tests)
     def k_encode(self, d_bytes: int, nbytes: int, d_packed: int, d_invalid: int) -> None:

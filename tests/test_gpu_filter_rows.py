@@ -1,4 +1,4 @@
-"""Rows taken out of a result on the device (include/dskgpu.h: dskgpu_filter_rows; csrc/tips.h: k_rows_compact, k_filter_offsets).
+"""Rows taken out of a result on the device (include/dskgpu.h: dskgpu_filter_rows; csrc/rowfilter.h: k_rows_compact, k_filter_offsets).
 
 All comparisons are exact.  A seeded random mask keeps about half the rows; afterwards rows() must be rows()[mask], the partitions must
 describe the kept rows, the count's stats and histogram must be untouched, and every consumer of the result -- lookups, unitigs, edges --

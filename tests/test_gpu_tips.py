@@ -1,5 +1,5 @@
 """The tips of the compacted de Bruijn graph, found and clipped on the device (include/dskgpu.h: dskgpu_graph_tips / dskgpu_clip_tips;
-csrc/tips.h).
+csrc/tips.h on the helpers of csrc/rules.h; the rows go through csrc/rowfilter.h).
 
 All comparisons are exact.  Tests 1 to 3 compare the device with the restatement of tests/test_tips_restatement.py, made of the rows as the
 context returns them: the bits of every unitig, the flag of every row, the stats of a round, and the rows a clip leaves.  Test 4 needs no
