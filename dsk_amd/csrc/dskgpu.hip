@@ -1865,6 +1865,7 @@ void dskgpu_destroy(dskgpu_ctx* ctx) {
     ctx->unitigs.release();
     ctx->threading.release();
     ctx->variants.release();
+    ctx->readsum.release();
     ctx->filtered.release();
     if (ctx->land) (void)hipHostFree(ctx->land);
     for (DevBuf* b : bufs) b->release();

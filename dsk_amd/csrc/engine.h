@@ -12,7 +12,9 @@
 // components.hip labels the connected components of the compacted graph and takes the small ones out (dskgpu_components*, dskgpu_graph_small_components,
 // dskgpu_drop_components) and owns dskgpu_ctx::unitigs.cc;
 // correct.hip corrects substitution errors in a read stream against the rows (dskgpu_correct_reads) and keeps nothing;
-// variants.hip reports the bubbles as pairs of sequences (dskgpu_variants*) and owns dskgpu_ctx::variants.  Private to the library.
+// variants.hip reports the bubbles as pairs of sequences (dskgpu_variants*) and owns dskgpu_ctx::variants;
+// readsum.hip summarises the abundances of every read of a stream, marks the reads by a rule and takes reads out of a stream
+// (dskgpu_read_summaries*, dskgpu_read_marks, dskgpu_select_reads) and owns dskgpu_ctx::readsum.  Private to the library.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -208,6 +210,14 @@ struct Variants {
     void release() { for (DevBuf* b : {&rec, &off, &stream}) b->release(); stats = dskgpu_variant_stats{}; valid = false; }
 };
 
+// The per-read summaries of a stream (readsum.hip), kept by dskgpu_read_summaries until the rows change: 32 bytes per record.
+struct ReadSummaries {
+    DevBuf table;
+    dskgpu_read_summary_stats stats{};
+    bool valid = false;            // a table of the current result is kept (dskgpu_ctx::drop_result and dskgpu_filter_rows drop it)
+    void release() { table.release(); stats = dskgpu_read_summary_stats{}; valid = false; }
+};
+
 // The rows that dskgpu_filter_rows kept (rowfilter.hip): two sets of row arrays, so that a filter of filtered rows reads one set and writes the
 // other; cur = the set res_w / res_ab point into, -1 = the result is still the count's own.  part_off: DSKGPU_F_PARTITION_ORDER, the first
 // kept row of every partition (n_parts + 1 entries) -- rows_partition_range reads them instead of the row sort's while cur >= 0.
@@ -343,10 +353,11 @@ struct dskgpu_ctx {
     Unitigs unitigs;
     Threading threading;
     Variants variants;
+    ReadSummaries readsum;
     Filtered filtered;
     // a count starts, or its result is not to be read: the index of the old rows and their unitigs go with them, and so does their memory
     // -- up to 32 + 8 bytes per row that the count about to run may need (a no-op for a context that was never queried)
-    void drop_result() { have_result = false; query.release(); unitigs.release(); threading.release(); variants.release(); filtered.release(); }
+    void drop_result() { have_result = false; query.release(); unitigs.release(); threading.release(); variants.release(); readsum.release(); filtered.release(); }
     // the read stream changed: what was learnt about the old reads -- their kept encoding apart (enc_keep: the caller's to clear) -- goes
     void reads_changed() { enc_fresh = false; sender.prepared = false; sender.exact = false; opt2_off = false; opt1_off = false; mw_v3_off = false; rec_l0_off = false; last_rows = 0; }
 

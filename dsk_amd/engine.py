@@ -116,6 +116,52 @@ class _CorrectStats(C.Structure):
     ]
 
 
+class _ReadSummaryParams(C.Structure):
+    _fields_ = [
+        ("trust_min", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint64 * 3),
+    ]
+
+
+class _ReadSummaryStats(C.Structure):
+    _fields_ = [
+        ("n_records", C.c_uint64),
+        ("n_empty", C.c_uint64),
+        ("n_valid", C.c_uint64),
+        ("n_solid", C.c_uint64),
+        ("max_len", C.c_uint64),
+        ("reserved", C.c_uint64 * 3),
+    ]
+
+
+class _ReadRule(C.Structure):
+    _fields_ = [
+        ("min_valid", C.c_uint32),
+        ("median_min", C.c_uint32),
+        ("median_max", C.c_uint32),
+        ("solid_num", C.c_uint32),
+        ("solid_den", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint64),
+    ]
+
+
+class _ReadMarkStats(C.Structure):
+    _fields_ = [
+        ("n_records", C.c_uint64),
+        ("n_kept", C.c_uint64),
+        ("kept_bytes", C.c_uint64),
+        ("kept_valid", C.c_uint64),
+        ("reserved", C.c_uint64 * 4),
+    ]
+
+
+# one summary of dskgpu_read_summaries_table (include/dskgpu.h: SUMMARY), 32 bytes
+READ_SUMMARY_DTYPE = np.dtype([("start", "<u8"), ("sum", "<u8"), ("len", "<u4"), ("n_valid", "<u4"), ("n_solid", "<u4"), ("median", "<u4")])
+READS_INVERT = 1
+
+
 class _TipParams(C.Structure):
     _fields_ = [
         ("max_nodes", C.c_uint32),
@@ -291,6 +337,7 @@ EXPORTS = [
     "dskgpu_components", "dskgpu_components_labels", "dskgpu_components_table", "dskgpu_graph_small_components", "dskgpu_drop_components",
     "dskgpu_thread_place", "dskgpu_thread_reads", "dskgpu_thread_walks", "dskgpu_thread_support",
     "dskgpu_correct_reads",
+    "dskgpu_read_summaries", "dskgpu_read_summaries_table", "dskgpu_read_marks", "dskgpu_select_reads",
     "dskgpu_variants", "dskgpu_variants_table", "dskgpu_variants_stream",
     "dskgpu_k_encode", "dskgpu_k_enumerate", "dskgpu_k_minimizers",
     "dskgpu_group_create", "dskgpu_group_destroy", "dskgpu_group_last_error", "dskgpu_group_size", "dskgpu_group_ctx",
@@ -439,6 +486,14 @@ def load_library():
     lib.dskgpu_thread_support.restype = C.c_int
     lib.dskgpu_correct_reads.argtypes = [vp, vp, u64, C.POINTER(_CorrectParams), vp, vp, C.POINTER(_CorrectStats)]
     lib.dskgpu_correct_reads.restype = C.c_int
+    lib.dskgpu_read_summaries.argtypes = [vp, vp, u64, C.POINTER(_ReadSummaryParams), C.POINTER(_ReadSummaryStats)]
+    lib.dskgpu_read_summaries.restype = C.c_int
+    lib.dskgpu_read_summaries_table.argtypes = [vp, vp]
+    lib.dskgpu_read_summaries_table.restype = C.c_int
+    lib.dskgpu_read_marks.argtypes = [vp, C.POINTER(_ReadRule), vp, C.POINTER(_ReadMarkStats)]
+    lib.dskgpu_read_marks.restype = C.c_int
+    lib.dskgpu_select_reads.argtypes = [vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
+    lib.dskgpu_select_reads.restype = C.c_int
     lib.dskgpu_k_encode.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_enumerate.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_minimizers.argtypes = [vp, vp, u64, vp, vp]
@@ -1039,6 +1094,68 @@ class KmerCounter:
         torch.cuda.current_stream(t.device).synchronize()          # the context's stream is not torch's: what torch enqueued is done before the kernels run
         st = self.correct_reads(t.data_ptr() if n else 0, n, out.data_ptr() if n else 0, state.data_ptr() if want_state and n else 0, trust_min)
         return (out, st, state) if want_state else (out, st)
+
+    # -- per-read abundance summaries and read selection (include/dskgpu.h: dskgpu_read_summaries / _read_summaries_table / _read_marks / dskgpu_select_reads)
+    def read_summaries(self, d_bytes: int, nbytes: int, trust_min: int = 0) -> dict:
+        """d_bytes: a read stream on the device.  Builds the summary of every record (what lies between two newlines) against the last
+        result and keeps the table in the context until the rows change.  trust_min: the abundance from which a position is solid (0, 1:
+        any row).  -> the stats: n_records, n_empty (no valid window), n_valid, n_solid, max_len."""
+        par, st = _ReadSummaryParams(trust_min=trust_min), _ReadSummaryStats()
+        self._ck(self._lib.dskgpu_read_summaries(self._h, C.c_void_p(d_bytes) if d_bytes else None, nbytes, C.byref(par), C.byref(st)))
+        self._read_summary_stats = _stats_dict(st)
+        return dict(self._read_summary_stats)
+
+    def read_summaries_table(self, d_records: int) -> None:
+        """d_records: 32 * n_records bytes on the device <- start u64, sum u64, len, n_valid, n_solid, median u32 of every record of the
+        kept table (READ_SUMMARY_DTYPE)."""
+        self._ck(self._lib.dskgpu_read_summaries_table(self._h, C.c_void_p(d_records) if d_records else None))
+
+    def read_summaries_numpy(self) -> np.ndarray:
+        """-> the kept table as a numpy array of READ_SUMMARY_DTYPE, one element per record of the stream the last read_summaries() of this
+        object took (when the library has dropped the table since, the call raises DSKGPU_E_STATE)."""
+        import torch
+        n = (getattr(self, "_read_summary_stats", None) or {"n_records": 0})["n_records"]
+        dev = torch.device("cuda", self.device)
+        rec = torch.zeros((max(n, 1), 4), dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()              # the context's stream is not torch's: the zero fill is done before the copy writes
+        self.read_summaries_table(rec.data_ptr())
+        return rec[:n].cpu().numpy().view(READ_SUMMARY_DTYPE).reshape(n).copy()
+
+    def read_marks(self, d_keep: int = 0, min_valid: int = 0, median_min: int = 0, median_max: int = 0, solid_num: int = 0, solid_den: int = 0,
+                   invert: bool = False) -> dict:
+        """The rule applied to the kept table: a record is kept when n_valid >= min_valid, median >= median_min, median <= median_max
+        (0: no upper bound) and n_solid / n_valid >= solid_num / solid_den (solid_den 0: no bound); invert flips the answer.  d_keep:
+        n_records bytes on the device <- 1 or 0; 0: the stats only.  -> the stats: n_records, n_kept, kept_bytes (the bytes of the
+        selection by these marks), kept_valid."""
+        rule, st = _ReadRule(min_valid=min_valid, median_min=median_min, median_max=median_max, solid_num=solid_num, solid_den=solid_den,
+                             flags=READS_INVERT if invert else 0), _ReadMarkStats()
+        self._ck(self._lib.dskgpu_read_marks(self._h, C.byref(rule), C.c_void_p(d_keep) if d_keep else None, C.byref(st)))
+        return _stats_dict(st)
+
+    def select_reads(self, d_bytes: int, nbytes: int, d_keep: int, n_records: int, d_out: int = 0, capacity: int = 0) -> Tuple[int, int]:
+        """The records of the stream whose byte in d_keep (n_records of them, on the device) is non-zero -> d_out, in stream order, each with
+        one newline behind it.  d_out 0: a sizing run.  Stateless: no result is needed.  -> (out_bytes, out_records)."""
+        ob, orec = C.c_uint64(0), C.c_uint64(0)
+        self._ck(self._lib.dskgpu_select_reads(self._h, C.c_void_p(d_bytes) if d_bytes else None, nbytes, C.c_void_p(d_keep) if d_keep else None, n_records,
+                                               C.c_void_p(d_out) if d_out else None, capacity, C.byref(ob), C.byref(orec)))
+        return int(ob.value), int(orec.value)
+
+    def select_reads_tensor(self, stream, keep):
+        """stream: CUDA uint8 tensor holding a read stream; keep: CUDA uint8 (or bool) tensor, one element per record, non-zero = keep.
+        A sizing run, one allocation, the selection.  -> uint8[out_bytes], the kept records."""
+        import torch
+        if not stream.is_cuda or stream.dtype != torch.uint8 or not keep.is_cuda or keep.dtype not in (torch.uint8, torch.bool):
+            raise ValueError("select_reads_tensor: CUDA tensors are needed, uint8 for the stream and uint8 or bool for the flags")
+        stream, keep = stream.contiguous(), keep.contiguous().view(torch.uint8)
+        n, nr = stream.numel(), keep.numel()
+        torch.cuda.current_stream(stream.device).synchronize()    # the context's stream is not torch's: what torch enqueued is done before the kernels run
+        args = (stream.data_ptr() if n else 0, n, keep.data_ptr() if nr else 0, nr)
+        need, _ = self.select_reads(*args)
+        out = torch.empty(need, dtype=torch.uint8, device=stream.device)
+        if need:
+            torch.cuda.current_stream(stream.device).synchronize()
+            self.select_reads(*args, out.data_ptr(), need)
+        return out
 
     # -- rows out of a result, and the tips of the compacted graph (include/dskgpu.h: dskgpu_filter_rows / _graph_tips / _clip_tips)
     def filter_rows(self, d_keep: int) -> int:

@@ -784,6 +784,80 @@ typedef struct dskgpu_correct_stats {
 int dskgpu_correct_reads(dskgpu_ctx* ctx, const void* d_bytes, uint64_t nbytes, const dskgpu_correct_params* params, void* d_out, void* d_state,
                          dskgpu_correct_stats* stats);
 
+/* ---- per-read abundance summaries and read selection: a count is also a spectrum that says something about each READ.  The calls above
+ * answer per position (dskgpu_query_reads, dskgpu_correct_reads, dskgpu_thread_place); these answer per read and take reads out of a
+ * stream: "keep the reads whose median k-mer abundance is between 5 and 80", "drop the reads with fewer than 90 % solid k-mers", "drop the
+ * reads that hit this contaminant set at all" -- khmer's filter-abund and slice-reads-by-coverage, the static half of digital
+ * normalisation, BBDuk-style screening -- without copying 4 bytes per base to the host.
+ *   RECORD     The stream is cut at the bytes 0x0A.  Record i is the bytes between the (i-1)-th and the i-th '\n', with neither included.
+ *              start_i is its first byte and len_i its length.  A record may be empty (two '\n' in a row, or a '\n' at byte 0).
+ *              n_records = the number of '\n', plus 1 when nbytes > 0 and the last byte is not '\n'.  Any other non-ACGT byte (N, '\r',
+ *              IUPAC) lies inside a record and only ends windows, as the input convention says.  A '\n' ends every window, so no window
+ *              spans two records.
+ *   VALUE      of a position p in a record.  valid(p) is exactly dskgpu_k_enumerate's validity.  For a valid p, a(p) is what
+ *              dskgpu_query_reads answers: the row's abundance, or 0 when the k-mer is no row.  p is SOLID when it is valid and
+ *              a(p) >= max(trust_min, 1).
+ *   SUMMARY    of record i, 32 bytes, in this order:
+ *                start    u64  start_i
+ *                sum      u64  sum of a(p) over the valid positions of the record
+ *                len      u32  len_i
+ *                n_valid  u32  valid positions
+ *                n_solid  u32  SOLID positions
+ *                median   u32  the values a(p) of the valid positions, sorted ascending: the element of index n_valid / 2 (integer
+ *                              division, khmer's convention).  0 when n_valid == 0.
+ *              A record longer than 2^32 - 1 bytes gives DSKGPU_E_ARG, and the error text says so.  The stream's length limit is that of
+ *              dskgpu_query_reads.
+ *   RULE       Record i is KEPT when all of the following hold: n_valid >= min_valid; median >= median_min; median_max == 0 or
+ *              median <= median_max; solid_den == 0 or (u64)n_solid * solid_den >= (u64)solid_num * n_valid.  With flag bit 0
+ *              (DSKGPU_READS_INVERT) the answer is flipped.  A null rule keeps everything.  Other flag bits or non-zero reserved words
+ *              give DSKGPU_E_ARG.
+ *   SELECTION  The kept records, in stream order, each followed by one '\n'.  out_bytes = sum over kept records of len + 1.
+ *              out_records = the number of kept records.  A last record without a '\n' gets one.  Selecting with every flag set from a
+ *              stream that ends in '\n' reproduces the stream.
+ * dskgpu_read_summaries builds the table of the stream's summaries and keeps it in the context, the way a threading is kept.  It runs on the
+ * context's stream, is synchronous on return, builds the lookup index on first use and encodes the stream into scratch of its own, freed
+ * before it returns; it leaves the reads (a kept encoding included), the result, the stats, the sender state and every graph table alone.
+ * Every k in 1..128, either row order, several passes.  One context: a rank of a group holds only the k-mers it owns, so world_size > 1
+ * gives DSKGPU_E_STATE, as for the correction.  d_bytes: the stream on the device, any alignment.  params: NULL = the defaults (trust_min 0);
+ * flags and reserved must be 0.  stats (may be NULL): n_records; n_empty = the records with n_valid == 0; n_valid and n_solid = the sums over
+ * the records; max_len = the longest record.
+ * Lifetime of the kept table: dropped by the next count, by dskgpu_filter_rows and everything built on it (dskgpu_clip_tips / _pop_bubbles /
+ * _remove_connections / _simplify / _simplify_all / _drop_components), by the next dskgpu_read_summaries and by dskgpu_destroy.
+ * Memory: while it runs, the 2-bit form of the stream (0.375 bytes per stream byte) + 4.125 bytes per stream byte for the values and the
+ * valid bits + 8 bytes per record for the record ends and 8 per record longer than the wave path takes (+ 16 bytes per 4096 stream bytes of
+ * block sums); what it keeps is 32 bytes per record.  dskgpu_select_reads takes, and frees before it returns, 24 bytes per record (+ the
+ * block sums).  A stream too big for the free HBM can be summarised and selected in pieces cut behind any '\n'.
+ * Stage times: "read values", "read records", "read summaries" (dskgpu_read_summaries), "read records", "read select"
+ * (dskgpu_select_reads), plus "query index" when the call builds the index.
+ * Errors: a null ctx, a null d_bytes with nbytes > 0, non-zero flags or reserved words, a stream longer than one launch of the read frame
+ * takes (as dskgpu_query_reads), a record longer than 2^32 - 1 bytes: DSKGPU_E_ARG; no result DSKGPU_E_STATE; a context with world_size > 1
+ * DSKGPU_E_STATE (the text says so); a table or marks call when no table is kept DSKGPU_E_STATE; DSKGPU_E_NOMEM leaves the context, its
+ * result and what was built before usable.  After a failed dskgpu_read_summaries no table is kept.  nbytes == 0: DSKGPU_OK, all-zero stats,
+ * a table of zero records is kept: the table call writes nothing, the marks call gives all-zero stats.  A result with zero rows: every value
+ * is 0, so every sum, n_solid and median is 0; n_valid is still counted. */
+#define DSKGPU_READS_INVERT 1u                           /* dskgpu_read_rule.flags bit 0: keep what the rule would drop */
+typedef struct dskgpu_read_summary_params { uint32_t trust_min, flags; uint64_t reserved[3]; } dskgpu_read_summary_params;     /* 32 bytes; flags and reserved must be 0 */
+typedef struct dskgpu_read_summary_stats  { uint64_t n_records, n_empty, n_valid, n_solid, max_len, reserved[3]; } dskgpu_read_summary_stats;  /* 64 bytes */
+typedef struct dskgpu_read_rule           { uint32_t min_valid, median_min, median_max, solid_num, solid_den, flags; uint64_t reserved; } dskgpu_read_rule; /* 32 bytes */
+typedef struct dskgpu_read_mark_stats     { uint64_t n_records, n_kept, kept_bytes, kept_valid, reserved[4]; } dskgpu_read_mark_stats;      /* 64 bytes; kept_bytes = sum of len + 1 */
+int dskgpu_read_summaries(dskgpu_ctx* ctx, const void* d_bytes, uint64_t nbytes, const dskgpu_read_summary_params* params, dskgpu_read_summary_stats* stats);
+/* The kept table, on the device: d_records = n_records summaries of 32 bytes, 8-byte aligned.  A null d_records: DSKGPU_E_ARG. */
+int dskgpu_read_summaries_table(dskgpu_ctx* ctx, void* d_records);
+/* The RULE applied to the kept table, which stays as it is.  d_keep: u8[n_records] on the device <- 1 (kept) or 0; may be NULL, for the stats
+ * only.  stats may be NULL, but not both: DSKGPU_E_ARG.  rule: NULL keeps everything.  stats: n_records, n_kept, kept_bytes = out_bytes of
+ * the selection by these marks, kept_valid = the sum of n_valid over the kept records. */
+int dskgpu_read_marks(dskgpu_ctx* ctx, const dskgpu_read_rule* rule, void* d_keep, dskgpu_read_mark_stats* stats);
+/* The SELECTION.  Stateless: it needs no result and no kept table, finds the records of the stream itself, works on a context that has never
+ * counted and leaves everything in the context alone.  d_keep: u8[n_records] on the device, non-zero = keep; from dskgpu_read_marks or the
+ * caller's own -- a caller with paired files ANDs the two files' flags and selects both streams, and the pairs stay in step.  n_records must
+ * be the stream's own count: anything else is DSKGPU_E_ARG (nbytes == 0: n_records 0, nothing is written, *out_bytes = *out_records = 0).
+ * d_out == NULL is a sizing run: only *out_bytes / *out_records are written (either may be NULL).  capacity < out_bytes with a non-null
+ * d_out: DSKGPU_E_ARG, nothing is written to d_out and *out_bytes is set to the need.  d_out must not overlap d_bytes.  Any alignment of
+ * either pointer.  A null ctx, a null d_bytes with nbytes > 0, a null d_keep with n_records > 0, a stream longer than dskgpu_query_reads
+ * takes: DSKGPU_E_ARG. */
+int dskgpu_select_reads(dskgpu_ctx* ctx, const void* d_bytes, uint64_t nbytes, const void* d_keep, uint64_t n_records, void* d_out, uint64_t capacity,
+                        uint64_t* out_bytes, uint64_t* out_records);
+
 /* ---- the same call on N GPUs of one node, inside ONE process (what `dsk -nb-gpus N` runs): the reference's
  * single `execute()` (src/DSK.cpp:55-60) still leaves ONE storage with a flat list of solid partitions
  * (utils/dsk2ascii.cpp:61,77).  A group owns one ctx per rank (world_size = n_ranks, rank r on devices[r], its own
