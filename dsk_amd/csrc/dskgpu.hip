@@ -1866,6 +1866,7 @@ void dskgpu_destroy(dskgpu_ctx* ctx) {
     ctx->threading.release();
     ctx->variants.release();
     ctx->readsum.release();
+    ctx->colors.release();
     ctx->filtered.release();
     if (ctx->land) (void)hipHostFree(ctx->land);
     for (DevBuf* b : bufs) b->release();

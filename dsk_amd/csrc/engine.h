@@ -14,7 +14,9 @@
 // correct.hip corrects substitution errors in a read stream against the rows (dskgpu_correct_reads) and keeps nothing;
 // variants.hip reports the bubbles as pairs of sequences (dskgpu_variants*) and owns dskgpu_ctx::variants;
 // readsum.hip summarises the abundances of every read of a stream, marks the reads by a rule and takes reads out of a stream
-// (dskgpu_read_summaries*, dskgpu_read_marks, dskgpu_select_reads) and owns dskgpu_ctx::readsum.  Private to the library.
+// (dskgpu_read_summaries*, dskgpu_read_marks, dskgpu_select_reads) and owns dskgpu_ctx::readsum;
+// colors.hip counts per row how often every sample (colour) of a read stream with bank boundaries holds it and reduces that matrix onto the
+// unitigs (dskgpu_colors_*) and owns dskgpu_ctx::colors.  Private to the library.
 #pragma once
 #include <algorithm>
 #include <cstring>
@@ -218,6 +220,15 @@ struct ReadSummaries {
     void release() { table.release(); stats = dskgpu_read_summary_stats{}; valid = false; }
 };
 
+// The colour matrix of the rows (colors.hip), kept from dskgpu_colors_begin until the rows change: u32 C[n_rows][n_colors], row-major.
+struct Colors {
+    DevBuf C;
+    u32 n_colors = 0;
+    u64 n_rows = 0;                // the rows of the result it was begun for
+    bool valid = false;            // a matrix of the current result is kept (dskgpu_ctx::drop_result and dskgpu_filter_rows drop it)
+    void release() { C.release(); n_colors = 0; n_rows = 0; valid = false; }
+};
+
 // The rows that dskgpu_filter_rows kept (rowfilter.hip): two sets of row arrays, so that a filter of filtered rows reads one set and writes the
 // other; cur = the set res_w / res_ab point into, -1 = the result is still the count's own.  part_off: DSKGPU_F_PARTITION_ORDER, the first
 // kept row of every partition (n_parts + 1 entries) -- rows_partition_range reads them instead of the row sort's while cur >= 0.
@@ -354,10 +365,11 @@ struct dskgpu_ctx {
     Threading threading;
     Variants variants;
     ReadSummaries readsum;
+    Colors colors;
     Filtered filtered;
     // a count starts, or its result is not to be read: the index of the old rows and their unitigs go with them, and so does their memory
     // -- up to 32 + 8 bytes per row that the count about to run may need (a no-op for a context that was never queried)
-    void drop_result() { have_result = false; query.release(); unitigs.release(); threading.release(); variants.release(); readsum.release(); filtered.release(); }
+    void drop_result() { have_result = false; query.release(); unitigs.release(); threading.release(); variants.release(); readsum.release(); colors.release(); filtered.release(); }
     // the read stream changed: what was learnt about the old reads -- their kept encoding apart (enc_keep: the caller's to clear) -- goes
     void reads_changed() { enc_fresh = false; sender.prepared = false; sender.exact = false; opt2_off = false; opt1_off = false; mw_v3_off = false; rec_l0_off = false; last_rows = 0; }
 
@@ -440,6 +452,7 @@ void query_begin(dskgpu_ctx* ctx);                       // stage marks of a cal
 int query_finish(dskgpu_ctx* ctx);                       // ... and the wait for the stream that resolves them
 
 // unitigs.hip
+int ensure_compaction(dskgpu_ctx* ctx, const char* who); // the compaction of the current result: there already, or built now (opens the call's stage marks)
 int ensure_edges(dskgpu_ctx* ctx, const char* who);      // the edges of the current result's compaction: there already, or built now (opens the call's stage marks)
 
 // rowfilter.hip: the machinery of a round that takes rows out, shared by the rules of rules.hip and by components.hip.  The record of a round

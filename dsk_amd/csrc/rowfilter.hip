@@ -86,7 +86,7 @@ int filter_apply(dskgpu_ctx* ctx, const unsigned char* keep, const u64* new_off,
     ctx->n_rows = n_kept;
     F.cur = dst;
     if (ctx->rs.part_mode) F.part_off.assign(new_off, new_off + (n_off - 1)); else F.part_off.clear();
-    ctx->query.invalidate(); ctx->unitigs.invalidate(); ctx->threading.release(); ctx->variants.release(); ctx->readsum.release();
+    ctx->query.invalidate(); ctx->unitigs.invalidate(); ctx->threading.release(); ctx->variants.release(); ctx->readsum.release(); ctx->colors.release();
     return DSKGPU_OK;
 }
 

@@ -233,6 +233,9 @@ int build_edges(dskgpu_ctx* ctx) {
 
 }  // namespace
 
+// the compaction alone, for a caller outside this file that needs no edges (colors.hip)
+int ensure_compaction(dskgpu_ctx* ctx, const char* who) { return ensure_unitigs(ctx, who); }
+
 // the edges of the current result's compaction: there already, or built now (the compaction and the index below them too).  rowfilter.hip calls it.
 int ensure_edges(dskgpu_ctx* ctx, const char* who) {
     if (const int rc = ensure_unitigs(ctx, who)) return rc;

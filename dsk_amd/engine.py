@@ -157,6 +157,16 @@ class _ReadMarkStats(C.Structure):
     ]
 
 
+class _ColorStats(C.Structure):
+    _fields_ = [
+        ("n_valid", C.c_uint64),
+        ("n_placed", C.c_uint64),
+        ("n_rows", C.c_uint64),
+        ("n_colors", C.c_uint64),
+        ("reserved", C.c_uint64 * 4),
+    ]
+
+
 # one summary of dskgpu_read_summaries_table (include/dskgpu.h: SUMMARY), 32 bytes
 READ_SUMMARY_DTYPE = np.dtype([("start", "<u8"), ("sum", "<u8"), ("len", "<u4"), ("n_valid", "<u4"), ("n_solid", "<u4"), ("median", "<u4")])
 READS_INVERT = 1
@@ -338,6 +348,7 @@ EXPORTS = [
     "dskgpu_thread_place", "dskgpu_thread_reads", "dskgpu_thread_walks", "dskgpu_thread_support",
     "dskgpu_correct_reads",
     "dskgpu_read_summaries", "dskgpu_read_summaries_table", "dskgpu_read_marks", "dskgpu_select_reads",
+    "dskgpu_colors_begin", "dskgpu_colors_add", "dskgpu_colors_rows", "dskgpu_colors_unitigs",
     "dskgpu_variants", "dskgpu_variants_table", "dskgpu_variants_stream",
     "dskgpu_k_encode", "dskgpu_k_enumerate", "dskgpu_k_minimizers",
     "dskgpu_group_create", "dskgpu_group_destroy", "dskgpu_group_last_error", "dskgpu_group_size", "dskgpu_group_ctx",
@@ -494,6 +505,14 @@ def load_library():
     lib.dskgpu_read_marks.restype = C.c_int
     lib.dskgpu_select_reads.argtypes = [vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     lib.dskgpu_select_reads.restype = C.c_int
+    lib.dskgpu_colors_begin.argtypes = [vp, u32]
+    lib.dskgpu_colors_begin.restype = C.c_int
+    lib.dskgpu_colors_add.argtypes = [vp, vp, u64, C.POINTER(u64), u32, u32, C.POINTER(_ColorStats)]
+    lib.dskgpu_colors_add.restype = C.c_int
+    lib.dskgpu_colors_rows.argtypes = [vp, u32, vp, vp]
+    lib.dskgpu_colors_rows.restype = C.c_int
+    lib.dskgpu_colors_unitigs.argtypes = [vp, u32, vp, vp, vp]
+    lib.dskgpu_colors_unitigs.restype = C.c_int
     lib.dskgpu_k_encode.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_enumerate.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_minimizers.argtypes = [vp, vp, u64, vp, vp]
@@ -1156,6 +1175,76 @@ class KmerCounter:
             torch.cuda.current_stream(stream.device).synchronize()
             self.select_reads(*args, out.data_ptr(), need)
         return out
+
+    # -- sample colours for rows, unitigs and variants (include/dskgpu.h: dskgpu_colors_begin / _colors_add / _colors_rows / _colors_unitigs)
+    def colors_begin(self, n_colors: int) -> None:
+        """A zeroed colour matrix u32[n_rows, n_colors] (n_colors 1..64) for the last result, kept in the context until the rows change;
+        it replaces the one kept before."""
+        self._ck(self._lib.dskgpu_colors_begin(self._h, n_colors))
+        self._n_colors = n_colors
+
+    def colors_add(self, d_bytes: int, nbytes: int, ends, first_color: int = 0) -> dict:
+        """d_bytes: a read stream on the device; ends: the end offset of every bank of it (non-decreasing, the last <= nbytes).  Every valid
+        window whose canonical k-mer is a row adds 1 to that row's cell of colour first_color + (the bank of the byte the window ends at).
+        -> the stats of this call: n_valid (valid windows that have a bank), n_placed (those that are rows), n_rows, n_colors."""
+        e = np.ascontiguousarray(ends, dtype=np.uint64).reshape(-1)
+        st = _ColorStats()
+        self._ck(self._lib.dskgpu_colors_add(self._h, C.c_void_p(d_bytes) if d_bytes else None, nbytes, e.ctypes.data_as(C.POINTER(C.c_uint64)) if len(e) else None,
+                                             len(e), first_color, C.byref(st)))
+        return _stats_dict(st)
+
+    def colors_add_tensor(self, stream, ends, first_color: int = 0) -> dict:
+        """stream: CUDA uint8 tensor holding a read stream; as colors_add."""
+        import torch
+        if not stream.is_cuda or stream.dtype != torch.uint8:
+            raise ValueError("colors_add_tensor: a CUDA uint8 tensor is needed")
+        stream = stream.contiguous()
+        n = stream.numel()
+        torch.cuda.current_stream(stream.device).synchronize()    # the context's stream is not torch's: what torch enqueued is done before the kernels read it
+        return self.colors_add(stream.data_ptr() if n else 0, n, ends, first_color)
+
+    def colors_rows(self, min_count: int, d_counts: int, d_mask: int) -> None:
+        """d_counts: n_rows * n_colors u32 on the device (result order, row-major) <- the matrix; d_mask: n_rows u64 <- bit c: the cell of
+        colour c is >= min_count; either may be 0."""
+        self._ck(self._lib.dskgpu_colors_rows(self._h, min_count, C.c_void_p(d_counts) if d_counts else None, C.c_void_p(d_mask) if d_mask else None))
+
+    def _colors_shape(self):
+        self.colors_add(0, 0, [])                                 # an empty stream does nothing: DSKGPU_E_STATE when no matrix is kept
+        return self.result_device()[2], self._n_colors
+
+    def colors_rows_tensor(self, min_count: int = 1):
+        """-> (int32[n_rows, n_colors] the matrix, to be viewed as u32; int64[n_rows] the masks, the bit pattern of a u64), CUDA tensors."""
+        import torch
+        n, nc = self._colors_shape()
+        dev = torch.device("cuda", self.device)
+        counts, mask = torch.zeros((n, nc), dtype=torch.int32, device=dev), torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()              # the context's stream is not torch's: the zero fill is done before the copy writes
+        self.colors_rows(min_count, counts.data_ptr() if n else 0, mask.data_ptr())
+        return counts, mask[:n]
+
+    def colors_unitigs(self, min_count: int, d_sum: int, d_all: int, d_any: int) -> None:
+        """d_sum: n_unitigs * n_colors u64 on the device <- the sum of every colour over the rows of every unitig; d_all / d_any: n_unitigs
+        u64 <- the AND / the OR of the masks (min_count) of its rows; any may be 0.  Builds the compaction when it is not there."""
+        self._ck(self._lib.dskgpu_colors_unitigs(self._h, min_count, *(C.c_void_p(p) if p else None for p in (d_sum, d_all, d_any))))
+
+    def colors_unitigs_tensor(self, min_count: int = 1):
+        """-> (int64[n_unitigs, n_colors] sums, int64[n_unitigs] all, int64[n_unitigs] any: the bit patterns of u64), CUDA tensors."""
+        import torch
+        _, nc = self._colors_shape()
+        nu = self.unitigs()["n_unitigs"]
+        dev = torch.device("cuda", self.device)
+        total = torch.zeros((nu, nc), dtype=torch.int64, device=dev)
+        all_, any_ = torch.zeros(max(nu, 1), dtype=torch.int64, device=dev), torch.zeros(max(nu, 1), dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        self.colors_unitigs(min_count, total.data_ptr() if nu else 0, all_.data_ptr(), any_.data_ptr())
+        return total, all_[:nu], any_[:nu]
+
+    def variants_colors_tensor(self, min_count: int = 1):
+        """-> int64[n_variants, 2, n_colors]: for every kept variant (variants() first) the colour sums of the unitig of allele A and of
+        allele B -- per-sample allele coverage.  A gather from colors_unitigs_tensor over the variant table."""
+        total, _, _ = self.colors_unitigs_tensor(min_count)
+        rec = self.variants_tensor()
+        return total[rec[:, :2] >> 1]
 
     # -- rows out of a result, and the tips of the compacted graph (include/dskgpu.h: dskgpu_filter_rows / _graph_tips / _clip_tips)
     def filter_rows(self, d_keep: int) -> int:

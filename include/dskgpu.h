@@ -858,6 +858,59 @@ int dskgpu_read_marks(dskgpu_ctx* ctx, const dskgpu_read_rule* rule, void* d_kee
 int dskgpu_select_reads(dskgpu_ctx* ctx, const void* d_bytes, uint64_t nbytes, const void* d_keep, uint64_t n_records, void* d_out, uint64_t capacity,
                         uint64_t* out_bytes, uint64_t* out_records);
 
+/* ---- sample colours for rows, unitigs and variants: everything above answers questions about ONE pooled set of reads.  The consumers
+ * these calls were modelled on are mostly multi-sample tools: DiscoSnp genotypes every bubble per sample, Cortex, Bifrost and kmtricks keep
+ * a colour per k-mer, a GFA viewer draws per-sample coverage on the unitigs, a differential analysis asks which unitigs are private to one
+ * sample.  These calls turn a read stream with bank boundaries into a row x colour count matrix and reduce it onto the unitigs.  Alphabet,
+ * window validity and positions are exactly those of dskgpu_k_enumerate / dskgpu_query_reads; "row" is as dskgpu_query_kmers means it.
+ *   COLOURS         A context holds at most one colour matrix.  It has n_colors columns, 1..64.  The matrix is u32 C[n_rows][n_colors],
+ *                   row-major, in result order, zeroed by dskgpu_colors_begin.
+ *   BANK            of a position.  In one dskgpu_colors_add call with end_offsets[0..n_banks), position p lies in bank b when b is the
+ *                   least index with p < end_offsets[b].  end_offsets is a host array, non-decreasing, with
+ *                   end_offsets[n_banks-1] <= nbytes.  Positions at or beyond the last end have no bank and are not counted.  The colour
+ *                   of p is first_color + b.  An empty bank (two equal ends) is legal.  The bank belongs to the byte the window ENDS at:
+ *                   in a stream whose banks each end with '\n', no window crosses a boundary.
+ *   CELL            C[r][c] is the number of positions p -- of any dskgpu_colors_add call since dskgpu_colors_begin -- that have colour
+ *                   c, whose window (the one ending at p) is valid and whose canonical k-mer is row r.  A window over a palindromic row
+ *                   (even k) counts once.  Arithmetic is modulo 2^32: fewer than 2^32 bytes per colour cannot wrap.  Integer adds
+ *                   commute, so the matrix does not depend on scheduling.
+ *   MASK            mask(min_count)[r] is a u64 whose bit c is set iff C[r][c] >= min_count.  min_count >= 1; 0 is DSKGPU_E_ARG.
+ *   UNITIG COLOURS  sum[u][c] is the sum of C[r][c] over the rows with unitig[r] == u (u64, exact); all[u] is the AND of those rows' masks,
+ *                   any[u] the OR.  sum[u][c] / L[u] is the sample's mean coverage of the unitig; `all` marks the unitigs that a sample
+ *                   covers end to end.
+ *   VARIANT COLOURS For variant v with alleles A, B (oriented unitigs of dskgpu_variants_table): vsum[v][0][c] = sum[A >> 1][c] and
+ *                   vsum[v][1][c] = sum[B >> 1][c] -- DiscoSnp's per-sample allele coverage.  A gather from the unitig table: no call of
+ *                   its own (KmerCounter.variants_colors_tensor does it).
+ * The calls run on the context's stream and are synchronous on return.  They change nothing else in the context: the reads, a kept
+ * encoding, the result, the stats, the sender state and a kept threading stay as they are.  dskgpu_colors_add builds the lookup index on
+ * first use and encodes the stream into scratch of its own (0.375 bytes per stream byte), freed before it returns; the matrix takes
+ * 4 * n_rows * n_colors bytes.  d_bytes: the stream on the device, any alignment, any length (a long stream takes several launches).
+ * Lifetime: the matrix lives in the context next to the read summaries.  It is dropped, and its memory freed, by the next count, by
+ * dskgpu_filter_rows and everything built on it (dskgpu_clip_tips / _pop_bubbles / _remove_connections / _simplify / _simplify_all /
+ * _drop_components) and by dskgpu_destroy; a second dskgpu_colors_begin replaces it.  The intended order is count, clean the graph, then
+ * colour.  After the rows change, add / rows / unitigs without a new begin are DSKGPU_E_STATE.
+ * Which results are served: every k (1..128), either row order, DSKGPU_F_NO_SORT, several passes, the per-bank modes and a rank's rows
+ * (world_size > 1) for begin / add / rows, which only need the lookup index.  dskgpu_colors_unitigs needs the compaction: it builds it on
+ * first use as the other graph calls do, and is DSKGPU_E_STATE on a rank of a group.
+ * Stage times: "colors" (dskgpu_colors_add), "color unitigs" (dskgpu_colors_unitigs), plus "query index" / "unitigs" when the call builds them.
+ * Errors: DSKGPU_E_ARG: a null ctx; n_colors 0 or > 64; first_color + n_banks > n_colors; n_banks == 0 with nbytes > 0; decreasing ends, or
+ * an end above nbytes; a null d_bytes or end_offsets with nbytes > 0; d_counts and d_mask both null, or all three outputs of _unitigs null;
+ * min_count == 0.  DSKGPU_E_STATE: no result, or no begin (a call out of order is reported before first_color + n_banks is compared with
+ * n_colors).  nbytes == 0: DSKGPU_OK, nothing is done, all-zero stats.  DSKGPU_E_NOMEM leaves the context and everything built
+ * usable; after a failed dskgpu_colors_begin no matrix is kept.  A result with zero rows: begin and add succeed, n_placed is 0, and nothing
+ * is written by the copy calls. */
+typedef struct dskgpu_color_stats { uint64_t n_valid, n_placed, n_rows, n_colors, reserved[4]; } dskgpu_color_stats;   /* 64 bytes */
+int dskgpu_colors_begin(dskgpu_ctx* ctx, uint32_t n_colors);
+/* stats (may be NULL): the counts of this one call.  n_valid = the valid windows that have a bank; n_placed = those of them that are rows,
+ * which is the amount this call added to the matrix; n_rows, n_colors = the shape of the matrix. */
+int dskgpu_colors_add(dskgpu_ctx* ctx, const void* d_bytes, uint64_t nbytes, const uint64_t* end_offsets, uint32_t n_banks, uint32_t first_color,
+                      dskgpu_color_stats* stats);
+/* d_counts: u32[n_rows * n_colors] on the device <- the matrix; d_mask: u64[n_rows] <- mask(min_count); either may be NULL, not both.
+ * d_counts 4-byte aligned (16-byte aligned with n_colors a multiple of 4: copied with 16-byte accesses), d_mask 8-byte aligned. */
+int dskgpu_colors_rows(dskgpu_ctx* ctx, uint32_t min_count, void* d_counts, void* d_mask);
+/* d_sum: u64[n_unitigs * n_colors], d_all / d_any: u64[n_unitigs], on the device, 8-byte aligned; any may be NULL, not all three. */
+int dskgpu_colors_unitigs(dskgpu_ctx* ctx, uint32_t min_count, void* d_sum, void* d_all, void* d_any);
+
 /* ---- the same call on N GPUs of one node, inside ONE process (what `dsk -nb-gpus N` runs): the reference's
  * single `execute()` (src/DSK.cpp:55-60) still leaves ONE storage with a flat list of solid partitions
  * (utils/dsk2ascii.cpp:61,77).  A group owns one ctx per rank (world_size = n_ranks, rank r on devices[r], its own
