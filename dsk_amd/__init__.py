@@ -14,4 +14,5 @@ from .engine import (  # noqa: F401
     load_library,
     make_table,
     library_path,
+    sample_distances,
 )

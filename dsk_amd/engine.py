@@ -167,6 +167,37 @@ class _ColorStats(C.Structure):
     ]
 
 
+class _ColorPairStats(C.Structure):
+    _fields_ = [
+        ("n_rows", C.c_uint64),
+        ("n_selected", C.c_uint64),
+        ("n_present", C.c_uint64),
+        ("n_colors", C.c_uint64),
+        ("reserved", C.c_uint64 * 4),
+    ]
+
+
+class _ColorRule(C.Structure):
+    _fields_ = [
+        ("need_all", C.c_uint64),
+        ("need_none", C.c_uint64),
+        ("min_count", C.c_uint32),
+        ("min_present", C.c_uint32),
+        ("max_present", C.c_uint32),
+        ("flags", C.c_uint32),
+    ]
+
+
+class _ColorMarkStats(C.Structure):
+    _fields_ = [
+        ("n_rows", C.c_uint64),
+        ("n_kept", C.c_uint64),
+        ("reserved", C.c_uint64 * 6),
+    ]
+
+
+COLORS_INVERT = 1
+
 # one summary of dskgpu_read_summaries_table (include/dskgpu.h: SUMMARY), 32 bytes
 READ_SUMMARY_DTYPE = np.dtype([("start", "<u8"), ("sum", "<u8"), ("len", "<u4"), ("n_valid", "<u4"), ("n_solid", "<u4"), ("median", "<u4")])
 READS_INVERT = 1
@@ -349,6 +380,7 @@ EXPORTS = [
     "dskgpu_correct_reads",
     "dskgpu_read_summaries", "dskgpu_read_summaries_table", "dskgpu_read_marks", "dskgpu_select_reads",
     "dskgpu_colors_begin", "dskgpu_colors_add", "dskgpu_colors_rows", "dskgpu_colors_unitigs",
+    "dskgpu_colors_pairs", "dskgpu_colors_load", "dskgpu_colors_marks",
     "dskgpu_variants", "dskgpu_variants_table", "dskgpu_variants_stream",
     "dskgpu_k_encode", "dskgpu_k_enumerate", "dskgpu_k_minimizers",
     "dskgpu_group_create", "dskgpu_group_destroy", "dskgpu_group_last_error", "dskgpu_group_size", "dskgpu_group_ctx",
@@ -513,6 +545,12 @@ def load_library():
     lib.dskgpu_colors_rows.restype = C.c_int
     lib.dskgpu_colors_unitigs.argtypes = [vp, u32, vp, vp, vp]
     lib.dskgpu_colors_unitigs.restype = C.c_int
+    lib.dskgpu_colors_pairs.argtypes = [vp, u32, vp, vp, vp, vp, C.POINTER(_ColorPairStats)]
+    lib.dskgpu_colors_pairs.restype = C.c_int
+    lib.dskgpu_colors_load.argtypes = [vp, vp, u32]
+    lib.dskgpu_colors_load.restype = C.c_int
+    lib.dskgpu_colors_marks.argtypes = [vp, C.POINTER(_ColorRule), vp, C.POINTER(_ColorMarkStats)]
+    lib.dskgpu_colors_marks.restype = C.c_int
     lib.dskgpu_k_encode.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_enumerate.argtypes = [vp, vp, u64, vp, vp]
     lib.dskgpu_k_minimizers.argtypes = [vp, vp, u64, vp, vp]
@@ -1246,6 +1284,68 @@ class KmerCounter:
         rec = self.variants_tensor()
         return total[rec[:, :2] >> 1]
 
+    # -- the samples compared with each other, rows chosen by colour, a matrix put back (include/dskgpu.h: dskgpu_colors_pairs / _colors_load / _colors_marks)
+    def colors_load(self, ptr: int, n_colors: int) -> None:
+        """ptr: n_rows * n_colors u32 on the device (result order, row-major), 4-byte aligned -> a copy of it is the kept colour matrix of the
+        last result, as if colors_begin and colors_add had built it; it replaces the one kept before."""
+        self._ck(self._lib.dskgpu_colors_load(self._h, C.c_void_p(ptr) if ptr else None, n_colors))
+        self._n_colors = n_colors
+
+    def colors_load_tensor(self, t) -> None:
+        """t: CUDA int32 tensor [n_rows, n_colors] (the bit patterns of u32, what colors_rows_tensor returns); as colors_load."""
+        import torch
+        if not t.is_cuda or t.dtype != torch.int32 or t.dim() != 2:
+            raise ValueError("colors_load_tensor: a CUDA int32 tensor [n_rows, n_colors] is needed")
+        n = self.result_device()[2]
+        if t.shape[0] != n:
+            raise ValueError("colors_load_tensor: %d rows for a result of %d" % (t.shape[0], n))
+        t = t.contiguous()
+        torch.cuda.current_stream(t.device).synchronize()         # the context's stream is not torch's: the matrix is written before the copy reads it
+        self.colors_load(t.data_ptr() if n else 0, int(t.shape[1]))
+
+    def colors_pairs(self, min_count: int, shared_ptr: int, cross_ptr: int, min_sum_ptr: int, select_ptr: int = 0) -> dict:
+        """shared_ptr / cross_ptr / min_sum_ptr: n_colors * n_colors u64 on the device each, any may be 0 <- the pair matrices of the kept
+        matrix over the rows whose byte at select_ptr is non-zero (0: every row), cells below min_count taken as 0.  -> the stats: n_rows,
+        n_selected, n_present (selected rows with a cell left), n_colors."""
+        st = _ColorPairStats()
+        self._ck(self._lib.dskgpu_colors_pairs(self._h, min_count, *(C.c_void_p(p) if p else None for p in (select_ptr, shared_ptr, cross_ptr, min_sum_ptr)), C.byref(st)))
+        return _stats_dict(st)
+
+    def colors_pairs_tensor(self, min_count: int = 1, select=None):
+        """select: None, or a CUDA bool / uint8 tensor of n_rows flags.  -> (shared, cross, min_sum: int64[n_colors, n_colors] CUDA tensors,
+        the stats)."""
+        import torch
+        n, nc = self._colors_shape()
+        dev = torch.device("cuda", self.device)
+        if select is not None:
+            if not select.is_cuda or select.dtype not in (torch.bool, torch.uint8) or select.numel() != n:
+                raise ValueError("colors_pairs_tensor: select must be a CUDA bool or uint8 tensor of %d flags" % n)
+            select = select.contiguous().view(torch.uint8)
+        out = torch.zeros((3, nc, nc), dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()              # the context's stream is not torch's: the zero fill is done before the kernel adds
+        st = self.colors_pairs(min_count, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), select.data_ptr() if select is not None and n else 0)
+        return out[0], out[1], out[2], st
+
+    def colors_marks(self, keep_ptr: int, need_all: int = 0, need_none: int = 0, min_count: int = 1, min_present: int = 0, max_present: int = 0,
+                     invert: bool = False) -> dict:
+        """keep_ptr: n_rows bytes on the device <- 1 or 0, the form filter_rows takes: with m the mask of the row's colours that hold at least
+        min_count, a row is kept when m has every bit of need_all, none of need_none, at least min_present bits and at most max_present
+        (0: no upper bound); invert flips the answer.  -> the stats: n_rows, n_kept."""
+        rule, st = _ColorRule(need_all=need_all, need_none=need_none, min_count=min_count, min_present=min_present, max_present=max_present,
+                              flags=COLORS_INVERT if invert else 0), _ColorMarkStats()
+        self._ck(self._lib.dskgpu_colors_marks(self._h, C.byref(rule), C.c_void_p(keep_ptr) if keep_ptr else None, C.byref(st)))
+        return _stats_dict(st)
+
+    def colors_marks_tensor(self, **rule):
+        """-> (uint8[n_rows] CUDA tensor of the marks, the stats); the rule as colors_marks."""
+        import torch
+        n, _ = self._colors_shape()
+        dev = torch.device("cuda", self.device)
+        keep = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        st = self.colors_marks(keep.data_ptr(), **rule)
+        return keep[:n], st
+
     # -- rows out of a result, and the tips of the compacted graph (include/dskgpu.h: dskgpu_filter_rows / _graph_tips / _clip_tips)
     def filter_rows(self, d_keep: int) -> int:
         """d_keep: n_rows bytes on the device (result order), non-zero = keep the row.  The result, its partitions and every lookup and
@@ -1625,6 +1725,46 @@ class KmerGroup:
         ab = np.zeros(n, dtype=np.uint32)
         self._ck(self._lib.dskgpu_group_partition_copy(self._h, p, C.c_void_p(kmers.ctypes.data), C.c_void_p(ab.ctypes.data)))
         return kmers, ab
+
+
+def sample_distances(shared, cross, min_sum) -> dict:
+    """The pair matrices of colors_pairs (numpy arrays or tensors, [n_colors, n_colors]) -> {name: float64[n_colors, n_colors]}, the
+    distances between the samples.  With N = diag(shared), T = diag(cross), a = shared, s = min_sum, U[i][j] = cross[i][j] / T[i] and
+    V[i][j] = cross[j][i] / T[j]:
+      jaccard 1 - a / (Ni + Nj - a); sorensen 1 - 2a / (Ni + Nj); ochiai 1 - a / sqrt(Ni Nj); kulczynski 1 - (a / Ni + a / Nj) / 2;
+      bray_curtis 1 - 2s / (Ti + Tj); ruzicka 1 - s / (Ti + Tj - s);
+      ab_jaccard 1 - UV / (U + V - UV); ab_ochiai 1 - sqrt(UV); ab_sorensen 1 - 2UV / (U + V).
+    An entry whose denominator is zero (an empty sample) is NaN."""
+    def f64(m):
+        m = m.cpu().numpy() if hasattr(m, "cpu") else np.asarray(m)
+        if m.dtype == np.int64:
+            m = m.view(np.uint64)                                 # (a tensor holds the bit pattern of a u64)
+        return m.astype(np.float64)
+
+    a, x, s = f64(shared), f64(cross), f64(min_sum)
+    if a.ndim != 2 or a.shape[0] != a.shape[1] or x.shape != a.shape or s.shape != a.shape:
+        raise ValueError("sample_distances: three square matrices of one shape are needed")
+    N, T = np.diag(a), np.diag(x)
+    Ni, Nj, Ti, Tj = N[:, None], N[None, :], T[:, None], T[None, :]
+
+    def over(num, den):
+        out = np.full(a.shape, np.nan)
+        np.divide(num, den, out=out, where=den != 0)
+        return out
+
+    U, V = over(x, Ti), over(x.T, Tj)
+    UV = U * V
+    return {
+        "jaccard": 1.0 - over(a, Ni + Nj - a),
+        "sorensen": 1.0 - over(2.0 * a, Ni + Nj),
+        "ochiai": 1.0 - over(a, np.sqrt(Ni * Nj)),
+        "kulczynski": 1.0 - (over(a, Ni) + over(a, Nj)) / 2.0,
+        "bray_curtis": 1.0 - over(2.0 * s, Ti + Tj),
+        "ruzicka": 1.0 - over(s, Ti + Tj - s),
+        "ab_jaccard": 1.0 - over(UV, U + V - UV),
+        "ab_ochiai": 1.0 - np.sqrt(UV),
+        "ab_sorensen": 1.0 - over(2.0 * UV, U + V),
+    }
 
 
 def kmer_to_string(value: int, k: int) -> str:

@@ -911,6 +911,52 @@ int dskgpu_colors_rows(dskgpu_ctx* ctx, uint32_t min_count, void* d_counts, void
 /* d_sum: u64[n_unitigs * n_colors], d_all / d_any: u64[n_unitigs], on the device, 8-byte aligned; any may be NULL, not all three. */
 int dskgpu_colors_unitigs(dskgpu_ctx* ctx, uint32_t min_count, void* d_sum, void* d_all, void* d_any);
 
+/* ---- comparing the samples, choosing rows by colour, keeping colours across a row change: the calls above look at one row or one unitig of
+ * the colour matrix at a time.  These look at the matrix as a whole.  dskgpu_colors_pairs reduces it to three n_colors x n_colors matrices,
+ * from which Jaccard, Sorensen, Ochiai, Kulczynski, Bray-Curtis and the abundance-weighted distances between samples follow (what Simka
+ * computes; what kmtricks and Mash-style workflows derive from a k-mer matrix; KmerCounter's sample_distances does the arithmetic) -- one pass
+ * over a matrix that already lies in device memory instead of a copy of 4 * n_rows * n_colors bytes.  dskgpu_colors_marks turns a rule on a
+ * row's colours into the byte per row that dskgpu_filter_rows takes (the k-mers private to some samples, present in at least m, the core, the
+ * accessory part), as dskgpu_read_marks does for reads.  dskgpu_colors_load makes a matrix of the caller's the kept one: a caller that saved
+ * the matrix with dskgpu_colors_rows before a row change puts it back, gathered to the kept rows, instead of streaming every read again.
+ *   THRESHOLDED CELL  C'[r][c] = C[r][c] if C[r][c] >= min_count, else 0.  min_count >= 1; 0 is DSKGPU_E_ARG.  mask(min_count)[r] has bit c
+ *                     set iff C'[r][c] > 0.
+ *   SELECTED          Row r is selected when d_select is NULL or d_select[r] != 0.  d_select: u8[n_rows] on the device, any alignment (the
+ *                     form of dskgpu_colors_marks' and dskgpu_filter_rows' bytes).
+ *   PAIR MATRICES     u64[n_colors][n_colors] each, row-major, on the device, 8-byte aligned; the sums run over the selected rows.
+ *                       shared[i][j]  = the number of rows with C'[r][i] > 0 and C'[r][j] > 0.  Symmetric; shared[i][i] is sample i's
+ *                                       distinct k-mers.
+ *                       cross[i][j]   = the sum of C'[r][i] over the rows with C'[r][j] > 0.  Not symmetric; cross[i][i] is sample i's
+ *                                       total, and cross[i][j] / cross[i][i] is Simka's U.
+ *                       min_sum[i][j] = the sum of min(C'[r][i], C'[r][j]).  Symmetric; min_sum[i][i] == cross[i][i].
+ *                     Any of the three may be NULL, but not all three.  Every entry is exact in 64 bits and does not depend on scheduling:
+ *                     a cell may be 2^32 - 1, and no partial sum is held in anything that can wrap (integer adds only).
+ *   RULE              With m = mask(rule.min_count)[r], keep0 is true exactly when (m & need_all) == need_all, (m & need_none) == 0,
+ *                     popcount(m) >= min_present, and max_present == 0 or popcount(m) <= max_present.  d_keep[r] (u8) = keep0 XOR flag
+ *                     bit 0 (DSKGPU_COLORS_INVERT): 1 or 0, the form dskgpu_filter_rows takes.
+ * State: the three calls need only the kept matrix, keep nothing in the context and change nothing in it (dskgpu_colors_load changes the
+ * matrix itself).  So they serve every k, either row order, DSKGPU_F_NO_SORT, several passes and a rank's rows (world_size > 1).  The ranks
+ * of a group partition the k-mers, so the job-wide pair matrices are the element-wise sums of the ranks' matrices.  The calls run on the
+ * context's stream and are synchronous on return.  dskgpu_colors_load does what dskgpu_colors_begin does -- same lifetime, same errors, it
+ * replaces a kept matrix -- but the new matrix is a copy of d_counts: u32[n_rows][n_colors] of the current result, row-major, on the device,
+ * 4-byte aligned.
+ * Stage times: "color pairs", "color marks", "color load".
+ * Errors: DSKGPU_E_ARG: a null ctx; min_count == 0; all three outputs null; n_colors 0 or > 64; a null d_counts while there are rows; a null
+ * rule; unknown flag bits; bits of need_all or need_none at or above n_colors; a null d_keep while there are rows.  DSKGPU_E_STATE: no kept
+ * matrix (pairs, marks); no result (load).  A result with zero rows: DSKGPU_OK; the pair matrices are zeroed, the stats are all zero, nothing
+ * is written to d_keep, and dskgpu_colors_load takes a null d_counts. */
+typedef struct dskgpu_color_pair_stats { uint64_t n_rows, n_selected, n_present, n_colors, reserved[4]; } dskgpu_color_pair_stats;   /* 64 bytes */
+/* stats (may be NULL): n_rows, n_colors = the shape of the matrix; n_selected = the selected rows; n_present = the selected rows with some
+ * C'[r][c] > 0. */
+int dskgpu_colors_pairs(dskgpu_ctx* ctx, uint32_t min_count, const void* d_select, void* d_shared, void* d_cross, void* d_min_sum,
+                        dskgpu_color_pair_stats* stats);
+int dskgpu_colors_load(dskgpu_ctx* ctx, const void* d_counts, uint32_t n_colors);
+#define DSKGPU_COLORS_INVERT 1u                          /* dskgpu_color_rule.flags bit 0: keep what the rule would drop */
+typedef struct dskgpu_color_rule { uint64_t need_all, need_none; uint32_t min_count, min_present, max_present, flags; } dskgpu_color_rule;   /* 32 bytes */
+typedef struct dskgpu_color_mark_stats { uint64_t n_rows, n_kept, reserved[6]; } dskgpu_color_mark_stats;                                    /* 64 bytes */
+/* stats (may be NULL): n_rows; n_kept = the rows whose byte is 1. */
+int dskgpu_colors_marks(dskgpu_ctx* ctx, const dskgpu_color_rule* rule, void* d_keep, dskgpu_color_mark_stats* stats);
+
 /* ---- the same call on N GPUs of one node, inside ONE process (what `dsk -nb-gpus N` runs): the reference's
  * single `execute()` (src/DSK.cpp:55-60) still leaves ONE storage with a flat list of solid partitions
  * (utils/dsk2ascii.cpp:61,77).  A group owns one ctx per rank (world_size = n_ranks, rank r on devices[r], its own
