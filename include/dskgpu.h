@@ -992,7 +992,15 @@ uint64_t dskgpu_group_partition_size(const dskgpu_group* g, uint32_t P);
 int dskgpu_group_partition_copy(const dskgpu_group* g, uint32_t P, uint64_t* kmers, uint32_t* abundance);
 
 /* ---- kernel-level entry points used by the parity tests (device pointers) */
-/* ASCII -> 2-bit packed words + invalid mask, one u64 / u32 per 32 bases. */
+/* ASCII -> 2-bit packed words + invalid mask: (nbytes + 31) / 32 words are written to each of d_packed (u64) and d_invalid (u32),
+ * and nothing behind them.  Word w holds bytes 32 w .. 32 w + 31; byte 32 w + j is "base j" of the word.
+ *   d_packed[w]   the code of base j in bits 63 - 2 j .. 62 - 2 j (base 0 in the two highest bits): A = 0, C = 1, T = 2, G = 3,
+ *                 either case
+ *   d_invalid[w]  bit 31 - j set iff byte 32 w + j is none of the eight letters ACGTacgt -- every other value of the 256, the
+ *                 control characters and the values from 0x80 on included -- or lies at or beyond nbytes: the pad of the last
+ *                 word reads as invalid
+ * The two code bits under an invalid position are unspecified: read d_packed under the mask of the valid positions only.
+ * d_bytes needs no alignment (a 16-byte aligned stream takes wider loads; the result is the same). */
 int dskgpu_k_encode(dskgpu_ctx* ctx, const void* d_bytes, uint64_t nbytes, void* d_packed, void* d_invalid);
 /* Canonical k-mer (words = ceil(k/32) u64, LSW first) + validity byte for the window ending at every byte. */
 int dskgpu_k_enumerate(dskgpu_ctx* ctx, const void* d_bytes, uint64_t nbytes, void* d_kmers, void* d_valid);

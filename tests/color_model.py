@@ -5,6 +5,7 @@ of tests/dense_streams.py (canon), cells are counted in a Counter, masks are Pyt
 result order), unitig[r] of every row and the stream with its bank ends."""
 from collections import Counter
 
+from tests.byte_streams import upper_bases
 from tests.dense_streams import canon
 
 _BASES = frozenset(b"ACGTacgt")
@@ -23,7 +24,7 @@ def rows_of(values, k):
 def windows(stream, k):
     """-> [(p, canonical k-mer)] of the valid windows of the stream, p = the byte the window ends at"""
     raw = bytes(stream)
-    text = raw.decode("latin-1").upper()
+    text = upper_bases(raw)
     out, run = [], 0
     for p in range(len(raw)):
         run = run + 1 if raw[p] in _BASES else 0

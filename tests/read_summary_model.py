@@ -5,6 +5,7 @@ STRINGS in the lexicographic canonical form of the correction's restatement (tes
 table is a dict canonical string -> abundance of which only lookups are asked."""
 import numpy as np
 
+from tests.byte_streams import upper_bases
 from tests.test_correct_restatement import _BASES, canon
 
 FIELDS = ("start", "sum", "len", "n_valid", "n_solid", "median")
@@ -40,7 +41,7 @@ def records(raw):
 def values(raw, table, k):
     """-> (valid bool[n], a int64[n]): the window ending at every byte"""
     n = len(raw)
-    text = raw.decode("latin-1").upper()
+    text = upper_bases(raw)
     valid, a = np.zeros(n, dtype=bool), np.zeros(n, dtype=np.int64)
     run = 0
     for p in range(n):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 pytest.importorskip("torch")          # (the GPU modules import it at the top)
+from tests.byte_streams import upper_bases      # noqa: E402
 from tests.test_gpu_unitigs import GOLDEN, revcomp_str      # noqa: E402
 from tests.test_unitigs_restatement import solid_rows      # noqa: E402
 
@@ -44,7 +45,7 @@ class CorrectRestatement:
 
     def states(self, raw):
         k, n = self.k, len(raw)
-        text = raw.decode("latin-1").upper()
+        text = upper_bases(raw)
         state = np.zeros(n, dtype=np.uint8)
         run = 0
         for p in range(n):

@@ -11,6 +11,7 @@ import pytest
 
 pytest.importorskip("torch")          # (the modules the helpers come from import it at the top)
 from tests import read_summary_model as M      # noqa: E402
+from tests.byte_streams import upper_bases      # noqa: E402
 from tests.test_correct_restatement import _BASES, canon      # noqa: E402
 from tests.test_gpu_unitigs import GOLDEN      # noqa: E402
 from tests.test_unitigs_restatement import solid_rows      # noqa: E402
@@ -96,7 +97,7 @@ def golden_part(oracle, golden_dir, n_records=600):
 
 def kmer_counts(raw, k):
     """Counter of the canonical strings of the valid windows"""
-    c, run, text = Counter(), 0, raw.decode("latin-1").upper()
+    c, run, text = Counter(), 0, upper_bases(raw)
     for p in range(len(raw)):
         run = run + 1 if raw[p] in _BASES else 0
         if run >= k:

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 pytest.importorskip("torch")          # (the GPU modules import it at the top)
+from tests.byte_streams import upper_bases      # noqa: E402
 from tests.test_gpu_unitigs import GOLDEN, circles_stream, handmade_stream, revcomp_str      # noqa: E402
 from tests.test_unitig_edges_restatement import EdgeRestatement      # noqa: E402
 from tests.test_unitigs_restatement import solid_rows      # noqa: E402
@@ -38,7 +39,7 @@ class ThreadRestatement(EdgeRestatement):
     def thread(self, stream):
         k = self.k
         raw = bytes(stream)
-        text = raw.decode("latin-1").upper()
+        text = upper_bases(raw)
         n = len(raw)
         T = Threaded()
         T.U = np.full(n, -1, dtype=np.int64)
