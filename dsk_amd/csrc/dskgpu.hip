@@ -649,6 +649,7 @@ int pass_plan(dskgpu_ctx* ctx, PassState<W>& ps, int extra_bits) {
     if (!make_plan(plan_n, extra_bits, W, (u32)ctx->num_cu, &pl))
         return fail(ctx, DSKGPU_E_OVERFLOW, "cannot partition finer (table overflow persists)");
     pl.d1.world = pl.d2.world = ctx->cfg.world_size; pl.d1.npass = pl.d2.npass = ps.npass; pl.d1.pass = pl.d2.pass = ps.pass;
+    pl.d1.ones_is_key = pl.d2.ones_is_key = ctx->sentinel_ok ? 0u : 1u;      // (k = 64, 128: no key array of this pass is padded, and the all-ones key in one is the k-mer)
     { const int e = upload_descs1(ctx, ps); if (e) return e; }
     if (pl.levels == 2 && ctx->sentinel_ok && !ctx->opt2_off && !ctx->tune.no_opt2 && ascatter_lds(W, pl.P2) <= 160 * 1024)
         ps.opt_cap = opt_groups(W) * (8u / W);                                                 // 545 (two-word keys: 1091) groups of 64 B

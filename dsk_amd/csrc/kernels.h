@@ -107,7 +107,9 @@ template <int W> __device__ __forceinline__ u64 digit_word(const KN<W>& h) { ret
 //             k-mers than one pass may hold (2^32 offsets / the HBM budget) are counted in several
 //             passes over the encoded reads, each keeping only its share of the key space -- the
 //             in-HBM counterpart of DSK's disk passes (doc/paper.tex:65-67, README.md:126-130).
-struct DigitSpec { u32 mode, pa, pb, world, npass, pass; };   // mode 0: owner(pa=G)  1: level1(pa=P1)  2: level2(pa=P1,pb=P2)
+struct DigitSpec { u32 mode, pa, pb, world, npass, pass, ones_is_key; };   // mode 0: owner(pa=G)  1: level1(pa=P1)  2: level2(pa=P1,pb=P2)
+// ones_is_key (multi-word keys): the all-ones key is the mixed form of a real k-mer of this k (k = 64, 128: ctx->sentinel_ok is false) --
+// nothing pads a key array with it then, and the key-array sources must hand it on as the key it is
 // MODE (compile time): 0 owner, 1 level 1, 2 level 2, 3 level 1 of a multi-pass count (adds the pass filter;
 // a separate instantiation so that the single-pass tile body stays branch-free)
 // pass of a key (of ds.npass): the fraction left over by the owner in h[31:12]
@@ -164,9 +166,9 @@ __device__ __forceinline__ u32 tile_keys_reads(const u64* __restrict__ packed, c
     return vm;
 }
 
-__device__ __forceinline__ bool is_pad_key(u64 h) { return h == DSK_EMPTY; }
-template <int W> __device__ __forceinline__ bool is_pad_key(const KN<W>& h) {      // (multi-word key arrays with pads: the sampled records of the receive side)
-    bool e = true;
+__device__ __forceinline__ bool is_pad_key(u64 h, const DigitSpec&) { return h == DSK_EMPTY; }      // (never a k-mer for k <= 32)
+template <int W> __device__ __forceinline__ bool is_pad_key(const KN<W>& h, const DigitSpec& ds) {      // (multi-word key arrays with pads: the sampled records of the receive side)
+    bool e = !ds.ones_is_key;
 #pragma unroll
     for (int x = 0; x < W; ++x) e = e && (h.w[x] == DSK_EMPTY);
     return e;
@@ -177,7 +179,7 @@ template <int W> __device__ __forceinline__ bool keys_same(const KN<W>& a, const
 // thread loads keys tid + j*SC_NT (coalesced).
 template <int W>
 __device__ __forceinline__ u32 tile_keys_array(const typename KeyT<W>::T* __restrict__ in, u64 k0, u64 kend,
-                                               typename KeyT<W>::T (&h)[Tile<W>::KPT]) {
+                                               typename KeyT<W>::T (&h)[Tile<W>::KPT], const DigitSpec& ds) {
     // branch-free: out-of-range lanes re-read the tile's last key (masked out by the
     // returned bits), so the loads stay one straight-line burst the compiler can count
     const typename KeyT<W>::T* base = in + k0;                       // wave-uniform
@@ -189,7 +191,7 @@ __device__ __forceinline__ u32 tile_keys_array(const typename KeyT<W>::T* __rest
         const u32 o = threadIdx.x + (u32)j * SC_NT;
         const bool ok = o < n;
         h[j] = base[ok ? o : n - 1];
-        vm |= ((ok && !is_pad_key(h[j])) ? 1u : 0u) << j;      // (the all-ones sentinel pads the slices a level-0 scatter leaves: never a key)
+        vm |= ((ok && !is_pad_key(h[j], ds)) ? 1u : 0u) << j;      // (the all-ones sentinel pads the slices a level-0 scatter leaves: never a key)
     }
     return vm;
 }
@@ -227,13 +229,13 @@ __global__ __launch_bounds__(SC_NT) void k_hist(const u64* __restrict__ packed, 
                 process(ha, vma);
             }
         } else {
-            if (d.begin < d.end) vma = tile_keys_array<W>(keys, d.begin, d.end, ha);
+            if (d.begin < d.end) vma = tile_keys_array<W>(keys, d.begin, d.end, ha, ds);
             for (u64 t0 = d.begin; t0 < d.end; t0 += 2 * step) {   // two tiles per trip: register ping-pong, no copies
-                if (t0 + step < d.end) vmb = tile_keys_array<W>(keys, t0 + step, d.end, hb);
+                if (t0 + step < d.end) vmb = tile_keys_array<W>(keys, t0 + step, d.end, hb, ds);
                 process(ha, vma);
                 const u64 t1 = t0 + step;
                 if (t1 >= d.end) break;
-                if (t1 + step < d.end) vma = tile_keys_array<W>(keys, t1 + step, d.end, ha);
+                if (t1 + step < d.end) vma = tile_keys_array<W>(keys, t1 + step, d.end, ha, ds);
                 process(hb, vmb);
             }
         }
@@ -620,7 +622,7 @@ __global__ __launch_bounds__(SC_NT, 4) void k_scatter(const u64* __restrict__ pa
             // next tile_scan / stage writes.
         };
         auto process = [&](Key (&h)[KPT], u32 vm) { rank_and_stage(h, vm); write_out(); };
-        if (SRC == 1 && d.begin < d.end) vma = tile_keys_array<W>(keys, d.begin, d.end, ha);
+        if (SRC == 1 && d.begin < d.end) vma = tile_keys_array<W>(keys, d.begin, d.end, ha, ds);
         lds_barrier();
         if constexpr (SRC == 2) {              // records: `packed` is the record array, the chunk range is in records
             if constexpr (W <= 2) {
@@ -720,11 +722,11 @@ __global__ __launch_bounds__(SC_NT, 4) void k_scatter(const u64* __restrict__ pa
             }
         } else {
             for (u64 t0 = d.begin; t0 < d.end; t0 += 2 * step) {   // two tiles per trip: register ping-pong, no copies
-                if (t0 + step < d.end) vmb = tile_keys_array<W>(keys, t0 + step, d.end, hb);   // prefetch under the LDS phases
+                if (t0 + step < d.end) vmb = tile_keys_array<W>(keys, t0 + step, d.end, hb, ds);   // prefetch under the LDS phases
                 process(ha, vma);
                 const u64 t1 = t0 + step;
                 if (t1 >= d.end) break;
-                if (t1 + step < d.end) vma = tile_keys_array<W>(keys, t1 + step, d.end, ha);
+                if (t1 + step < d.end) vma = tile_keys_array<W>(keys, t1 + step, d.end, ha, ds);
                 process(hb, vmb);
             }
         }
@@ -1063,7 +1065,7 @@ __global__ __launch_bounds__(SC_NT, 4) void k_scatter_al(const typename KeyT<W>:
             u32 rk[KPT];
 #pragma unroll
             for (int j = 0; j < KPT; ++j) {
-                const bool pad = (OPT && is_empty_key(h[j])) || is_pad_key(h[j]);      // sentinel of a level-1 slice tail / of a level-0 key array
+                const bool pad = (OPT && is_empty_key(h[j])) || is_pad_key(h[j], ds);      // sentinel of a level-1 slice tail / of a level-0 key array
                 u32 dj = key_digit<MODE>(digit_word(h[j]), ds);             // unconditional + select: no exec-mask traffic around the multiply
                 asm volatile("" : "+v"(dj));
                 dj = ((vm & (1u << j)) && !pad && key_in_pass<MODE>(digit_word(h[j]), ds)) ? dj : P;
@@ -2417,7 +2419,7 @@ __global__ __launch_bounds__(SC_NT) void k_collect_heavy(const u64* __restrict__
         for (u64 t0 = d.begin; t0 < d.end; t0 += step) {
             Key h[KPT];
             u32 vm;
-            if constexpr (SRC == 0) vm = tile_keys_reads(packed, inval, t0, d.end, k, h); else vm = tile_keys_array<W>(keys, t0, d.end, h);
+            if constexpr (SRC == 0) vm = tile_keys_reads(packed, inval, t0, d.end, k, h); else vm = tile_keys_array<W>(keys, t0, d.end, h, ds);
 #pragma unroll
             for (int j = 0; j < KPT; ++j) {
                 u32 f = 0xFFu;
