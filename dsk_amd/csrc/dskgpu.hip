@@ -14,6 +14,7 @@
 #include <system_error>
 #include "engine.h"
 #include "kernels.h"
+#include "planning.h"
 #include "superkmer_recv.h"
 #include "rawparse.h"
 
@@ -290,84 +291,26 @@ inline void launch_count(dskgpu_ctx* ctx, unsigned grid, typename KeyT<W>::T* ke
     launch_count_impl(ctx, grid, keys, solid_keys, solid_ab, ovf, cp);
 }
 
-struct Plan {
-    int levels;
-    u32 P1, P2, F;
-    DigitSpec d1, d2;
-};
-
-#define TARGET_KEYS 2900      // mean keys per final sub-partition (the count kernel prefetches 3072 per sub-partition; table: 4096 slots, 3584 usable)
-#define TARGET_KEYS2 2560     // two-word keys: 3072-slot top-word table (k_count2v3), 2688 usable; 4096-slot index table (k_count_mw)
-#ifndef TARGET_KEYS4
-#define TARGET_KEYS4 640      // four-word keys: 1024 staged per sub-partition
-#endif
 #ifndef OPT_GROUPS4
 #define OPT_GROUPS4 OPT_GROUPS
 #endif
-#define MAX_LEVEL_BINS 2048
-#define ONE_LEVEL_BINS 1024
 #define CH2 65536u            // keys per level-2 chunk
 #define OPT_GROUPS 545u
 #define OPT_GROUPS2 1023u     // two-word keys: regions of 1023 groups of 64 B = 4092 keys (the count kernels are paced by their two barriers per
                               // sub-partition, not by its keys: half as many sub-partitions of twice the size -- see NOTEBOOK.md section 6 "k = 63")
 inline u32 opt_groups(int W) { return W == 2 ? (AL_G2 == 8 ? 1022u : OPT_GROUPS2) : (W == 1 && AL_G1 == 16) ? 546u : W == 4 ? OPT_GROUPS4 : OPT_GROUPS; }      // (AL_G2 == 8, experiments: 511 groups of 128 B)
-inline u64 target_keys(int W) { return W == 1 ? TARGET_KEYS : W == 2 ? TARGET_KEYS2 : TARGET_KEYS4; }
 #define OPT_CAP 4360u          // segment-owned level-2 scatter: keys per sub-partition region (mean <= TARGET_KEYS).
                               // 545 groups of 64 B -- an ODD number, so the region starts (and the write fronts that advance
                               // through all regions in step) spread over every HBM channel instead of camping on a few
 
-// Final sub-partitions F = P1 * P2 sized to the input (any integer, not a power
-// of two: digits use the multiply-shift reduction of key_digit()).
-bool make_plan(u64 n_upper, int extra_bits, int W, u32 num_cu, Plan* pl) {
-    const u64 target = target_keys(W);
-    u64 F = ((n_upper + target - 1) / target) << extra_bits;
-    if (F < 2) F = 2;
-    if (F <= ONE_LEVEL_BINS) { pl->levels = 1; pl->P1 = (u32)F; pl->P2 = 1; }
-    else {
-        // Level 1 costs more per key the more bins it has (3.05 ps + 1.7 fs per bin and key, NOTEBOOK.md section 6: every tile leaves a
-        // partial line per bin), level 2 costs the same for any number of bins its kernel holds (the per-bin carry must fit LDS:
-        // p2max).  So: the FEWEST level-1 bins that keep level 2 inside that kernel -- but at least one segment per CU, and a
-        // multiple of the CU count: level 2 gives every block whole segments (level-1 bins), one block per CU, and a count that is
-        // not a multiple leaves some blocks one segment more than the rest (770 segments on 256 CUs cost 20 %).
-        u64 p2max = MAX_LEVEL_BINS; while (p2max > 64 && ascatter_lds(W, (u32)p2max) > 160 * 1024) --p2max;
-        u64 p1 = 1; while (p1 * p1 < F) ++p1;                                  // balanced split: small inputs
-        const bool large = F >= (u64)num_cu * 64;
-        if (large) {
-            p1 = std::max<u64>((F + p2max - 2) / (p2max - 1), num_cu);         // (p2max - 1: room for the odd-P2 adjustment below)
-            p1 = (p1 + num_cu - 1) / num_cu * num_cu;
-            if (p1 > MAX_LEVEL_BINS - 8) p1 = MAX_LEVEL_BINS - 8;
-        }
-        u64 p2 = (F + p1 - 1) / p1;
-        // An ODD number of level-2 bins: the regions of sub-partition q start q * 545 groups of 64 B into the buffer, and the
-        // blocks walk their segments in step, so with an even P2 (768 * 545 * 64 B = a multiple of 8 KB between segments) all
-        // write fronts sit on the same few HBM channels -- measured 6.0 ms at P2 = 768 against 4.7-5.0 ms at P2 = 769.
-        if (p2 % 2 == 0 && p2 + 1 <= p2max) ++p2;
-        if (p1 > MAX_LEVEL_BINS || p2 > MAX_LEVEL_BINS) return false;
-        pl->levels = 2; pl->P1 = (u32)p1; pl->P2 = (u32)p2;
-    }
-    pl->F = pl->P1 * pl->P2;
-    pl->d1 = DigitSpec{1u, pl->P1, 0u, 1u, 1u, 0u};
-    pl->d2 = DigitSpec{2u, pl->P1, pl->P2, 1u, 1u, 0u};
-    return true;
-}
+// (make_plan: planning.h)
 
 // Build level-1 chunk descriptors on the host (ranges are static).
 // unit = tile granularity of the source (Tile<W>::WORDS words or Tile<W>::KEYS keys).
 void build_descs1(dskgpu_ctx* ctx, u64 n_units_total, u64 tile, u64 max_chunks, u32* nch_out) {
-    const u64 ntiles = std::max<u64>(1, (n_units_total + tile - 1) / tile);
-    u64 nch = std::min<u64>(ntiles, max_chunks);
-    const u64 tpc = (ntiles + nch - 1) / nch;
-    nch = (ntiles + tpc - 1) / tpc;
+    u64 tpc; const u64 nch = chunks1(n_units_total, tile, max_chunks, &tpc);      // (planning.h)
     ctx->h_descs1.resize(nch);
-    for (u64 c = 0; c < nch; ++c) {
-        ChunkDesc d;
-        d.begin = c * tpc * tile;
-        d.end = std::min<u64>(n_units_total, (c + 1) * tpc * tile);
-        if (d.begin > d.end) d.begin = d.end;
-        d.flat_base = (u32)c;
-        d.stride = (u32)nch;
-        ctx->h_descs1[c] = d;
-    }
+    for (u64 c = 0; c < nch; ++c) ctx->h_descs1[c] = chunk_desc1(c, nch, tpc, tile, n_units_total);
     *nch_out = (u32)nch;
 }
 
@@ -693,9 +636,10 @@ int pass_layout1(dskgpu_ctx* ctx, PassState<W>& ps) {
     if (ps.opt1) {
         const u32 nch1 = ps.nch1;
         const unsigned grid1 = ps.grid1 = scatter_grid(ctx, W, pl.P1, nch1, !uniform1);
-        // a block's share of the input: it walks chunks blockIdx, blockIdx + grid, .. (equal chunks, the busiest block has ceil(nch/grid))
-        const u64 cpb = (nch1 + grid1 - 1) / grid1;
-        double share = (double)cpb / (double)nch1;
+        // a block's share of the input: it walks chunks blockIdx, blockIdx + grid, .. -- the busiest block's units over all units, from the
+        // descriptors upload_descs1 has just built, nch1 of them (busiest_share1, planning.h: the last chunk may be short, so this is not
+        // ceil(nch / grid) / nch)
+        double share = busiest_share1(ctx->h_descs1.data(), nch1, grid1);
         if (src.from_rec && ctx->rec_slice_end.size() > 1) {      // a launch per slice: the busiest block's chunks of every slice add up
             share = 0.0;
             u64 rb = 0;
@@ -1842,6 +1786,7 @@ int dskgpu_create(const dskgpu_config* cfg, dskgpu_ctx** out) {
         ctx->l0_sender.sp = sp;      // (the same k, m and R; its G is the passes of the count that uses it)
     }
     { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && cus > 0) ctx->num_cu = cus; }      // (one attribute, not the whole property block)
+    if (ctx->tune.num_cu) ctx->num_cu = (int)ctx->tune.num_cu;      // DSKGPU_NUM_CU (tests): no kernel waits for another block, so a grid sized for more or fewer CUs than the device has only runs in more or fewer rounds
     e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
     if (e != hipSuccess) { g_create_err = std::string("hipStreamCreate: ") + hipGetErrorString(e); delete ctx; return DSKGPU_E_DEVICE; }
     ctx->own_stream = true;

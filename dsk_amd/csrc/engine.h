@@ -90,6 +90,7 @@ struct Tuning {
     bool cc_plain = false, cc_stages = false;   // DSKGPU_CC_PLAIN: the component table by one add per unitig and column instead of the wave-combined form; DSKGPU_CC_STAGES: the build of the components marks "component labelling" / "component numbering" / "component table" instead of "components" (tools/bench_components.py)
     bool correct_staged = false;                // DSKGPU_CORRECT_STAGED: the trials of dskgpu_correct_reads by the staged pair (one window of every alternative as a batch, then a wave per surviving candidate) instead of one thread per candidate, which is the default because it measured faster (profiles/read_correction.md; tests, tools/bench_correct.py)
     u32 pairs_reg_max = ~0u, pairs_grid = 0; bool pairs_no_skip = false;    // DSKGPU_PAIRS_GRID: blocks of a pair kernel at the most (unset: CP_GRID; tests: 2 makes every block walk several stretches of a small matrix); DSKGPU_PAIRS_REG_MAX: n_colors (0..8) up to which dskgpu_colors_pairs runs the one-thread-per-row kernel instead of the tiled one (unset: CP_REG_SWITCH of colors.h); DSKGPU_PAIRS_NO_SKIP: the tiled kernel does not step over all-zero rows (tests, tools/bench_color_pairs.py, profiles/color_pairs.md)
+    u32 num_cu = 0;                             // DSKGPU_NUM_CU: the CU count every grid and plan is sized from (1..1024; unset, 0 or out of range: the device's own; tests: 1 and 3 make every block of a small input take several units of work, 32 and 304 are a CPX partition and a device whose count is no power of two)
     void read() {
         auto on =[](const char* n) { return getenv(n) != nullptr; };
         auto num = [](const char* n, u64 dflt) { const char* e = getenv(n); return e ? (u64)atoll(e) : dflt; };
@@ -106,6 +107,7 @@ struct Tuning {
         cc_plain = on("DSKGPU_CC_PLAIN"); cc_stages = on("DSKGPU_CC_STAGES");
         correct_staged = on("DSKGPU_CORRECT_STAGED");
         pairs_reg_max = (u32)num("DSKGPU_PAIRS_REG_MAX", pairs_reg_max); pairs_no_skip = on("DSKGPU_PAIRS_NO_SKIP"); pairs_grid = (u32)num("DSKGPU_PAIRS_GRID", 0);
+        { const u64 n = num("DSKGPU_NUM_CU", 0); num_cu = n >= 1 && n <= 1024 ? (u32)n : 0u; }
         rs_block_rows = (u32)num("DSKGPU_RS_BLOCK_ROWS", 0); rs_bbits = (u32)num("DSKGPU_RS_BBITS", 0); rs_heavy = (u32)num("DSKGPU_RS_HEAVY", 0);
     }
 };

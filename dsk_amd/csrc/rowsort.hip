@@ -8,6 +8,7 @@
 
 #include "engine.h"
 #include "partsort.h"
+#include "planning_rowsort.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -105,27 +106,7 @@ int sort_rows_full_multiword(dskgpu_ctx* ctx, u64 n) {
     return DSKGPU_OK;
 }
 
-// step A's chunks: about 64 K rows each, a multiple of the CU count of them (whole rounds of blocks), at least one tile each (tile 0:
-// no such floor) -> the number of chunks, *chunk = rows per chunk
-u64 step_a_chunks(u64 n, u64 ncu, u64 tile, u64* chunk) {
-    u64 nch = (n + 65535) / 65536;
-    nch = (nch + ncu - 1) / ncu * ncu;
-    if (tile) nch = std::max<u64>(1, std::min<u64>(nch, (n + tile - 1) / tile));
-    *chunk = (n + nch - 1) / nch;
-    return (n + *chunk - 1) / *chunk;
-}
-
-// the same over a sparse source (the rows still lie in the count kernel's F sub-partitions): chunks = groups of *qpc consecutive sub-partitions
-// (about 64 K rows, at most RS_SP_MAXQ sub-partitions), *nch_sp of them, + one chunk of *chunk rows for the dense tail (the rows of the
-// k-mers counted apart) -> the number of chunks
-u64 step_a_chunks_sparse(u64 F, u64 n_sparse, u32 n_tail, u64 ncu, u32* qpc, u64* nch_sp, u64* chunk) {
-    u64 want = std::max<u64>(1, (n_sparse + 65535) / 65536);
-    want = (want + ncu - 1) / ncu * ncu;
-    *qpc = (u32)std::min<u64>(std::max<u64>(1, (F + want - 1) / want), RS_SP_MAXQ);
-    *nch_sp = (F + *qpc - 1) / *qpc;
-    *chunk = n_tail;
-    return *nch_sp + (n_tail ? 1 : 0);
-}
+// (step_a_chunks, step_a_chunks_sparse: planning_rowsort.h)
 
 // the fewest top bits of the first digit (bA bits; bucket b = [start[b], start[b + 1])) whose groups of buckets hold <= rs_max rows
 // each; -1 when one bucket alone holds more

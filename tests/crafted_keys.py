@@ -17,6 +17,8 @@ word for fixed lower words.  h can be chosen freely only where the top word is (
 63 / 127 (62 bits), and by enumeration down to k = 27 (54 bits: 523 members per (hi32, low12)).  For k = 33..~60 and 65..~125 the
 top word holds too few bits (for k <= 96 word 3 is zero: h is a hash of the low words) -- not crafted.
 """
+import os
+
 import numpy as np
 
 M64 = (1 << 64) - 1
@@ -361,8 +363,20 @@ def ascatter_lds(W, P):
     return keys * key + P * (G - 1) * key + (P + 1) * 4 + P * 4 + (P + 1) * 12 + P * 2 + 20 * 4 + 32 + 320 * 4 + 16 + 2 * 64 * 2 + 16
 
 
-def make_plan(n_upper, extra_bits, W, num_cu=256):
-    """dskgpu.hip: make_plan -> (levels, P1, P2), or None where it gives up"""
+def plan_num_cu():
+    """the CU count the library plans with: DSKGPU_NUM_CU where the environment forces one (1..1024, as Tuning::read takes it), else the
+    MI355X's 256"""
+    try:
+        n = int(os.environ.get("DSKGPU_NUM_CU", "0"))
+    except ValueError:
+        n = 0
+    return n if 1 <= n <= 1024 else 256
+
+
+def make_plan(n_upper, extra_bits, W, num_cu=None):
+    """planning.h: make_plan -> (levels, P1, P2), or None where it gives up"""
+    if num_cu is None:
+        num_cu = plan_num_cu()
     target = TARGET_KEYS[W]
     F = ((n_upper + target - 1) // target) << extra_bits
     F = max(F, 2)
@@ -375,7 +389,7 @@ def make_plan(n_upper, extra_bits, W, num_cu=256):
     while p1 * p1 < F:
         p1 += 1
     if F >= num_cu * 64:
-        p1 = max((F + p2max - 2) // (p2max - 1), num_cu)
+        p1 = max((F + p2max - 2) // (p2max - 1), num_cu, 2)
         p1 = (p1 + num_cu - 1) // num_cu * num_cu
         p1 = min(p1, 2048 - 8)
     p2 = (F + p1 - 1) // p1

@@ -390,23 +390,31 @@ def test_mostly_invalid_stream_with_a_dense_tail(oracle, dev, monkeypatch):
     assert st["n_levels"] == 2 and st["n_retries"] >= 1 and st["n_heavy"] == 0
 
 
+def finer_partition_retry_case(oracle, reads, k, dev, monkeypatch):
+    """the first half of test_table_overflow_retry_partitions_finer for one k: a load limit that the plain plan exceeds and a 2-4x
+    finer one meets -> the stats of the repeated count (DSKGPU_TABLE_MAXLOAD stays set)"""
+    from dsk_amd import KmerCounter
+    with KmerCounter(kmer_size=k) as kc:
+        t = torch.from_numpy(reads).to(dev)
+        kc.set_reads_device(t.data_ptr(), t.numel())
+        kc.count()
+        st0 = kc.stats()
+    per_sub = st0["n_distinct"] / st0["n_final_bins"]
+    monkeypatch.setenv("DSKGPU_TABLE_MAXLOAD", str(max(8, int(per_sub * 0.8))))    # the first plan overflows, a 2-4x finer one fits
+    st = check_against_oracle(oracle, reads, k, dev)
+    assert 1 <= st["n_retries"] <= 3 and st["n_final_bins"] > st0["n_final_bins"]
+    return st
+
+
 def test_table_overflow_retry_partitions_finer(oracle, dev, monkeypatch):
     """A count table that would hold more distinct keys than its load limit flags overflow and the host repeats the pass
     with twice the sub-partitions (dskgpu.hip: extra_bits).  DSKGPU_TABLE_MAXLOAD lowers the limit so that the first
     plan overflows; the result must be the same and stats.n_retries says how often the plan was refined.  A limit no
     refinement can meet ends with DSKGPU_E_OVERFLOW after three retries."""
-    from dsk_amd import KmerCounter, synth, DskGpuError
+    from dsk_amd import synth, DskGpuError
     reads = synth.make_reads(synth.make_genome(300_000, dev), 60_000, 150).cpu().numpy()
     for k in (31, 63):
-        with KmerCounter(kmer_size=k) as kc:
-            t = torch.from_numpy(reads).to(dev)
-            kc.set_reads_device(t.data_ptr(), t.numel())
-            kc.count()
-            st0 = kc.stats()
-        per_sub = st0["n_distinct"] / st0["n_final_bins"]
-        monkeypatch.setenv("DSKGPU_TABLE_MAXLOAD", str(max(8, int(per_sub * 0.8))))    # the first plan overflows, a 2-4x finer one fits
-        st = check_against_oracle(oracle, reads, k, dev)
-        assert 1 <= st["n_retries"] <= 3 and st["n_final_bins"] > st0["n_final_bins"]
+        finer_partition_retry_case(oracle, reads, k, dev, monkeypatch)
         monkeypatch.setenv("DSKGPU_TABLE_MAXLOAD", "1")
         with pytest.raises(DskGpuError) as e:
             gpu_count(reads, k, dev)
@@ -1106,11 +1114,16 @@ def test_receive_side_multi_pass_on_the_fast_path(oracle, dev, k, explicit):
 def test_multi_gpu_path_on_one_device(oracle, golden_dir, dev, world, k, explicit):
     """dskgpu_mg_scatter / dskgpu_mg_count with the exchange done by hand: `world` contexts on the
     same GPU, each fed its shard of the reads; the union of their results must equal the oracle."""
-    from dsk_amd import KmerCounter, DskGpuError
     s, _ = oracle.load_bank(os.path.join(golden_dir, "read50x_ref10K_e001.fasta.gz"))
+    multi_gpu_path_case(oracle, s, dev, world, k, explicit)
+
+
+def multi_gpu_path_case(oracle, s, dev, world, k, explicit):
+    """the body of test_multi_gpu_path_on_one_device on the stream s -> per rank (the bytes of its shard, the 64-bit words it received)"""
+    from dsk_amd import KmerCounter, DskGpuError
     recs = bytes(s).split(b"\n")
     W = 1 if k <= 32 else 2
-    ctxs, sends, counts, shards, kmers = [], [], [], [], []
+    ctxs, sends, counts, shards, kmers, sizes = [], [], [], [], [], []
     for r in range(world):
         shard = torch.from_numpy(np.frombuffer(b"\n".join(recs[r::world]) + b"\n", dtype=np.uint8).copy()).to(dev)
         kc = KmerCounter(kmer_size=k, abundance_min=1, world_size=world, rank=r, mg_explicit=explicit)
@@ -1139,6 +1152,7 @@ def test_multi_gpu_path_on_one_device(oracle, golden_dir, dev, world, k, explici
             with pytest.raises(DskGpuError):
                 ctxs[d].mg_count(recv.data_ptr(), recv.numel(), wrong)
         ctxs[d].mg_count(recv.data_ptr(), recv.numel(), hint if d % 2 == 0 else 0)
+        sizes.append((shards[d].numel(), recv.numel()))
         kk, aa = ctxs[d].rows()
         rows_k.append(kk); rows_a.append(aa); hist += ctxs[d].histogram()
     kk = np.concatenate(rows_k); aa = np.concatenate(rows_a)
@@ -1153,6 +1167,7 @@ def test_multi_gpu_path_on_one_device(oracle, golden_dir, dev, world, k, explici
     assert sum(c.stats()["n_kmers"] for c in ctxs) == ref.total
     for c in ctxs:
         c.close()
+    return sizes
 
 
 @pytest.mark.parametrize("world,k,est_scale", [(4, 31, 1.0), (2, 63, 1.0), (4, 31, 0.5), (2, 31, 3.0)])
@@ -1880,9 +1895,14 @@ def test_group_count_in_one_process(oracle, golden_dir, dev, monkeypatch, ranks,
     """dskgpu_group_*: what `dsk -nb-gpus N` runs -- N ranks inside one process, the exchange inside the library.  On the
     1-GPU box several ranks share device 0 (transport "copy"); the single-rank cases with transport "rccl" push the
     degenerate exchange (every record to owner 0) through librccl's grouped ncclSend / ncclRecv."""
+    s, _ = oracle.load_bank(os.path.join(golden_dir, "read50x_ref10K_e001.fasta.gz"))
+    group_count_case(oracle, s, monkeypatch, ranks, k, transport, explicit)
+
+
+def group_count_case(oracle, s, monkeypatch, ranks, k, transport, explicit):
+    """the body of test_group_count_in_one_process on the stream s"""
     from dsk_amd import KmerGroup
     monkeypatch.setenv("DSKGPU_GROUP_TRANSPORT", transport)
-    s, _ = oracle.load_bank(os.path.join(golden_dir, "read50x_ref10K_e001.fasta.gz"))
     recs = bytes(s).split(b"\n")
     ref = oracle.count(s, k)
     with KmerGroup([0] * ranks, kmer_size=k, abundance_min=2, nb_partitions=3, mg_explicit=explicit) as g:

@@ -386,6 +386,17 @@ def test_key_mixers_unit(bins):
     assert "ALL OK" in out, out
 
 
+def test_planners_unit(bins):
+    """C++ sweep of the host planners of dsk_amd/csrc/planning.h (tests/host/test_planning.cpp): make_plan, the level-1 chunks and the
+    row sort's chunks keep what their comments promise at every CU count from 1 to 320, every key width and extra_bits, over sizes from
+    1 to 2^33 and the neighbours of every threshold."""
+    exe = os.path.join(ROOT, "tests", "host", "test_planning")
+    if not os.path.exists(exe):
+        pytest.skip("no hipcc on this machine")
+    out = subprocess.run([exe], stdout=subprocess.PIPE).stdout.decode()
+    assert "ALL OK" in out, out[-4000:]
+
+
 def test_boundary_names_compile_and_run(bins, tmp_path):
     """A caller written with exactly the names SURVEY.md section 8(b) lists (Group::getPartition<Count>, Tool::createIterator,
     LOCAL, Integer::apply<Functor,Parameter>, StorageFactory, OptionFailure::displayErrors ...) builds against the host layer
