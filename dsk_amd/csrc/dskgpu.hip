@@ -1,6 +1,6 @@
-// dskgpu.hip -- C-ABI (include/dskgpu.h) over the HIP kernels in kernels.h.  The row order of a result is rowsort.hip's.
-// Host-side orchestration of the count path that stands where
-// SortingCountAlgorithm<span>::execute() is called (src/DSK.cpp:60).
+// dskgpu.hip -- the count path over the HIP kernels in kernels.h, and its part of the C-ABI (include/dskgpu.h): create / destroy, count,
+// the receive side of the multi-GPU exchange, the result.  The other units and what they own: engine.h.  Host-side orchestration that
+// stands where SortingCountAlgorithm<span>::execute() is called (src/DSK.cpp:60).
 // gfx950 only; there is no CPU fallback: every entry point needs a HIP device.
 #include <algorithm>
 #include <cstdio>
@@ -10,15 +10,10 @@
 #include <string>
 #include <vector>
 
-#include <thread>
-#include <system_error>
 #include "engine.h"
 #include "kernels.h"
 #include "planning.h"
 #include "superkmer_recv.h"
-#include "rawparse.h"
-
-#include <rocprim/device/device_radix_sort.hpp>
 
 #define DSKGPU_VERSION "dskgpu 0.1 (gfx950)"
 
@@ -1073,12 +1068,12 @@ int pass_rows(dskgpu_ctx* ctx, PassState<W>& ps) {
     bool sparse_sort = false;
     if constexpr (W <= 2) {
         sparse_sort = ps.npass == 1 && ctx->job_passes == 1 && ns > 0 && ns <= rs_max_rows(ctx) && !(ctx->cfg.flags & DSKGPU_F_NO_SORT) &&
-                      !ctx->tune.rs_slab_rows && !ctx->bank_job.active && (W == 1 || 2u * ctx->cfg.kmer_size > 64u);
+                      !ctx->tune.rs_slab_rows && !ctx->banks.job.active && (W == 1 || 2u * ctx->cfg.kmer_size > 64u);
     } else {
         // four-word rows: sparse only for DSKGPU_F_PARTITION_ORDER (k_part_sort4 reads them there and writes them dense into ro / rows_ab, which is
         // where the global sort of four-word rows, sort_rows4, wants them should a block give up); without the flag k_compact as before
         sparse_sort = (ctx->cfg.flags & DSKGPU_F_PARTITION_ORDER) && ps.npass == 1 && ctx->job_passes == 1 && ns > 0 && ns < 0xFFFF0000ull &&
-                      !(ctx->cfg.flags & DSKGPU_F_NO_SORT) && !ctx->tune.rs_slab_rows && !ctx->bank_job.active;
+                      !(ctx->cfg.flags & DSKGPU_F_NO_SORT) && !ctx->tune.rs_slab_rows && !ctx->banks.job.active;
     }
     if (sparse_sort) ctx->sp_rows = sparse_rows<W>(ctx, ps, ro, rows_ab, (u32)nhs);
     PartPasses& mp = ctx->rs.mp;
@@ -1338,7 +1333,7 @@ int run_pipeline(dskgpu_ctx* ctx, bool from_reads, const typename KeyT<W>::T* d_
         ctx->job_passes = npass;
         PartPasses& mp = ctx->rs.mp;
         mp.passes.clear(); mp.off_used = 0;
-        mp.ok = npass > 1 && (ctx->cfg.flags & DSKGPU_F_PARTITION_ORDER) && !(ctx->cfg.flags & DSKGPU_F_NO_SORT) && !ctx->bank_job.active;
+        mp.ok = npass > 1 && (ctx->cfg.flags & DSKGPU_F_PARTITION_ORDER) && !(ctx->cfg.flags & DSKGPU_F_NO_SORT) && !ctx->banks.job.active;
         if (mp.ok) { CK(mp.flag.ensure(256)); CK(hipMemsetAsync(mp.flag.p, 0, 4, ctx->stream)); }
         for (u32 p = 0; p < npass; ++p) {
             PassResult r{};
@@ -1545,202 +1540,11 @@ int sk_count(dskgpu_ctx* ctx, const u64* d_rec, u64 recv_words, u64 n_kmers_hint
     return rc;
 }
 
-// Multi-bank count: every bank is counted on its own (all distinct k-mers kept), the per-bank rows are
-// united and sorted by k-mer, and k_merge_banks applies the solidity kind / builds the histograms.  In steps, so that the
-// in-process group (group.hip) can put its own count -- scatter, exchange, mg_count -- between them:
-//   banks_begin   the per-bank counts keep every k-mer (abundance window 1 .. max, rows unsorted); the union is empty
-//   banks_select  the context's read stream = bank b of the stream it was given (or all of it again: b = ~0u)
-//   banks_add     the rows of the count just finished join the union as bank b
-//   banks_finish  configuration and read stream restored; union sorted by k-mer, merged -> the result of the context
-
-u32 banks_of(dskgpu_ctx* ctx) {
-    std::vector<u64> ends = ctx->bank_ends;
-    if (ends.empty() || ends.back() < ctx->n_bytes) ends.push_back(ctx->n_bytes);
-    return (u32)ends.size();
-}
-int banks_begin(dskgpu_ctx* ctx) {
-    BankJob& j = ctx->bank_job;
-    j.ends = ctx->bank_ends;
-    if (j.ends.empty() || j.ends.back() < ctx->n_bytes) j.ends.push_back(ctx->n_bytes);
-    if (j.ends.size() > 32) return fail(ctx, DSKGPU_E_ARG, "at most 32 banks are supported by the solidity kinds");
-    if (ctx->enc_keep) return fail(ctx, DSKGPU_E_STATE, "per-bank counts (-solidity-kind, -histo2D) need the reads themselves: not after dskgpu_encode_reads");
-    j.cfg = ctx->cfg; j.base = ctx->d_reads; j.total = ctx->n_bytes;
-    j.nu = 0; j.tot_kmers = 0; j.passes = 1; j.retries = 0; j.active = true;
-    ctx->cfg.abundance_min = 1; ctx->cfg.abundance_max = 0xFFFFFFFFu; ctx->cfg.flags |= DSKGPU_F_NO_SORT;
-    return DSKGPU_OK;
-}
-void banks_select(dskgpu_ctx* ctx, u32 b) {
-    BankJob& j = ctx->bank_job;
-    if (!j.active) return;
-    if (b >= j.ends.size()) { ctx->d_reads = j.base; ctx->n_bytes = j.total; }
-    else { const u64 beg = b ? j.ends[b - 1] : 0; ctx->d_reads = j.base + beg; ctx->n_bytes = j.ends[b] - beg; }
-    ctx->enc_fresh = false; ctx->sender.prepared = false;
-}
-void banks_abort(dskgpu_ctx* ctx) {      // (an error inside a per-bank count: the context gets its configuration and its read stream back)
-    BankJob& j = ctx->bank_job;
-    if (!j.active) return;
-    ctx->cfg = j.cfg; ctx->d_reads = j.base; ctx->n_bytes = j.total; j.active = false;
-}
-template <int W>
-int banks_add(dskgpu_ctx* ctx, u32 b) {
-    BankJob& j = ctx->bank_job;
-    const u64 n = ctx->n_rows, nu = j.nu;
-    j.tot_kmers += ctx->stats.n_kmers; j.passes = std::max<u32>(j.passes, (u32)ctx->stats.n_passes); j.retries += ctx->stats.n_retries;
-    bool nomem = ctx->u_val.ensure_keep((nu + n + 1) * 8, nu * 8, ctx->stream) != 0;
-    for (int x = 0; x < W; ++x) nomem = nomem || ctx->u_w[x].ensure_keep((nu + n + 1) * 8, nu * 8, ctx->stream) != 0;
-    if (nomem) return fail(ctx, DSKGPU_E_NOMEM, "bank rows");
-    if (n) {
-        for (int x = 0; x < W; ++x)
-            CK(hipMemcpyAsync(ctx->u_w[x].as<u64>() + nu, ctx->res_w[x], n * 8, hipMemcpyDeviceToDevice, ctx->stream));
-        hipLaunchKernelGGL(k_pack_bank, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->u_val.as<u64>() + nu, ctx->res_ab, n, b);
-        CK(hipStreamSynchronize(ctx->stream));
-    }
-    j.nu += n;
-    return DSKGPU_OK;
-}
-template <int W>
-int banks_finish(dskgpu_ctx* ctx) {
-    BankJob& j = ctx->bank_job;
-    const u32 B = (u32)j.ends.size();
-    const u64 nu = j.nu, total = j.total, tot_kmers = j.tot_kmers; const u32 passes = j.passes, retries = j.retries;
-    banks_abort(ctx);                          // configuration and read stream back
-    ctx->drop_result();
-    int rc = DSKGPU_OK;
-    if (nu >= 0xFFFF0000ull) return fail(ctx, DSKGPU_E_ARG, "too many distinct k-mers over the banks for the merge");
-    // ---- sort the union by k-mer
-    CK(ctx->s_w[0].ensure((nu + 1) * 8)); CK(ctx->s_val.ensure((nu + 1) * 8));
-    const unsigned gb = (unsigned)std::max<u64>(1, (nu + 255) / 256);
-    if (nu) {
-        size_t tmp = 0;
-        if (W == 1) {
-            const unsigned end_bit = std::min(64u, 2u * ctx->cfg.kmer_size);
-            // LIBRARY SORT (rocprim), labelled: bank merges (-solidity-kind other than sum / -histo2D) order (value, bank) pairs once per job -- not on the sum path
-            CK(rocprim::radix_sort_pairs(nullptr, tmp, ctx->u_w[0].as<u64>(), ctx->s_w[0].as<u64>(), ctx->u_val.as<u64>(), ctx->s_val.as<u64>(), (size_t)nu, 0u, end_bit, ctx->stream));
-            CK(ctx->srt_tmp.ensure(tmp));
-            CK(rocprim::radix_sort_pairs(ctx->srt_tmp.p, tmp, ctx->u_w[0].as<u64>(), ctx->s_w[0].as<u64>(), ctx->u_val.as<u64>(), ctx->s_val.as<u64>(), (size_t)nu, 0u, end_bit, ctx->stream));
-        } else {
-            const u64* rows[4] = {nullptr, nullptr, nullptr, nullptr};
-            for (int x = 0; x < W; ++x) rows[x] = ctx->u_w[x].as<u64>();
-            if ((rc = sort_index_multiword(ctx, rows, nu, W))) return rc;
-            const u32* idx = ctx->srt_idx.as<u32>();
-            for (int x = 0; x < W; ++x) {
-                CK(ctx->s_w[x].ensure((nu + 1) * 8));
-                hipLaunchKernelGGL(k_gather<u64>, dim3(gb), dim3(256), 0, ctx->stream, ctx->s_w[x].as<u64>(), ctx->u_w[x].as<u64>(), idx, nu);
-            }
-            CK(ctx->s_val.ensure((nu + 1) * 8));
-            hipLaunchKernelGGL(k_gather<u64>, dim3(gb), dim3(256), 0, ctx->stream, ctx->s_val.as<u64>(), ctx->u_val.as<u64>(), idx, nu);
-        }
-        CKL("bank sort");
-    }
-    // ---- merge: solidity + histograms
-    const size_t nh = (size_t)ctx->cfg.histo_max + 1;
-    CK(ctx->m_flag.ensure((nu + 2) * 4)); CK(ctx->m_pos.ensure((nu + 2) * 4)); CK(ctx->m_sum.ensure((nu + 2) * 4));
-    CK(ctx->gh2d.ensure(nh * 11 * 8));
-    CK(hipMemsetAsync(ctx->ghist.p, 0, nh * 8, ctx->stream));
-    CK(hipMemsetAsync(ctx->gh2d.p, 0, nh * 11 * 8, ctx->stream));
-    CK(hipMemsetAsync(ctx->gstats.p, 0, 32, ctx->stream));
-    MergeParams mp{B, ctx->cfg.solidity_kind, ctx->cfg.solidity_custom, ctx->cfg.abundance_min, ctx->cfg.abundance_max, ctx->cfg.histo_max,
-                   (ctx->cfg.flags & DSKGPU_F_HISTO2D) ? 1u : 0u};
-    u64 n_solid = 0;
-    if (nu) {
-        RowsIn ri{}; RowsOut ro{};
-        for (int x = 0; x < W; ++x) ri.w[x] = ctx->s_w[x].as<u64>();
-        hipLaunchKernelGGL(k_merge_banks<W>, dim3(gb), dim3(256), 0, ctx->stream, ri,
-                           ctx->s_val.as<u64>(), nu, mp, ctx->m_flag.as<u32>(), ctx->m_sum.as<u32>(), ctx->ghist.as<u64>(), ctx->gh2d.as<u64>(), ctx->gstats.as<u64>());
-        hipLaunchKernelGGL(k_copy_u32, dim3(gb), dim3(256), 0, ctx->stream, ctx->m_pos.as<u32>(), ctx->m_flag.as<u32>(), nu);
-        CKL("k_merge_banks");
-        ctx->h_sc[SC_F] = (u32)nu;
-        CK(hipMemcpyAsync(ctx->scalars.as<u32>() + SC_F, &ctx->h_sc[SC_F], 4, hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = run_scan(ctx, ctx->m_pos.as<u32>(), ctx->scalars.as<u32>() + SC_F, nu))) return rc;
-        CK(hipMemcpyAsync(&ctx->h_back[1], ctx->m_pos.as<u32>() + nu, 4, hipMemcpyDeviceToHost, ctx->stream));
-        CK(hipStreamSynchronize(ctx->stream));
-        n_solid = ctx->h_back[1];
-        CK(ctx->out_ab.ensure((n_solid + 1) * 4));
-        for (int x = 0; x < W; ++x) { CK(ctx->out_w[x].ensure((n_solid + 1) * 8)); ro.w[x] = ctx->out_w[x].as<u64>(); }
-        hipLaunchKernelGGL(k_pick_rows<W>, dim3(gb), dim3(256), 0, ctx->stream, ri,
-                           ctx->m_sum.as<u32>(), ctx->m_flag.as<u32>(), ctx->m_pos.as<u32>(), nu, ro, ctx->out_ab.as<u32>());
-        CKL("k_pick_rows");
-    }
-    ctx->hist.assign(nh, 0); ctx->hist2d.assign(nh * 11, 0);
-    CK(hipMemcpyAsync(ctx->hist.data(), ctx->ghist.p, nh * 8, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipMemcpyAsync(ctx->hist2d.data(), ctx->gh2d.p, nh * 11 * 8, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipMemcpyAsync(&ctx->h_stats[0], ctx->gstats.p, 32, hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    for (int x = 0; x < 4; ++x) ctx->res_w[x] = x < W ? ctx->out_w[x].as<u64>() : nullptr;
-    ctx->res_ab = ctx->out_ab.as<u32>();
-    ctx->n_rows = n_solid;
-    ctx->stats.n_bytes = total; ctx->stats.n_kmers = tot_kmers; ctx->stats.n_distinct = ctx->h_stats[0]; ctx->stats.n_solid = n_solid;
-    ctx->stats.n_passes = passes; ctx->stats.n_retries = retries;
-    ctx->stats.n_partitions = ctx->cfg.nb_partitions ? ctx->cfg.nb_partitions : 4u;
-    ctx->have_result = true;
-    return DSKGPU_OK;
-}
-template <int W>
-int run_banks(dskgpu_ctx* ctx) {
-    int rc = banks_begin(ctx);
-    if (rc) return rc;
-    const u32 B = (u32)ctx->bank_job.ends.size();
-    for (u32 b = 0; b < B; ++b) {
-        banks_select(ctx, b);
-        if ((rc = run_pipeline<W>(ctx, true, nullptr, 0)) || (rc = banks_add<W>(ctx, b))) { banks_abort(ctx); return rc; }
-    }
-    return banks_finish<W>(ctx);
-}
-
 }  // namespace
 
-// ---- the same steps for group.hip (one library, not part of the C-ABI)
-__attribute__((visibility("hidden"))) bool dskgpu_i_per_bank(dskgpu_ctx* ctx) {
-    const bool banks = ctx->bank_ends.size() > 1 || (!ctx->bank_ends.empty() && ctx->bank_ends.back() < ctx->n_bytes);
-    return banks && (ctx->cfg.solidity_kind != DSKGPU_SOLIDITY_SUM || (ctx->cfg.flags & DSKGPU_F_HISTO2D));
-}
-__attribute__((visibility("hidden"))) uint32_t dskgpu_i_banks(dskgpu_ctx* ctx) { return banks_of(ctx); }
-__attribute__((visibility("hidden"))) int dskgpu_i_banks_begin(dskgpu_ctx* ctx) { return banks_begin(ctx); }
-__attribute__((visibility("hidden"))) void dskgpu_i_banks_select(dskgpu_ctx* ctx, uint32_t b) { banks_select(ctx, b); }
-__attribute__((visibility("hidden"))) void dskgpu_i_banks_abort(dskgpu_ctx* ctx) { banks_abort(ctx); }
-__attribute__((visibility("hidden"))) int dskgpu_i_banks_add(dskgpu_ctx* ctx, uint32_t b) {
-    return ctx->W == 1 ? banks_add<1>(ctx, b) : ctx->W == 2 ? banks_add<2>(ctx, b) : banks_add<4>(ctx, b);
-}
-__attribute__((visibility("hidden"))) int dskgpu_i_banks_finish(dskgpu_ctx* ctx) {
-    return ctx->W == 1 ? banks_finish<1>(ctx) : ctx->W == 2 ? banks_finish<2>(ctx) : banks_finish<4>(ctx);
-}
+int count_reads(dskgpu_ctx* ctx) { return ctx->W == 1 ? run_pipeline<1>(ctx, true, nullptr, 0) : ctx->W == 2 ? run_pipeline<2>(ctx, true, nullptr, 0) : run_pipeline<4>(ctx, true, nullptr, 0); }
 
 // =============================================================== C-ABI
-static_assert(((size_t)32 << 20) / RP_BLOCK <= (size_t)RP_NT * RP_SCAN_PER, "k_rp_scan walks the block summaries of one staging piece (PIN_CHUNK) with RP_SCAN_PER per thread");
-template <int FMT>
-static void launch_raw_chunk(dskgpu_ctx* ctx, u32 n, uint8_t* out) {
-    const u32 nb = (n + RP_BLOCK - 1) / RP_BLOCK;
-    const unsigned char* in = ctx->raw_in.as<unsigned char>();
-    RawState* st = ctx->raw_state.as<RawState>();
-    hipLaunchKernelGGL((k_rp_count<FMT>), dim3(nb), dim3(RP_NT), 0, ctx->stream, in, n, ctx->raw_blk.as<RpBlock>());
-    hipLaunchKernelGGL((k_rp_scan<FMT>), dim3(1), dim3(RP_NT), 0, ctx->stream, in, n, nb, ctx->raw_blk.as<RpBlock>(), st,
-                       ctx->raw_boff.as<unsigned long long>(), ctx->raw_bstate.as<u32>(), out);
-    hipLaunchKernelGGL((k_rp_write<FMT>), dim3(nb), dim3(RP_NT), 0, ctx->stream, in, n, ctx->raw_boff.as<unsigned long long>(),
-                       ctx->raw_bstate.as<u32>(), st, out);
-}
-
-// The raw pushes' result: the stream's length comes back from the device (the one synchronisation of a raw ingest), the terminator is set.
-int raw_finish(dskgpu_ctx* ctx, u64* lines) {
-    if (!ctx->raw_pending) return DSKGPU_OK;
-    RawState s;
-    CK(hipMemcpyAsync(&s, ctx->raw_state.p, sizeof(RawState), hipMemcpyDeviceToHost, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    ctx->raw_pending = false;
-    uint8_t* dst = ctx->reads_own.as<uint8_t>();
-    if (!rp_file_ok(s)) s.bad = 1;      // (the last file, now that it is complete: its quality lines must add up to its sequence lines)
-    if (s.bad) {             // the text is not what the device parser handles: the raw pushes are dropped, the stream is what it was before them
-        ctx->reads_len = ctx->raw_base;
-        ctx->d_reads = dst; ctx->n_bytes = ctx->reads_len;
-        return fail(ctx, DSKGPU_E_FORMAT, "dskgpu_push_raw: the text is not 4-line FASTQ / FASTA as declared (the raw pushes were dropped: parse on the host and push the reads)");
-    }
-    if (s.out_len + 1 > ctx->reads_own.cap) return fail(ctx, DSKGPU_E_STATE, "dskgpu_push_raw: stream longer than its bound");
-    CK(hipMemsetAsync(dst + s.out_len, '\n', 1, ctx->stream));
-    ctx->reads_len = s.out_len + 1;
-    if (lines) *lines = s.recs;
-    ctx->d_reads = dst; ctx->n_bytes = ctx->reads_len; ctx->enc_keep = false; ctx->reads_changed();
-    return DSKGPU_OK;
-}
-
 extern "C" {
 
 const char* dskgpu_version(void) { return DSKGPU_VERSION; }
@@ -1798,27 +1602,10 @@ void dskgpu_destroy(dskgpu_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->cfg.device);
     (void)hipStreamSynchronize(ctx->stream);
-    DevBuf* bufs[] = {&ctx->reads_own, &ctx->raw_in, &ctx->raw_blk, &ctx->raw_boff, &ctx->raw_bstate, &ctx->raw_state, &ctx->packed, &ctx->inval, &ctx->bufA, &ctx->bufB, &ctx->mat1, &ctx->mat2, &ctx->sums,
-                      &ctx->descs1, &ctx->descs2, &ctx->seg, &ctx->fstart, &ctx->nsolid, &ctx->scalars, &ctx->ghist, &ctx->gstats, &ctx->chain_next, &ctx->smp_mat, &ctx->smp_descs, &ctx->boff, &ctx->hv_lut, &ctx->hv_collect, &ctx->hv_buf, &ctx->dbg, &ctx->l0buf,
-                      &ctx->out_ab, &ctx->srt_ab, &ctx->srt_tmp,
-                      &ctx->srt_idx, &ctx->srt_idx2, &ctx->srt_k, &ctx->srt_k2, &ctx->abund2, &ctx->acc_ab, &ctx->u_val,
-                      &ctx->s_val, &ctx->m_flag, &ctx->m_pos, &ctx->m_sum, &ctx->gh2d,
-                      &ctx->sk_sums, &ctx->sk_cbase, &ctx->sk_keys, &ctx->cur_state, &ctx->smp_keys, &ctx->back_dev};
-    if (ctx->back_host) (void)hipHostFree(ctx->back_host);
-    ctx->rs.release();
-    ctx->sender.release(); ctx->l0_sender.release();
-    ctx->query.release();
-    ctx->unitigs.release();
-    ctx->threading.release();
-    ctx->variants.release();
-    ctx->readsum.release();
-    ctx->colors.release();
-    ctx->filtered.release();
-    if (ctx->land) (void)hipHostFree(ctx->land);
-    for (DevBuf* b : bufs) b->release();
-    for (int i = 0; i < 4; ++i) { ctx->out_w[i].release(); ctx->srt_w[i].release(); ctx->acc_w[i].release(); ctx->u_w[i].release(); ctx->s_w[i].release(); }
+    ctx->release();              // every owner frees what it holds: the count path, then the structured concerns
+    ctx->reads.release(); ctx->banks.release(); ctx->rs.release(); ctx->sender.release(); ctx->l0_sender.release();
+    ctx->drop_result();          // (query, unitigs, threading, variants, readsum, colors, filtered: it releases each of them, and says so)
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
-    for (int i = 0; i < 2; ++i) { if (ctx->pin[i]) (void)hipHostFree(ctx->pin[i]); if (ctx->pin_ev[i]) (void)hipEventDestroy(ctx->pin_ev[i]); }
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
 }
@@ -1834,165 +1621,6 @@ int dskgpu_set_stream(dskgpu_ctx* ctx, void* hip_stream) {
         CK(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
         ctx->own_stream = true;
     }
-    return DSKGPU_OK;
-}
-
-#define PIN_CHUNK ((size_t)32 << 20)
-static_assert(PIN_CHUNK == ((size_t)32 << 20), "launch_raw_chunk's capacity check is written for 32 MB pieces");
-// pageable -> pinned: one thread copies ~10 GB/s on the host this was measured on, the link takes 55: big pieces are copied by up to eight (a memory-mapped file's pages are also faulted in by the copy)
-static void stage_copy(void* dst, const void* src, size_t n) {
-    const unsigned T = n >= ((size_t)16 << 20) ? 8u : n >= ((size_t)8 << 20) ? 4u : n >= ((size_t)2 << 20) ? 2u : 1u;
-    if (T == 1) { std::memcpy(dst, src, n); return; }
-    const size_t per = (((n + T - 1) / T) + 4095) & ~(size_t)4095;          // T * per >= n
-    auto part = [=](unsigned t) { const size_t a = (size_t)t * per; if (a < n) std::memcpy((char*)dst + a, (const char*)src + a, std::min(per, n - a)); };
-    std::thread th[7];
-    unsigned started = 1;
-    try { for (; started < T; ++started) th[started - 1] = std::thread(part, started); }
-    catch (const std::system_error&) {}                      // (no more threads to be had: the parts that got none are copied here)
-    part(0);
-    for (unsigned t = started; t < T; ++t) part(t);
-    for (unsigned t = 1; t < started; ++t) th[t - 1].join();
-}
-
-static int ensure_pinned(dskgpu_ctx* ctx) {      // the two pinned staging buffers of dskgpu_push_reads (also set up by dskgpu_reserve_reads: off the first push's path)
-    if (ctx->pin[0] && ctx->pin[1]) return DSKGPU_OK;
-    for (int i = 0; i < 2; ++i) {
-        if (!ctx->pin[i]) CK(hipHostMalloc(&ctx->pin[i], PIN_CHUNK, hipHostMallocDefault));
-        if (!ctx->pin_ev[i]) CK(hipEventCreateWithFlags(&ctx->pin_ev[i], hipEventDisableTiming));
-    }
-    return DSKGPU_OK;
-}
-
-int dskgpu_push_reads(dskgpu_ctx* ctx, const char* bytes, uint64_t nbytes) {
-    if (!ctx || (!bytes && nbytes)) return DSKGPU_E_ARG;
-    CK(hipSetDevice(ctx->cfg.device));
-    if (ctx->raw_pending) { const int e = raw_finish(ctx, nullptr); if (e) return e; }
-    const u64 need = ctx->reads_len + nbytes + 1;
-    if (need > ctx->reads_own.cap) {
-        DevBuf nb;
-        CK(nb.ensure(std::max<u64>(need, std::max<u64>(ctx->reads_own.cap * 2, (u64)256 << 20))));
-        if (ctx->reads_len) CK(hipMemcpyAsync(nb.p, ctx->reads_own.p, ctx->reads_len, hipMemcpyDeviceToDevice, ctx->stream));
-        CK(hipStreamSynchronize(ctx->stream));
-        ctx->reads_own.release();
-        ctx->reads_own = nb;
-    }
-    uint8_t* dst = ctx->reads_own.as<uint8_t>();
-    if (nbytes) {
-        // pageable host memory -> two pinned staging buffers -> HBM: the CPU copy of one chunk
-        // overlaps the DMA of the previous one (a direct pageable hipMemcpy reached 4.5 GB/s)
-        const size_t CH = PIN_CHUNK;
-        { const int e = ensure_pinned(ctx); if (e) return e; }
-        for (u64 off = 0; off < nbytes; off += CH, ctx->pin_next ^= 1) {
-            const int slot = ctx->pin_next;       // (alternates ACROSS calls too: the copy of this call's first piece overlaps the DMA of the last call's last one)
-            const size_t len = (size_t)std::min<u64>(CH, nbytes - off);
-            if (ctx->pin_used[slot]) CK(hipEventSynchronize(ctx->pin_ev[slot]));
-            stage_copy(ctx->pin[slot], bytes + off, len);
-            CK(hipMemcpyAsync(dst + ctx->reads_len + off, ctx->pin[slot], len, hipMemcpyHostToDevice, ctx->stream));
-            CK(hipEventRecord(ctx->pin_ev[slot], ctx->stream));
-            ctx->pin_used[slot] = true;
-        }
-    }
-    CK(hipMemsetAsync(dst + ctx->reads_len + nbytes, '\n', 1, ctx->stream));
-    // (no synchronisation here: the caller's bytes were copied to the pinned staging buffers above, and everything that reads the
-    //  device copy -- the count, a later growth of the buffer -- is ordered behind the DMA on the context's stream.  A bank that
-    //  hands over a few MB per call keeps the link busy this way instead of paying a round trip per call.)
-    ctx->reads_len += nbytes + 1;
-    ctx->d_reads = dst; ctx->n_bytes = ctx->reads_len; ctx->enc_keep = false; ctx->reads_changed();
-    return DSKGPU_OK;
-}
-
-int dskgpu_raw_finish(dskgpu_ctx* ctx, uint64_t* stream_bytes, uint64_t* records) {
-    if (!ctx) return DSKGPU_E_ARG;
-    CK(hipSetDevice(ctx->cfg.device));
-    u64 ln = 0;
-    const int rc = raw_finish(ctx, &ln);
-    if (stream_bytes) *stream_bytes = ctx->reads_len;
-    if (records) *records = ln;
-    return rc;
-}
-
-int dskgpu_push_raw(dskgpu_ctx* ctx, const char* text, uint64_t nbytes, int format, int new_file) {
-    if (!ctx || (!text && nbytes) || (format != DSKGPU_RAW_FASTA && format != DSKGPU_RAW_FASTQ)) return DSKGPU_E_ARG;
-    CK(hipSetDevice(ctx->cfg.device));
-    if (!ctx->raw_pending) {
-        CK(ctx->raw_state.ensure(sizeof(RawState)));
-        CK(ctx->raw_in.ensure(PIN_CHUNK));
-        const u64 maxb = PIN_CHUNK / RP_BLOCK;
-        CK(ctx->raw_blk.ensure(maxb * sizeof(RpBlock)));
-        CK(ctx->raw_boff.ensure(maxb * 8));
-        CK(ctx->raw_bstate.ensure((maxb + 1) * 4));
-        ctx->raw_base = ctx->raw_ub = ctx->reads_len;
-        hipLaunchKernelGGL(k_rp_init, dim3(1), dim3(1), 0, ctx->stream, ctx->raw_state.as<RawState>(), (unsigned long long)ctx->reads_len);
-        CKL("k_rp_init");
-        ctx->raw_pending = true;
-    } else if (new_file) {
-        hipLaunchKernelGGL(k_rp_fresh, dim3(1), dim3(1), 0, ctx->stream, ctx->raw_state.as<RawState>());
-        CKL("k_rp_fresh");
-    }
-    // what the text can leave at most: every byte, the separator in front of a new file, the terminator
-    const u64 need = ctx->raw_ub + nbytes + 2;
-    if (need > ctx->reads_own.cap) {
-        DevBuf nb;
-        CK(nb.ensure(std::max<u64>(need, std::max<u64>(ctx->reads_own.cap * 2, (u64)256 << 20))));
-        if (ctx->raw_ub) CK(hipMemcpyAsync(nb.p, ctx->reads_own.p, ctx->raw_ub, hipMemcpyDeviceToDevice, ctx->stream));
-        CK(hipStreamSynchronize(ctx->stream));
-        ctx->reads_own.release();
-        ctx->reads_own = nb;
-    }
-    uint8_t* out = ctx->reads_own.as<uint8_t>();
-    if (nbytes) {
-        const size_t CH = PIN_CHUNK;
-        { const int e = ensure_pinned(ctx); if (e) return e; }
-        for (u64 off = 0; off < nbytes; off += CH, ctx->pin_next ^= 1) {
-            const int slot = ctx->pin_next;
-            const size_t len = (size_t)std::min<u64>(CH, nbytes - off);
-            if (ctx->pin_used[slot]) CK(hipEventSynchronize(ctx->pin_ev[slot]));
-            stage_copy(ctx->pin[slot], text + off, len);
-            CK(hipMemcpyAsync(ctx->raw_in.p, ctx->pin[slot], len, hipMemcpyHostToDevice, ctx->stream));      // (one device buffer: the stream orders the next piece's DMA behind this piece's kernels, which take a fraction of the DMA's time)
-            CK(hipEventRecord(ctx->pin_ev[slot], ctx->stream));
-            ctx->pin_used[slot] = true;
-            if (format == DSKGPU_RAW_FASTQ) launch_raw_chunk<RP_FASTQ>(ctx, (u32)len, out);
-            else launch_raw_chunk<RP_FASTA>(ctx, (u32)len, out);
-            CKL("k_rp_write");
-        }
-    }
-    ctx->raw_ub += nbytes + 1;
-    return DSKGPU_OK;
-}
-
-int dskgpu_stream_bytes(dskgpu_ctx* ctx, uint64_t* stream_bytes) {
-    if (!ctx || !stream_bytes) return DSKGPU_E_ARG;
-    CK(hipSetDevice(ctx->cfg.device));
-    RAW_SYNC(ctx);
-    *stream_bytes = ctx->reads_len;
-    return DSKGPU_OK;
-}
-
-int dskgpu_rewind_reads(dskgpu_ctx* ctx, uint64_t stream_bytes) {
-    if (!ctx) return DSKGPU_E_ARG;
-    CK(hipSetDevice(ctx->cfg.device));
-    RAW_SYNC(ctx);
-    if (ctx->enc_keep) return fail(ctx, DSKGPU_E_STATE, "dskgpu_rewind_reads: the reads were encoded and released (dskgpu_encode_reads)");
-    if (stream_bytes > ctx->reads_len) return fail(ctx, DSKGPU_E_ARG, "dskgpu_rewind_reads: the stream is shorter than that");
-    ctx->reads_len = stream_bytes;
-    while (!ctx->bank_ends.empty() && ctx->bank_ends.back() > stream_bytes) ctx->bank_ends.pop_back();
-    ctx->d_reads = ctx->reads_own.as<uint8_t>(); ctx->n_bytes = ctx->reads_len; ctx->reads_changed();
-    return DSKGPU_OK;
-}
-
-int dskgpu_reserve_reads(dskgpu_ctx* ctx, uint64_t nbytes) {
-    if (!ctx) return DSKGPU_E_ARG;
-    CK(hipSetDevice(ctx->cfg.device));
-    RAW_SYNC(ctx);
-    { const int e = ensure_pinned(ctx); if (e) return e; }
-    if (nbytes + 1 <= ctx->reads_own.cap) return DSKGPU_OK;
-    DevBuf nb;
-    CK(nb.ensure(nbytes + 1));
-    if (ctx->reads_len) CK(hipMemcpyAsync(nb.p, ctx->reads_own.p, ctx->reads_len, hipMemcpyDeviceToDevice, ctx->stream));
-    CK(hipStreamSynchronize(ctx->stream));
-    ctx->reads_own.release();
-    ctx->reads_own = nb;
-    if (ctx->reads_len) ctx->d_reads = nb.as<uint8_t>();
     return DSKGPU_OK;
 }
 
@@ -2028,21 +1656,6 @@ int dskgpu_reserve_work(dskgpu_ctx* ctx, uint64_t nbytes) {
     return DSKGPU_OK;
 }
 
-int dskgpu_set_reads_device(dskgpu_ctx* ctx, const void* d_bytes, uint64_t nbytes) {
-    if (!ctx || (!d_bytes && nbytes)) return DSKGPU_E_ARG;
-    // The caller usually just PRODUCED these bytes on a stream of its own (torch's), and the context's stream is non-blocking: nothing
-    // orders the two.  Wait for the device once, here, so that a count can never read reads that are still being written (the r03
-    // intermittent failure of the multi-process test was exactly that, in the test's reference count).  Once per read set, not per count.
-    CK(hipSetDevice(ctx->cfg.device));
-    CK(hipDeviceSynchronize());
-    ctx->raw_pending = false;
-    ctx->d_reads = static_cast<const uint8_t*>(d_bytes); ctx->enc_keep = false; ctx->reads_changed();
-    ctx->n_bytes = nbytes;
-    ctx->reads_len = 0;
-    ctx->bank_ends.clear();
-    return DSKGPU_OK;
-}
-
 int dskgpu_encode_reads(dskgpu_ctx* ctx) {
     if (!ctx) return DSKGPU_E_ARG;
     CK(hipSetDevice(ctx->cfg.device));
@@ -2055,7 +1668,7 @@ int dskgpu_encode_reads(dskgpu_ctx* ctx) {
     CK(hipStreamSynchronize(ctx->stream));
     ctx->enc_keep = true;
     ctx->d_reads = nullptr;                    // the caller's buffer is never read again
-    ctx->reads_own.release(); ctx->reads_len = 0;      // pushed reads: their ASCII copy in HBM goes too (a later push starts a new read set)
+    ctx->reads.own.release(); ctx->reads.len = 0;      // pushed reads: their ASCII copy in HBM goes too (a later push starts a new read set)
     return DSKGPU_OK;
 }
 
@@ -2065,44 +1678,14 @@ int dskgpu_count(dskgpu_ctx* ctx) {
     CK(hipSetDevice(ctx->cfg.device));
     RAW_SYNC(ctx);
     ctx->stats = dskgpu_stats{};
-    const bool banks = ctx->bank_ends.size() > 1 || (!ctx->bank_ends.empty() && ctx->bank_ends.back() < ctx->n_bytes);
-    if (banks && (ctx->cfg.solidity_kind != DSKGPU_SOLIDITY_SUM || (ctx->cfg.flags & DSKGPU_F_HISTO2D)))
-        return ctx->W == 1 ? run_banks<1>(ctx) : ctx->W == 2 ? run_banks<2>(ctx) : run_banks<4>(ctx);
-    if (ctx->cfg.flags & DSKGPU_F_HISTO2D) ctx->hist2d.clear();
-    if (ctx->W == 1) return run_pipeline<1>(ctx, true, nullptr, 0);
-    if (ctx->W == 2) return run_pipeline<2>(ctx, true, nullptr, 0);
-    return run_pipeline<4>(ctx, true, nullptr, 0);
-}
-
-int dskgpu_next_bank(dskgpu_ctx* ctx) {
-    if (!ctx) return DSKGPU_E_ARG;
-    if (ctx->raw_pending) { CK(hipSetDevice(ctx->cfg.device)); RAW_SYNC(ctx); }
-    // (every call ends a bank, an empty one too: a rank of a group that was handed nothing of a small bank must count as many banks as
-    //  the others -- until r06 a bank that added no bytes was not recorded: the ranks of `dsk -nb-gpus 4 -solidity-kind min` then ran
-    //  different numbers of per-bank steps and waited for each other for ever; on one GPU an empty input file was not a bank at all)
-    ctx->bank_ends.push_back(ctx->reads_len);
-    return DSKGPU_OK;
-}
-
-int dskgpu_set_banks(dskgpu_ctx* ctx, const uint64_t* end_offsets, uint32_t n_banks) {
-    if (!ctx || (!end_offsets && n_banks)) return DSKGPU_E_ARG;
-    ctx->bank_ends.assign(end_offsets, end_offsets + n_banks);
-    for (size_t i = 1; i < ctx->bank_ends.size(); ++i)
-        if (ctx->bank_ends[i] < ctx->bank_ends[i - 1]) { ctx->bank_ends.clear(); return fail(ctx, DSKGPU_E_ARG, "bank end offsets must be non-decreasing"); }
-    return DSKGPU_OK;
-}
-
-int dskgpu_histogram2d(const dskgpu_ctx* ctx, uint64_t* out, uint32_t nrows) {
-    if (!ctx || !out) return DSKGPU_E_ARG;
-    if (!ctx->have_result || ctx->hist2d.empty()) return DSKGPU_E_STATE;
-    if (nrows != ctx->cfg.histo_max + 1) return DSKGPU_E_ARG;
-    std::memcpy(out, ctx->hist2d.data(), ctx->hist2d.size() * 8);
-    return DSKGPU_OK;
+    if (per_bank_job(ctx)) return run_banks(ctx);
+    if (ctx->cfg.flags & DSKGPU_F_HISTO2D) ctx->banks.forget_hist2d();
+    return count_reads(ctx);
 }
 
 uint64_t dskgpu_mg_send_capacity_words(dskgpu_ctx* ctx) {
     if (!ctx) return 0;
-    if (ctx->raw_pending && (hipSetDevice(ctx->cfg.device) != hipSuccess || raw_finish(ctx, nullptr) != DSKGPU_OK)) return 0;
+    if (ctx->reads.raw_pending && (hipSetDevice(ctx->cfg.device) != hipSuccess || raw_finish(ctx, nullptr) != DSKGPU_OK)) return 0;
     if (!ctx->sk_mode) return (ctx->n_bytes + 1) * (u64)ctx->W;
     if (hipSetDevice(ctx->cfg.device) != hipSuccess) return 0;
     return sk_send_capacity_words(ctx);

@@ -1,5 +1,7 @@
 // engine.h -- what the host translation units of libdskgpu share: the context (dskgpu_ctx) with its buffers and switches,
-// the error macros, and the functions one of them calls in the other.  dskgpu.hip runs the count path and the C-ABI;
+// the error macros, and the functions one of them calls in the other.  dskgpu.hip runs the count path and the rest of the C-ABI;
+// reads.hip takes the reads in -- pushed bytes, raw file text, a read set on the device (dskgpu_push_reads .. _set_reads_device) -- and owns dskgpu_ctx::reads;
+// banks.hip counts the banks of the reads one by one and merges them (dskgpu_next_bank, _set_banks, _histogram2d, the dskgpu_i_* steps of group.hip) and owns dskgpu_ctx::banks;
 // sender.hip turns the 2-bit read stream into super-k-mer records -- for the multi-GPU exchange (dskgpu_mg_sample .. _mg_slices_finish) and for
 // the record-based level 0 of a multi-pass count (rec_l0_*) -- and owns the two Sender states (dskgpu_ctx::sender, ::l0_sender);
 // rowsort.hip orders the solid rows (order_rows) and owns the row sort's state (dskgpu_ctx::rs); query.hip answers lookups in the
@@ -27,6 +29,7 @@
 #include "layouts.h"
 
 hipError_t placed_malloc(void** out, size_t bytes);      // (dskgpu.hip: DSKGPU_PLACE)
+#define HIDDEN __attribute__((visibility("hidden")))      // keeps a name out of the library's dynamic symbols (nm -D): functions one unit calls in another, and the out-of-line copies the compiler emits of in-class release() members
 
 struct DevBuf {
     void* p = nullptr;
@@ -278,12 +281,40 @@ struct Sender {
     void release() { for (DevBuf* b : {&table, &load, &sent, &lay, &cb64}) b->release(); table_dirty = true; prepared = false; nslices = 0; }
 };
 
-// state of a per-bank count in steps (banks_begin .. banks_finish below)
+// The read stream a context owns (reads.hip): `own` holds the first `len` bytes of what was pushed.  pin / pin_ev / pin_used / pin_next: the two pinned staging
+// buffers of the host-to-device copy, the event behind each one's last copy, and the slot the next piece takes.  dskgpu_push_raw: file text parsed on the device; the
+// stream's length is on the device (RawState) until raw_finish reads it back -- raw_base / raw_ub: the stream's length before the raw pushes / an upper bound of it now
+struct ReadStream {
+    DevBuf own; u64 len = 0;
+    void* pin[2] = {nullptr, nullptr}; hipEvent_t pin_ev[2] = {nullptr, nullptr}; bool pin_used[2] = {false, false}; int pin_next = 0;
+    DevBuf raw_in, raw_blk, raw_boff, raw_bstate, raw_state;
+    bool raw_pending = false; u64 raw_base = 0, raw_ub = 0;
+    HIDDEN void release() {
+        for (DevBuf* b : {&own, &raw_in, &raw_blk, &raw_boff, &raw_bstate, &raw_state}) b->release();
+        len = 0; raw_pending = false;
+        for (int i = 0; i < 2; ++i) { if (pin[i]) (void)hipHostFree(pin[i]); if (pin_ev[i]) (void)hipEventDestroy(pin_ev[i]); pin[i] = nullptr; pin_ev[i] = nullptr; pin_used[i] = false; }
+    }
+};
+
+// state of a per-bank count in steps (banks.hip: banks_begin .. banks_finish)
 struct BankJob { dskgpu_config cfg; const uint8_t* base; u64 total; std::vector<u64> ends; u64 nu, tot_kmers; u32 passes, retries; bool active = false; };
+
+// Multi-bank mode (banks.hip: solidity kinds, 2-D histogram).  ends: the end offset of every declared bank in the read stream; u_w / u_val:
+// the union of the per-bank rows and their (bank, abundance) values, s_w: the rows sorted (the sorted values borrow dskgpu_ctx::s_val);
+// m_flag / m_pos / m_sum / gh2d: the merge's solidity flags, their scan, the abundance sums and the 2-D histogram, hist2d its host copy
+struct Banks {
+    BankJob job{};
+    std::vector<u64> ends;
+    DevBuf u_w[4], s_w[4], u_val, m_flag, m_pos, m_sum, gh2d;
+    std::vector<u64> hist2d;
+    void forget_ends() { ends.clear(); }                   // the reads are another read set
+    void cut_ends(u64 stream_bytes) { while (!ends.empty() && ends.back() > stream_bytes) ends.pop_back(); }      // the stream was rewound
+    void forget_hist2d() { hist2d.clear(); }               // a count without banks has none
+    HIDDEN void release() { for (int x = 0; x < 4; ++x) { u_w[x].release(); s_w[x].release(); } for (DevBuf* b : {&u_val, &m_flag, &m_pos, &m_sum, &gh2d}) b->release(); }
+};
 
 struct dskgpu_ctx {
     dskgpu_config cfg{};
-    BankJob bank_job{};
     Tuning tune;
     int W = 1;
     int words_out = 1;
@@ -292,13 +323,10 @@ struct dskgpu_ctx {
     int num_cu = 256;
     std::string err;
 
-    // input
-    DevBuf reads_own; u64 reads_len = 0;
-    void* pin[2] = {nullptr, nullptr}; hipEvent_t pin_ev[2] = {nullptr, nullptr}; bool pin_used[2] = {false, false}; int pin_next = 0;   // pinned H2D staging
+    // input: the current reads, whoever owns the bytes (the caller, or `reads`)
+    ReadStream reads;
     const uint8_t* d_reads = nullptr; u64 n_bytes = 0;
-    // dskgpu_push_raw: file text parsed on the device; the stream's length is on the device (RawState) until raw_finish reads it back
-    DevBuf raw_in, raw_blk, raw_boff, raw_bstate, raw_state;
-    bool raw_pending = false; u64 raw_base = 0, raw_ub = 0;      // the stream's length before the raw pushes / an upper bound of it now
+    Banks banks;
 
     DevBuf packed, inval;          // K1 output
     DevBuf bufA, bufB;             // partition ping-pong
@@ -311,11 +339,18 @@ struct dskgpu_ctx {
     std::vector<ChunkDesc> h_descs_s, h_descs1, h_descs2; std::vector<u64> h_cbeg; std::vector<u32> h_boff; std::vector<u64> h_mom;
     DevBuf out_w[4], srt_w[4], acc_w[4];   // rows as struct-of-arrays: word i of every row in [i]
     DevBuf out_ab, srt_ab, srt_tmp, srt_idx, srt_idx2, srt_k, srt_k2, abund2, acc_ab;   // srt_k2: one record per row for the multi-word gather
+    DevBuf s_val;                  // row sort: the sorted keys of a pass (scratch beside srt_k / srt_idx2); the bank merge borrows it for its sorted values, as it borrows srt_tmp and srt_idx
+    // the count path's own buffers, those declared further down included (sk_*, cur_state, back_*, land): a new one goes into this list
+    HIDDEN void release() {
+        for (DevBuf* b : {&packed, &inval, &bufA, &bufB, &mat1, &mat2, &sums, &descs1, &descs2, &seg, &fstart, &nsolid, &scalars, &ghist, &gstats, &chain_next,
+                          &smp_keys, &smp_mat, &smp_descs, &boff, &dbg, &l0buf, &hv_lut, &hv_collect, &hv_buf, &out_ab, &srt_ab, &srt_tmp, &srt_idx, &srt_idx2,
+                          &srt_k, &srt_k2, &abund2, &acc_ab, &s_val, &sk_sums, &sk_cbase, &sk_keys, &cur_state, &back_dev}) b->release();
+        for (int i = 0; i < 4; ++i) { out_w[i].release(); srt_w[i].release(); acc_w[i].release(); }
+        if (back_host) (void)hipHostFree(back_host);
+        if (land) (void)hipHostFree(land);
+        back_host = land = nullptr;
+    }
     u64 max_keys_per_pass = 0;     // 0 = as many as 32-bit offsets allow
-    // multi-bank mode (solidity kinds, 2-D histogram)
-    std::vector<u64> bank_ends;    // end offset of every declared bank in the read stream
-    DevBuf u_w[4], s_w[4], u_val, s_val, m_flag, m_pos, m_sum, gh2d;
-    std::vector<u64> hist2d;
     std::vector<u32> h_starts;     // explicit-key exchange: first key of every owner in the send buffer
     // the 2-bit form of the reads (packed / inval) between calls.  Both flags describe ctx->packed, which the count path writes and checks
     // (run_encode, encode_current) as much as the sender does: they stay here, not in Sender
@@ -373,6 +408,7 @@ struct dskgpu_ctx {
     Filtered filtered;
     // a count starts, or its result is not to be read: the index of the old rows and their unitigs go with them, and so does their memory
     // -- up to 32 + 8 bytes per row that the count about to run may need (a no-op for a context that was never queried)
+    // (dskgpu_destroy frees these owners through it: it has to release(), not invalidate())
     void drop_result() { have_result = false; query.release(); unitigs.release(); threading.release(); variants.release(); readsum.release(); colors.release(); filtered.release(); }
     // the read stream changed: what was learnt about the old reads -- their kept encoding apart (enc_keep: the caller's to clear) -- goes
     void reads_changed() { enc_fresh = false; sender.prepared = false; sender.exact = false; opt2_off = false; opt1_off = false; mw_v3_off = false; rec_l0_off = false; last_rows = 0; }
@@ -424,11 +460,16 @@ inline unsigned blocks(u64 items, u64 per_block) { return (unsigned)((items + pe
 
 // dskgpu.hip
 int encode_current(dskgpu_ctx* ctx, u64* nwords_out);    // the 2-bit form of the current reads in ctx->packed / inval: encoded now, or kept (dskgpu_encode_reads)
-int raw_finish(dskgpu_ctx* ctx, u64* lines);             // the raw pushes' result: the stream's length comes back from the device
-#define RAW_SYNC(ctx) do { if ((ctx)->raw_pending) { const int e_ = raw_finish(ctx, nullptr); if (e_) return e_; } } while (0)
+HIDDEN int count_reads(dskgpu_ctx* ctx);                     // count the context's current reads with its configuration (what dskgpu_count runs when there are no banks)
 int encode_into(dskgpu_ctx* ctx, const uint8_t* d_bytes, u64 n, u64* packed, u32* inval);      // k_encode of n bytes into (n + 31) / 32 words of the caller's buffers
 int run_scan(dskgpu_ctx* ctx, u32* a, const u32* d_len, u64 max_len);
 int allow_big_lds(dskgpu_ctx* ctx, const void* fn, int bytes = 160 * 1024);      // (bytes: kernels with static LDS next to the dynamic block ask for what they use)
+
+// reads.hip, banks.hip
+int raw_finish(dskgpu_ctx* ctx, u64* lines);             // the raw pushes' result: the stream's length comes back from the device
+#define RAW_SYNC(ctx) do { if ((ctx)->reads.raw_pending) { const int e_ = raw_finish(ctx, nullptr); if (e_) return e_; } } while (0)
+HIDDEN bool per_bank_job(const dskgpu_ctx* ctx);         // the reads have several banks and the configuration needs them counted one by one
+HIDDEN int run_banks(dskgpu_ctx* ctx);                   // ... that count: every bank through count_reads, then the merge
 
 // sender.hip
 #define REC_L0_NO 2001             // rec_l0_prepare / _sweep: this input does not take the record path (not an error)

@@ -28,7 +28,7 @@
 
 #include "../../include/dskgpu.h"
 
-// the per-bank steps of dskgpu.hip (same library, not part of the C-ABI): see "Multi-bank count" there
+// the per-bank steps of banks.hip (same library, not part of the C-ABI): see "Multi-bank count" there
 bool dskgpu_i_per_bank(dskgpu_ctx* ctx);
 uint32_t dskgpu_i_banks(dskgpu_ctx* ctx);
 int dskgpu_i_banks_begin(dskgpu_ctx* ctx);
