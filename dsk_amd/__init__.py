@@ -14,5 +14,6 @@ from .engine import (  # noqa: F401
     load_library,
     make_table,
     library_path,
+    parse_ascii_rows,
     sample_distances,
 )

@@ -480,7 +480,7 @@ uint64_t sk_send_capacity_words(dskgpu_ctx* ctx);        // the exchange: words 
 int sk_scatter(dskgpu_ctx* ctx, void* d_send, uint64_t capacity_words, uint64_t* send_words);      // ... and the records into it, grouped by owner
 
 // rowsort.hip
-int order_rows(dskgpu_ctx* ctx, u64 n, u32 npass);
+int order_rows(dskgpu_ctx* ctx, u64 n, u32 npass, bool loaded = false);      // loaded: the rows of dskgpu_load_rows (equal values allowed, global order, no histogram read-back)
 u64 rs_max_rows(const dskgpu_ctx* ctx);
 int sort_index_multiword(dskgpu_ctx* ctx, const u64* const* rows, u64 n, int W);
 u32 part_sort_nparts(const SparseRows& rows);

@@ -780,7 +780,8 @@ int sort_rows4(dskgpu_ctx* ctx, u64 n, Round* r) {
 
 // ---- the first round of a row sort: the path for (W, n, flags, switches), which order_rows finishes.  rows: where the rows lie while they are
 // still sparse (W = 0: dense in out_*)
-int sort_rows(dskgpu_ctx* ctx, u64 n, const SparseRows& rows, bool global, Round* r) {
+// loaded: the rows of dskgpu_load_rows, which knows neither flag: always ordered, always globally
+int sort_rows(dskgpu_ctx* ctx, u64 n, const SparseRows& rows, bool global, Round* r, bool loaded) {
     const int W = ctx->W;
     for (int x = 0; x < 4; ++x) ctx->res_w[x] = x < W ? ctx->out_w[x].as<u64>() : nullptr;
     ctx->res_ab = ctx->out_ab.as<u32>();
@@ -788,9 +789,10 @@ int sort_rows(dskgpu_ctx* ctx, u64 n, const SparseRows& rows, bool global, Round
     ctx->rs.listed = 0;
     // (four-word rows have one sparse reader, the partition-order pass: sparse rows that it will not take are an error, not a quiet detour)
     const bool part = (ctx->cfg.flags & DSKGPU_F_PARTITION_ORDER) && !global && n < 0xFFFF0000ull;
-    if (rows.W && (n == 0 || (ctx->cfg.flags & DSKGPU_F_NO_SORT) || rows.W != W || (W == 4 && !part)))
+    const bool no_sort = (ctx->cfg.flags & DSKGPU_F_NO_SORT) && !loaded;
+    if (rows.W && (n == 0 || no_sort || rows.W != W || (W == 4 && !part)))
         return fail(ctx, DSKGPU_E_STATE, "row sort: sparse rows on a path that cannot read them");
-    if (n == 0 || (ctx->cfg.flags & DSKGPU_F_NO_SORT)) return DSKGPU_OK;
+    if (n == 0 || no_sort) return DSKGPU_OK;
     if (rows.W && part) return sort_rows_partition_order(ctx, rows, n, r);
     if (rows.W == 1) return sort_rows_msd(ctx, n, r, &rows);      // the rows of a single one-word pass, still in the count kernel's regions (pass_rows made sure this sort takes them)
     if (rows.W == 2) return sort_rows2_msd(ctx, n, r, &rows);     // (the two-word twin)
@@ -812,7 +814,9 @@ int sort_rows(dskgpu_ctx* ctx, u64 n, const SparseRows& rows, bool global, Round
 // ctx->rs.mp.ok held) -> ctx->res_* ascending, globally or inside the partitions of ctx->rs (DSKGPU_F_PARTITION_ORDER).  Finishes
 // what the first round left (k_sort_back's read-back, the listed sub-buckets, the full-width library fallback: stats.sort_fallback)
 // and, for a single pass (hist_back), copies the abundance histogram to ctx->hist with the same read-back.  Synchronous.
-int order_rows(dskgpu_ctx* ctx, u64 n, u32 npass) {
+// loaded: the caller is dskgpu_load_rows (loadrows.hip), not a count -- dense rows that may hold EQUAL values, the global order whatever
+// the context's flags say, and no histogram to read back (the load bins its own once the equal rows are combined).
+int order_rows(dskgpu_ctx* ctx, u64 n, u32 npass, bool loaded) {
     const int W = ctx->W;
     RowSort& rs = ctx->rs;
     PartPasses& mp = rs.mp;
@@ -820,7 +824,7 @@ int order_rows(dskgpu_ctx* ctx, u64 n, u32 npass) {
     // same sparse rows, except four-word ones: sort_rows4 reads the dense rows the partition pass left in out_*
     const SparseRows sparse = ctx->take_sparse_rows();
     // partition order over all passes: every pass ordered its partitions on the way in -- nothing left to sort unless a block gave up
-    if (npass > 1 && mp.ok && !mp.passes.empty()) {
+    if (npass > 1 && mp.ok && !mp.passes.empty() && !loaded) {
         u32 h_flag = 1;
         mp.h_off.resize(mp.off_used);
         CK(hipMemcpyAsync(&h_flag, mp.flag.p, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -839,12 +843,13 @@ int order_rows(dskgpu_ctx* ctx, u64 n, u32 npass) {
         }
         if (ctx->tune.verbose) fprintf(stderr, "[dskgpu] row order: a partition of one pass exceeds what one block orders -- global order over all passes instead\n");
     }
-    bool global = false;
+    bool global = loaded;
+    const bool hist_back = npass == 1 && !loaded;
     for (;;) {
         Round r;
-        int rc = sort_rows(ctx, n, global && sparse.W == 4 ? SparseRows{} : sparse, global, &r);
+        int rc = sort_rows(ctx, n, global && sparse.W == 4 ? SparseRows{} : sparse, global, &r, loaded);
         if (rc) return rc;
-        ctx->mark("sort");
+        if (!loaded) ctx->mark("sort");      // (a load marks "load order" itself, behind the fix-up rounds and the fallback that runs of equal rows can take)
         const size_t nh = ctx->hist.size();
         if (r.back) {      // histogram + the sort's two words: one copy into pinned memory (three pageable ones were ~25 us of idle GPU each)
             if ((rc = grow_pinned(ctx, rs.hist_pin, rs.hist_pin_n, nh + 2, nh + 2))) return rc;
@@ -852,13 +857,13 @@ int order_rows(dskgpu_ctx* ctx, u64 n, u32 npass) {
             hipLaunchKernelGGL(k_sort_back, dim3(1), dim3(64), 0, ctx->stream, (const u32*)ctx->scalars.as<u32>(),
                                r.back == 1 ? (const u32*)rs.ovs.as<u32>() : (const u32*)nullptr, gh + nh);
             CKL("k_sort_back");
-            const size_t from = npass == 1 ? 0 : nh;
+            const size_t from = hist_back ? 0 : nh;
             CK(hipMemcpyAsync(rs.hist_pin + from, gh + from, (nh + 2 - from) * 8, hipMemcpyDeviceToHost, ctx->stream));
             CK(hipStreamSynchronize(ctx->stream));
             rs.flag = (u32)rs.hist_pin[nh]; rs.listed = (u32)rs.hist_pin[nh + 1];
-            if (npass == 1) memcpy(ctx->hist.data(), rs.hist_pin, nh * 8);
+            if (hist_back) memcpy(ctx->hist.data(), rs.hist_pin, nh * 8);
         } else {
-            if (npass == 1) CK(hipMemcpyAsync(ctx->hist.data(), ctx->ghist.p, nh * 8, hipMemcpyDeviceToHost, ctx->stream));
+            if (hist_back) CK(hipMemcpyAsync(ctx->hist.data(), ctx->ghist.p, nh * 8, hipMemcpyDeviceToHost, ctx->stream));
             CK(hipStreamSynchronize(ctx->stream));
         }
         if (rs.part_mode && rs.flag) {      // a partition (or a value bin of one) above what a block orders in LDS: the global sort, on the same sparse rows

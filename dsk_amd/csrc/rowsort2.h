@@ -268,16 +268,16 @@ __device__ __forceinline__ bool rs2_wave_sort(u64* gh, u64* gl, u32* ga, u32 nd,
         if (lane == 63) wc[RS_CELLS] = run;
     }
     rs_wave_sync();
-    u32 o[RPL], c[RPL], fin[RPL], cmax = 0;
+    u32 o[RPL], c[RPL], fin[RPL], at[RPL], cmax = 0;
 #pragma unroll
     for (int t = 0; t < RPL; ++t) {
         const u32 i = lane + 64 * t;
-        o[t] = 0; c[t] = 0; fin[t] = 0;
+        o[t] = 0; c[t] = 0; fin[t] = 0; at[t] = 0;
         if (i < nd) {
             const u32 d = r[t] >> 16;
             o[t] = wc[d]; c[t] = wc[d + 1] - o[t];
-            const u32 at = o[t] + (r[t] & 0xFFFFu);
-            rh[at] = h[t]; rl[at] = l[t]; ra[at] = a[t];
+            at[t] = o[t] + (r[t] & 0xFFFFu);
+            rh[at[t]] = h[t]; rl[at[t]] = l[t]; ra[at[t]] = a[t];
             fin[t] = o[t];
             if (c[t] > 1) cmax = c[t] > cmax ? c[t] : cmax;
         }
@@ -287,7 +287,10 @@ __device__ __forceinline__ bool rs2_wave_sort(u64* gh, u64* gl, u32* ga, u32 nd,
     for (u32 j = 0; __ballot(j < cmax); ++j) {
 #pragma unroll
         for (int t = 0; t < RPL; ++t)
-            if (c[t] > 1 && j < c[t]) fin[t] += rs2_less(rh[o[t] + j], rl[o[t] + j], h[t], l[t]) ? 1u : 0u;      // (rows are distinct: no ties)
+            if (c[t] > 1 && j < c[t]) {      // (equal rows -- a load's input may repeat a value, a count's rows are distinct -- keep their placement order, as in rs_wave_sort)
+                const u64 xh = rh[o[t] + j], xl = rl[o[t] + j];
+                fin[t] += (rs2_less(xh, xl, h[t], l[t]) || (xh == h[t] && xl == l[t] && o[t] + j < at[t])) ? 1u : 0u;
+            }
     }
     rs_wave_sync();
 #pragma unroll
@@ -333,9 +336,12 @@ __global__ __launch_bounds__(RS_NT) void k2_big(Rows2 v, const u32* __restrict__
         const u32 o = sub[i], nd = sub[i + 1] - o;
         if (nd > block_rows) {
             if (tid == 0) {
-                // (distinct rows with no value bits left below the two digits cannot exist; shB <= 0 here would mean a broken digit plan)
-                const u32 at = sp.shB > 0 ? atomicAdd(&ovs[0], 1u) : RS2_OVS_CAP;
-                if (at < RS2_OVS_CAP) { ovs[1 + 3 * at] = base + o; ovs[2 + 3 * at] = nd; ovs[3 + 3 * at] = (u32)sp.shB; } else *flag = 1u;
+                // no value bits left below the two digits: the rows of this sub-bucket are EQUAL (a load's input may repeat a value; distinct rows
+                // cannot get here) -- equal rows are in order wherever they lie, as in k_rs_big
+                if (sp.shB > 0) {
+                    const u32 at = atomicAdd(&ovs[0], 1u);
+                    if (at < RS2_OVS_CAP) { ovs[1 + 3 * at] = base + o; ovs[2 + 3 * at] = nd; ovs[3 + 3 * at] = (u32)sp.shB; } else *flag = 1u;
+                }
             }
             continue;
         }

@@ -198,6 +198,22 @@ class _ColorMarkStats(C.Structure):
 
 COLORS_INVERT = 1
 
+
+class _LoadStats(C.Structure):
+    _fields_ = [
+        ("n_in", C.c_uint64),
+        ("n_distinct", C.c_uint64),
+        ("n_rows", C.c_uint64),
+        ("n_below", C.c_uint64),
+        ("n_above", C.c_uint64),
+        ("n_kmers", C.c_uint64),
+        ("n_saturated", C.c_uint64),
+        ("sorted_input", C.c_uint64),
+    ]
+
+
+LOAD_COMBINE = {"sum": 0, "max": 1, "min": 2, "unique": 3}      # DSKGPU_LOAD_*
+
 # one summary of dskgpu_read_summaries_table (include/dskgpu.h: SUMMARY), 32 bytes
 READ_SUMMARY_DTYPE = np.dtype([("start", "<u8"), ("sum", "<u8"), ("len", "<u4"), ("n_valid", "<u4"), ("n_solid", "<u4"), ("median", "<u4")])
 READS_INVERT = 1
@@ -381,6 +397,7 @@ EXPORTS = [
     "dskgpu_read_summaries", "dskgpu_read_summaries_table", "dskgpu_read_marks", "dskgpu_select_reads",
     "dskgpu_colors_begin", "dskgpu_colors_add", "dskgpu_colors_rows", "dskgpu_colors_unitigs",
     "dskgpu_colors_pairs", "dskgpu_colors_load", "dskgpu_colors_marks",
+    "dskgpu_load_rows",
     "dskgpu_variants", "dskgpu_variants_table", "dskgpu_variants_stream",
     "dskgpu_k_encode", "dskgpu_k_enumerate", "dskgpu_k_minimizers",
     "dskgpu_group_create", "dskgpu_group_destroy", "dskgpu_group_last_error", "dskgpu_group_size", "dskgpu_group_ctx",
@@ -549,6 +566,8 @@ def load_library():
     lib.dskgpu_colors_pairs.restype = C.c_int
     lib.dskgpu_colors_load.argtypes = [vp, vp, u32]
     lib.dskgpu_colors_load.restype = C.c_int
+    lib.dskgpu_load_rows.argtypes = [vp, vp, vp, C.c_uint64, u32, C.POINTER(_LoadStats)]
+    lib.dskgpu_load_rows.restype = C.c_int
     lib.dskgpu_colors_marks.argtypes = [vp, C.POINTER(_ColorRule), vp, C.POINTER(_ColorMarkStats)]
     lib.dskgpu_colors_marks.restype = C.c_int
     lib.dskgpu_k_encode.argtypes = [vp, vp, u64, vp, vp]
@@ -1303,6 +1322,90 @@ class KmerCounter:
         torch.cuda.current_stream(t.device).synchronize()         # the context's stream is not torch's: the matrix is written before the copy reads it
         self.colors_load(t.data_ptr() if n else 0, int(t.shape[1]))
 
+    # -- saved rows loaded into the context, counts merged (include/dskgpu.h: dskgpu_load_rows)
+    def load_rows(self, d_kmers: int, d_abundance: int, n: int, combine: str = "sum") -> dict:
+        """d_kmers: n values of `words` u64 each on the device (row-major, LSW first, 8-byte aligned); d_abundance: n u32 on the device; any
+        order, any repeats, not memory of this context.  The rows become the result as if a count had found them: equal values combined
+        (combine: "sum", "max", "min", or "unique" = a repeat is an error), filtered by abundance_min / abundance_max, in the global order.
+        -> the load's stats (n_in, n_distinct, n_rows, n_below, n_above, n_kmers, n_saturated, sorted_input)."""
+        if combine not in LOAD_COMBINE:
+            raise ValueError("load_rows: combine must be one of %s" % ", ".join(LOAD_COMBINE))
+        st = _LoadStats()
+        self._ck(self._lib.dskgpu_load_rows(self._h, C.c_void_p(d_kmers) if d_kmers else None, C.c_void_p(d_abundance) if d_abundance else None,
+                                            n, LOAD_COMBINE[combine], C.byref(st)))
+        self._n_colors = 0
+        return _stats_dict(st)
+
+    def load_rows_tensor(self, kmers, abundance, combine: str = "sum") -> dict:
+        """kmers: CUDA tensor [n, words] of 64-bit values (int64 or uint64 bit patterns, LSW first; [n] for words == 1); abundance: CUDA tensor
+        [n] of 32-bit values (int32 or uint32 bit patterns), both on the context's device; as load_rows."""
+        import torch
+        if not kmers.is_cuda or kmers.element_size() != 8 or not abundance.is_cuda or abundance.element_size() != 4 or abundance.is_floating_point() or kmers.is_floating_point():
+            raise ValueError("load_rows_tensor: CUDA tensors of 64-bit values and of 32-bit abundances are needed")
+        if kmers.device.index != self.device or abundance.device.index != self.device:
+            raise ValueError("load_rows_tensor: the tensors must be on the context's device, cuda:%d" % self.device)
+        kmers, abundance = kmers.contiguous(), abundance.contiguous()
+        n = abundance.numel()
+        if kmers.numel() != n * self.words or (kmers.dim() == 2 and kmers.shape[1] != self.words) or kmers.dim() > 2 or (kmers.dim() == 1 and self.words != 1 and n):
+            raise ValueError("load_rows_tensor: kmers must be [n, %d] for %d abundances" % (self.words, n))
+        torch.cuda.current_stream(kmers.device).synchronize()     # the context's stream is not torch's: the rows are written before the load reads them
+        return self.load_rows(kmers.data_ptr() if n else 0, abundance.data_ptr() if n else 0, n, combine)
+
+    def load_rows_numpy(self, kmers, abundance, combine: str = "sum") -> dict:
+        """kmers: uint64 [n, words] (or [n] for words == 1), abundance: uint32 [n], host arrays: copied up, then as load_rows."""
+        import torch
+        kmers = np.ascontiguousarray(kmers, dtype=np.uint64).reshape(-1, self.words)
+        abundance = np.ascontiguousarray(abundance, dtype=np.uint32).reshape(-1)
+        if kmers.shape[0] != abundance.shape[0]:
+            raise ValueError("load_rows_numpy: %d k-mers for %d abundances" % (kmers.shape[0], abundance.shape[0]))
+        dev = torch.device("cuda", self.device)
+        return self.load_rows_tensor(torch.from_numpy(kmers.view(np.int64)).to(dev), torch.from_numpy(abundance.view(np.int32)).to(dev), combine)
+
+    def save_rows(self, path: str) -> None:
+        """The rows of the last result -- and the colour matrix when one is kept -- into one .npz: k, kmers, abundance [, colors]."""
+        kmers, ab = self.rows()
+        data = {"k": np.array(self.kmer_size, dtype=np.int64), "kmers": kmers, "abundance": ab}
+        if getattr(self, "_n_colors", 0):
+            try:
+                counts, _ = self.colors_rows_tensor(1)
+                data["colors"] = counts.cpu().numpy().view(np.uint32)
+            except DskGpuError:                                  # (no matrix is kept any more: the rows changed since)
+                pass
+        with open(path, "wb") as f:
+            np.savez(f, **data)
+
+    def load_saved(self, path: str, combine: str = "unique") -> dict:
+        """What save_rows wrote becomes the result (load_rows_numpy); a saved colour matrix is put back (colors_load) when the load kept every
+        saved row in its place -- otherwise the matrix no longer fits the rows, and this raises and says why."""
+        import torch
+        with np.load(path) as z:
+            k = int(z["k"])
+            kmers, ab = z["kmers"], z["abundance"]
+            colors = z["colors"] if "colors" in z.files else None
+        if k != self.kmer_size:
+            raise ValueError("load_saved: %s holds rows of k = %d, this context counts k = %d" % (path, k, self.kmer_size))
+        kmers = np.ascontiguousarray(kmers, dtype=np.uint64).reshape(-1, self.words)
+        if colors is not None:
+            if colors.shape[0] != kmers.shape[0]:
+                raise ValueError("load_saved: %s holds %d lines of colours for %d rows" % (path, colors.shape[0], kmers.shape[0]))
+            # the matrix has one line per saved row: rows saved in partition order are put in the global order with their lines here,
+            # so that line r still belongs to row r once the load has ordered the rows
+            order = np.lexsort(tuple(kmers[:, w] for w in range(self.words)))
+            kmers, ab, colors = kmers[order], ab[order], colors[order]
+        st = self.load_rows_numpy(kmers, ab, combine)
+        if colors is not None:
+            if st["n_rows"] != st["n_in"]:
+                raise ValueError("load_saved: the colour matrix of %s is not restored: the load kept %d of the %d saved rows (%d distinct, %d below "
+                                 "abundance_min, %d above abundance_max), and the matrix has one line per saved row"
+                                 % (path, st["n_rows"], st["n_in"], st["n_distinct"], st["n_below"], st["n_above"]))
+            self.colors_load_tensor(torch.from_numpy(np.ascontiguousarray(colors).view(np.int32)).to(torch.device("cuda", self.device)))
+        return st
+
+    def load_ascii(self, path: str, combine: str = "sum") -> dict:
+        """The text `dsk2ascii` writes (`<letters> <abundance>` per line) becomes the result: parse_ascii_rows, then load_rows_numpy."""
+        kmers, ab = parse_ascii_rows(path, self.kmer_size)
+        return self.load_rows_numpy(kmers, ab, combine)
+
     def colors_pairs(self, min_count: int, shared_ptr: int, cross_ptr: int, min_sum_ptr: int, select_ptr: int = 0) -> dict:
         """shared_ptr / cross_ptr / min_sum_ptr: n_colors * n_colors u64 on the device each, any may be 0 <- the pair matrices of the kept
         matrix over the rows whose byte at select_ptr is non-zero (0: every row), cells below min_count taken as 0.  -> the stats: n_rows,
@@ -1770,3 +1873,37 @@ def sample_distances(shared, cross, min_sum) -> dict:
 def kmer_to_string(value: int, k: int) -> str:
     """Kmer<span>::ModelCanonical::toString (utils/dsk2ascii.cpp:104): MSB-first, A C T G = 0 1 2 3."""
     return "".join("ACTG"[(value >> (2 * (k - 1 - i))) & 3] for i in range(k))
+
+
+def parse_ascii_rows(path_or_lines, k: int) -> Tuple[np.ndarray, np.ndarray]:
+    """`dsk2ascii`'s default text -- `<letters> <abundance>` per line, the inverse of kmer_to_string -- as (kmers uint64[n, words] LSW first,
+    abundance uint32[n]).  path_or_lines: a file name or an iterable of lines.  A line of the wrong length, with other letters or with an
+    abundance that is no positive 32-bit number raises ValueError naming the line (1-based)."""
+    words = (k + 31) // 32
+    code = {"A": 0, "C": 1, "T": 2, "G": 3}
+    if isinstance(path_or_lines, (str, bytes, os.PathLike)):
+        with open(path_or_lines, "r") as f:
+            lines = f.read().splitlines()
+    else:
+        lines = [ln.decode() if isinstance(ln, bytes) else ln for ln in path_or_lines]
+    kmers, ab = [], []
+    for no, line in enumerate(lines, 1):
+        line = line.rstrip("\r\n")
+        if not line.strip():
+            continue
+        parts = line.split()
+        if len(parts) != 2:
+            raise ValueError("line %d: expected `<letters> <abundance>`, got %r" % (no, line))
+        letters, count = parts
+        if len(letters) != k:
+            raise ValueError("line %d: %d letters, k is %d" % (no, len(letters), k))
+        value = 0
+        for ch in letters:
+            if ch not in code:
+                raise ValueError("line %d: letter %r is none of A, C, G, T" % (no, ch))
+            value = (value << 2) | code[ch]
+        if not count.isdigit() or not 1 <= int(count) <= 0xFFFFFFFF:
+            raise ValueError("line %d: abundance %r is no number in 1 .. 2^32 - 1" % (no, count))
+        kmers.append([(value >> (64 * w)) & 0xFFFFFFFFFFFFFFFF for w in range(words)])
+        ab.append(int(count))
+    return np.array(kmers, dtype=np.uint64).reshape(-1, words), np.array(ab, dtype=np.uint32)

@@ -957,6 +957,50 @@ typedef struct dskgpu_color_mark_stats { uint64_t n_rows, n_kept, reserved[6]; }
 /* stats (may be NULL): n_rows; n_kept = the rows whose byte is 1. */
 int dskgpu_colors_marks(dskgpu_ctx* ctx, const dskgpu_color_rule* rule, void* d_keep, dskgpu_color_mark_stats* stats);
 
+/* ---- saved rows loaded into a context, counts merged: everything above starts from a count of reads made by this context.  The reference's
+ * whole point is to leave a reusable k-mer table, and its users add the abundances of equal k-mers of two tables (Jellyfish `merge`, KMC
+ * `kmc_tools simple union`, banks counted on different days).  A LOAD IS A COUNT WHOSE INPUT IS (k-mer, abundance) PAIRS INSTEAD OF READS:
+ * equal k-mers are combined, the context's abundance_min / abundance_max filter the combined value, the histogram is taken over all distinct
+ * k-mers, the kept rows become the result in the global order, and every later call (lookups, graph, filter, colours) works as after a count.
+ *   input      d_kmers: n values of words = ceil(k / 32) u64 each, row-major, least-significant word first (the layout of
+ *              dskgpu_partition_copy, dskgpu_query_kmers and dskgpu_k_enumerate), 8-byte aligned; d_abundance: n u32, 4-byte aligned.  Both on
+ *              the device, in any order, with any number of repeats; both are left as they were.  They must NOT be memory the context owns
+ *              (dskgpu_result_device's arrays among it): that is the caller's duty.  n <= 2^32 - 2, the limit of the lookup index and of this
+ *              call: more is DSKGPU_E_ARG.  For k > 64 the limit is n < 2^32 - 65536, that of the row order of four-word rows.
+ *   validity   every value < 4^k and canonical -- value <= revcomp(value) in the order A=0 C=1 T=2 G=3; the palindromes of an even k are
+ *              valid -- and every abundance >= 1; with DSKGPU_LOAD_UNIQUE no value may repeat.  A violation is DSKGPU_E_ARG, and the error
+ *              text names the LOWEST offending input index and what is wrong with it.  A repeat under DSKGPU_LOAD_UNIQUE is looked for once
+ *              every row is valid by itself; the offending index is then the lowest i whose value also stands at some j < i, and the text
+ *              gives the value.  Validation reads only the input: on this error the previous result and everything built on it are untouched.
+ *   combine    DSKGPU_LOAD_SUM: the abundances of equal values added in 64 bits and stored saturated at 2^32 - 1; _MAX, _MIN: the largest /
+ *              smallest; _UNIQUE: equal values are an error.
+ *   result     the distinct values with abundance_min <= combined <= abundance_max, ascending by value over all rows, struct-of-arrays in
+ *              buffers of the context, exactly as a global-order count leaves them.  A load ignores DSKGPU_F_PARTITION_ORDER and
+ *              DSKGPU_F_NO_SORT: the loaded result is always in the global order, its partitions are the n_rows * p / P ranges with
+ *              P = nb_partitions or 4.  A later dskgpu_count follows the flags again.
+ *   record     the load REPLACES the count's record: dskgpu_histogram = hist[min(combined, histo_max)] over all distinct values;
+ *              dskgpu_get_stats: n_bytes 0, n_kmers = the exact 64-bit sum of the INPUT abundances (not of the saturated ones), n_distinct =
+ *              the distinct values, n_solid = the rows kept, n_partitions as above, sort_fallback as the row order reports it, every other
+ *              field 0; the 2-D histogram is forgotten.
+ *   stats      (may be NULL) n_in = n; n_distinct, n_rows, n_kmers as in the record; n_below / n_above: the distinct values filtered out on
+ *              either side; n_saturated: the distinct values whose SUM exceeded 2^32 - 1; sorted_input: 1 when the input was already strictly
+ *              ascending (the order step is then skipped).
+ * State: where a count would drop the old result it goes here too, with the index, compaction, threading, variants, summaries, colours and
+ * filtered rows.  The context's reads, a kept encoding and the sender state are untouched: load, then dskgpu_count, gives what the count
+ * alone gives.  n == 0: DSKGPU_OK, a result with zero rows and an all-zero histogram; null arrays are allowed then.  The call runs on the
+ * context's stream and is synchronous on return.  Stage times: "load check", "load order", "load combine".
+ * Errors: DSKGPU_E_ARG: a null ctx; a null array while n > 0; a misaligned array; combine > 3; n above the limit; an invalid row.
+ * DSKGPU_E_STATE: a context of a group (world_size > 1): a rank owns a slice of the k-mer space and a load knows nothing of it.
+ * DSKGPU_E_NOMEM / DSKGPU_E_DEVICE: as after a failed count, there is no result. */
+#define DSKGPU_LOAD_SUM    0u   /* equal k-mers: abundances added in 64 bits, stored saturated at 2^32 - 1 */
+#define DSKGPU_LOAD_MAX    1u
+#define DSKGPU_LOAD_MIN    2u
+#define DSKGPU_LOAD_UNIQUE 3u   /* equal k-mers are an error (DSKGPU_E_ARG) */
+typedef struct dskgpu_load_stats {
+    uint64_t n_in, n_distinct, n_rows, n_below, n_above, n_kmers, n_saturated, sorted_input;
+} dskgpu_load_stats;            /* 64 bytes */
+int dskgpu_load_rows(dskgpu_ctx* ctx, const void* d_kmers, const void* d_abundance, uint64_t n, uint32_t combine, dskgpu_load_stats* stats);
+
 /* ---- the same call on N GPUs of one node, inside ONE process (what `dsk -nb-gpus N` runs): the reference's
  * single `execute()` (src/DSK.cpp:55-60) still leaves ONE storage with a flat list of solid partitions
  * (utils/dsk2ascii.cpp:61,77).  A group owns one ctx per rank (world_size = n_ranks, rank r on devices[r], its own
